@@ -24,10 +24,16 @@ barrier and the max-reduce of the timing (no data-path collective), on a
 gloo process group with CPU tensors: no RCCL communicator or torch HIP stream
 takes a hardware queue from the engine.
 
-Also reported (never `value`): host_buffers, the streaming rate with the
-input coming from host memory each push (fvad_engine_submit: pinned slots,
-H2D overlapped with the previous push), and cpu_baseline, the oracle's whole
-per-stream path on this host's cores.
+A plain run sets up, warms up, times the --steps pushes, writes the last
+timed push's outputs if --dump-outputs DIR is given, and prints the line; its
+roofline comes from the events of the timed pushes themselves.
+
+With --full also reported (never `value`), each from a run of its own:
+host_buffers, the streaming rate with the input coming from host memory each
+push (fvad_engine_submit: pinned slots, H2D overlapped with the previous
+push); variants, the fp16 engine modes and the long-running VADMachine regime
+on the same workload; roofline.one_engine (with --groups > 1); and
+cpu_baseline, the oracle's whole per-stream path on this host's cores.
 
 Prints ONE JSON line on rank 0.
 """
@@ -64,7 +70,16 @@ def parse():
                     help="staged (bit-exact, default), fused (bit-exact), fp16 (configs[4]: GRU on MFMA, tolerance), "
                          "fp16_fused (configs[4]'s fused FFT -> feature -> GRU kernel, k_fused16; equal to fp16)")
     ap.add_argument("--no-vadm", action="store_true", help="staged: do not run the device VADMachine (k_vadm)")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle on this host (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beyond the headline figure: host_buffers, "
+                         "variants, roofline.one_engine (--groups > 1) and cpu_baseline; each can still be "
+                         "switched off by its own option below")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed push computed (the arrays of "
+                         "Engine.fetch, win_flag as float32, and every stream's VADMachine segments so far) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="--full: time the CPU oracle on this host (rank 0)")
     ap.add_argument("--cpu-streams", type=int, default=48,
                     help="CPU sample: streams 0..N-1 of this rank's partition (every 20th has digital silence)")
     ap.add_argument("--cpu-ticks", type=int, default=0,
@@ -74,7 +89,8 @@ def parse():
     ap.add_argument("--pmc-json", default=None,
                     help="PMC byte counts (tools/profile.sh); default profiles/pmc_traffic[_<mode>].json")
     ap.add_argument("--host-rate", type=int, default=1,
-                    help="also time pushes from host buffers (PCIe-inclusive; reported as host_buffers, never value)")
+                    help="--full: also time pushes from host buffers (PCIe-inclusive; reported as host_buffers, "
+                         "never value)")
     ap.add_argument("--cpu-stub", action="store_true",
                     help="no GPU: gloo ranks with a stub engine (tests the launcher, barrier and max-reduce)")
     ap.add_argument("--rehearse-on-gpu0", action="store_true",
@@ -86,14 +102,16 @@ def parse():
                          "sub-partitions pushing concurrently, k_prep3 / VADMachines on shared side streams "
                          "(opt-in: the gain depends on the runtime's hardware-queue placement, DESIGN.md 8 r5)")
     ap.add_argument("--one-engine-leg", type=int, default=1,
-                    help="with --groups > 1, also time one engine over all the rank's streams "
+                    help="--full with --groups > 1: also time one engine over all the rank's streams "
                          "(roofline.one_engine: each kernel alone on the GPU)")
     ap.add_argument("--variants", type=int, default=1,
-                    help="staged runs: also time the fp16 engine mode (configs[4]'s variant) on the same "
+                    help="--full, staged runs: also time the fp16 engine mode (configs[4]'s variant) on the same "
                          "workload and report it under `variants` (never `value`)")
     a = ap.parse_args()
     if a.groups < 1 or a.streams_per_gpu % a.groups:
         ap.error("--groups must divide --streams-per-gpu")
+    if not a.full:  # a plain run does only what `value` needs
+        a.cpu_baseline = a.host_rate = a.one_engine_leg = a.variants = 0
     return a
 
 
@@ -405,6 +423,38 @@ def host_rate(grp, args, rank, dist, torch, base):
                     "push's H2D copy and k_prep3 and the last push's drain)" % (args.steps, DEPTH + 2)}
 
 
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(grp, args, rank, vadm):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    timed push, as DIR/<name>.npy (rank r > 0: <name>.rank<r>.npy) -- the
+    per-tick outputs of that push (Engine.fetch: vad, ratio, win_flag,
+    win_ratio, win_vad, band; [ticks][streams]..., float32) and, with device
+    VADMachines, `segments`: float64 rows (stream, sample_from, sample_to,
+    debug_rnn_vad, debug_avg_speech_vol_ratio) of every segment the machines
+    have emitted up to that push.  The input is the seeded synthetic audio, so
+    the same arguments give the same arrays from run to run.  Above 64 MiB in
+    all, a fixed seeded sample of the streams is kept (`streams`: their
+    indices within the rank's partition)."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    outs = [e.fetch(args.ticks) for e in grp.engines]
+    arrays = {k: np.concatenate([o[k] for o in outs], axis=1).astype(np.float32) for k in outs[0]}
+    keep = np.arange(grp.B)
+    per_stream = sum(v.nbytes for v in arrays.values()) // grp.B + 8  # + its entry of `streams`
+    if per_stream * grp.B > DUMP_CAP_BYTES // 2:  # the other half is the segments' bound
+        keep = np.sort(np.random.default_rng(0).choice(grp.B, max(1, DUMP_CAP_BYTES // 2 // per_stream),
+                                                       replace=False))
+        arrays = {k: np.ascontiguousarray(v[:, keep]) for k, v in arrays.items()}
+    arrays["streams"] = keep.astype(np.float64)
+    if vadm:
+        rows = [(s,) + seg for s in keep for seg in grp.segments(int(s))]
+        arrays["segments"] = np.array(rows, np.float64).reshape(-1, 5)[: DUMP_CAP_BYTES // 2 // 40]
+    for k, v in arrays.items():
+        np.save(os.path.join(args.dump_outputs, k + ("" if rank == 0 else ".rank%d" % rank) + ".npy"), v)
+
+
 def gather_kernel_tables(kt, dist, torch, rank):
     """Every rank's per-kernel event times; the line reports the max over ranks
     per kernel (the slowest rank sets the step) and which rank that was."""
@@ -476,6 +526,8 @@ def main():
     kt, ranks = gather_kernel_tables(kt_local, dist, torch, rank)
     value = aggregate_rate(B * Ch * T, world, args.steps, elapsed)
     ms_per_step = 1000.0 * elapsed / args.steps
+    if args.dump_outputs:
+        dump_outputs(eng, args, rank, args.mode != "fused" and not args.no_vadm)
 
     host = host_rate(eng, args, rank, dist, torch, base) if args.host_rate else None
     rss_stage("after_host_buffers")
@@ -556,6 +608,7 @@ def main():
     line = {
         "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
+        "full": bool(args.full),
         "vs_baseline": None, "dtype": "f32" if args.mode not in ("fp16", "fp16_fused") else "f32+f16 (GRU gates: f16 MFMA, f32 accumulate)",
         "data": "synthetic" + ("; REHEARSAL: %d ranks sharing GPU 0 over gloo (--rehearse-on-gpu0), not a "
                                "scaling figure" % world if args.rehearse_on_gpu0 else ""),
