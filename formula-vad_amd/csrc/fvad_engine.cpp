@@ -472,7 +472,7 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   }
   if (hi - lo + 1 > 256 && (c.mode == FVAD_MODE_FUSED || c.fft_size == 2048))
     return fail(FVAD_EINVAL, "reported bins must span <= 256");
-  if (c.mode != FVAD_MODE_STAGED && c.mode != FVAD_MODE_FUSED && !fp16_mode(c.mode))
+  if (c.mode != FVAD_MODE_STAGED && c.mode != FVAD_MODE_FUSED && !fp16_mode(c.mode) && c.mode != FVAD_MODE_F32_FAST)
     return fail(FVAD_EINVAL, "unknown engine mode");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FVAD_EDEVICE, "no HIP device available");
@@ -802,6 +802,7 @@ int launch_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bo
   a.gru16_frags = e->d_gru16;
   a.gru16_bias = e->d_gru16_bias;
   a.fuse16 = e->cfg.mode == FVAD_MODE_FP16_FUSED;
+  a.fma = e->cfg.mode == FVAD_MODE_F32_FAST;
   for (int m = 0; m < fvad::rnnimg::kMats; m++) a.rnn_act[m] = e->rnn_act[m];
   a.ys = e->d_ys;
   a.ring = e->d_ring;
@@ -1487,6 +1488,7 @@ extern "C" const char *fvad_engine_kernel_name(const fvad_engine *e, int i) {
   if (!e || i < 0 || i >= e->n_kernels) return nullptr;
   if (e->cfg.mode == FVAD_MODE_FUSED) return i == 0 ? "k_prep" : "k_frame";
   if (fp16_mode(e->cfg.mode) && i == 6) return e->cfg.mode == FVAD_MODE_FP16_FUSED ? "k_fused16" : "k_gru16";
+  if (e->cfg.mode == FVAD_MODE_F32_FAST && e->cfg.use_denoiser && i == 6) return "k_rnn3f";
   if (e->olafb && i == 8) return "k_olafb";
   return fvad::staged_kernel_name(i);
 }

@@ -140,6 +140,8 @@ struct StagedArgs {
   float *out_vad, *out_win_ratio, *out_win_vad, *out_band, *out_den;
   int *out_win_flag;
   int raw_s16;
+  int fma;                 // FVAD_MODE_F32_FAST: k_rnn3f (fused multiply-add terms) runs in k_rnn3's place
+                           //   (here, in what was padding, every other field keeps its offset)
   VadmArgs vadm;
   unsigned *work;          // [kWorkCounters] dynamic group counters of the persistent kernels
   unsigned long long *stamps;  // diagnostic build only (FVAD_STAMPS): per-phase cycles of k_rnn3

@@ -794,27 +794,47 @@ struct VecT<4> {
 __device__ __forceinline__ float wbyte(uint2 w8, int u) {
   return (float)(signed char)((u < 4 ? w8.x : w8.y) >> (8 * (u & 3)));
 }
-template <int SL>
+// (FMA, through every helper below: k_rnn3f's form of a term, one fused
+// multiply-add -- a single rounding -- where k_rnn3 multiplies, then adds)
+template <int SL, bool FMA>
 __device__ __forceinline__ void mac(float (&acc)[SL], float w, const typename VecT<SL>::T &v) {
-  acc[0] = acc[0] + w * v.x;
-  acc[1] = acc[1] + w * v.y;
-  if constexpr (SL == 4) {
-    acc[2] = acc[2] + w * v.z;
-    acc[3] = acc[3] + w * v.w;
+  if constexpr (FMA) {
+    acc[0] = __builtin_fmaf(w, v.x, acc[0]);
+    acc[1] = __builtin_fmaf(w, v.y, acc[1]);
+    if constexpr (SL == 4) {
+      acc[2] = __builtin_fmaf(w, v.z, acc[2]);
+      acc[3] = __builtin_fmaf(w, v.w, acc[3]);
+    }
+  } else {
+    acc[0] = acc[0] + w * v.x;
+    acc[1] = acc[1] + w * v.y;
+    if constexpr (SL == 4) {
+      acc[2] = acc[2] + w * v.z;
+      acc[3] = acc[3] + w * v.w;
+    }
   }
 }
-template <int SL>
+template <int SL, bool FMA>
 __device__ __forceinline__ void mac_r(float (&acc)[SL], float w, const typename VecT<SL>::T &sv,
                                       const typename VecT<SL>::T &rv) {
-  acc[0] = acc[0] + w * sv.x * rv.x;
-  acc[1] = acc[1] + w * sv.y * rv.y;
-  if constexpr (SL == 4) {
-    acc[2] = acc[2] + w * sv.z * rv.z;
-    acc[3] = acc[3] + w * sv.w * rv.w;
+  if constexpr (FMA) {
+    acc[0] = __builtin_fmaf(w * sv.x, rv.x, acc[0]);
+    acc[1] = __builtin_fmaf(w * sv.y, rv.y, acc[1]);
+    if constexpr (SL == 4) {
+      acc[2] = __builtin_fmaf(w * sv.z, rv.z, acc[2]);
+      acc[3] = __builtin_fmaf(w * sv.w, rv.w, acc[3]);
+    }
+  } else {
+    acc[0] = acc[0] + w * sv.x * rv.x;
+    acc[1] = acc[1] + w * sv.y * rv.y;
+    if constexpr (SL == 4) {
+      acc[2] = acc[2] + w * sv.z * rv.z;
+      acc[3] = acc[3] + w * sv.w * rv.w;
+    }
   }
 }
 
-template <int n, int S, int SL>
+template <int n, int S, int SL, bool FMA>
 __device__ __forceinline__ void mv_seg(const int8_t *__restrict__ wc, const float *vT, int s0, float (&acc)[SL]) {
   typedef typename VecT<SL>::T V;
   constexpr int nb = n / 8, r = n % 8;
@@ -825,17 +845,17 @@ __device__ __forceinline__ void mv_seg(const int8_t *__restrict__ wc, const floa
 #pragma unroll
     for (int u = 0; u < 8; u++) v[u] = *reinterpret_cast<const V *>(vT + (jb * 8 + u) * S + s0);
 #pragma unroll
-    for (int u = 0; u < 8; u++) mac<SL>(acc, wbyte(w8, u), v[u]);
+    for (int u = 0; u < 8; u++) mac<SL, FMA>(acc, wbyte(w8, u), v[u]);
   }
   if (r) {
     const uint2 w8 = *reinterpret_cast<const uint2 *>(wc + nb * 8);
 #pragma unroll
-    for (int u = 0; u < r; u++) mac<SL>(acc, wbyte(w8, u), *reinterpret_cast<const V *>(vT + (nb * 8 + u) * S + s0));
+    for (int u = 0; u < r; u++) mac<SL, FMA>(acc, wbyte(w8, u), *reinterpret_cast<const V *>(vT + (nb * 8 + u) * S + s0));
   }
 }
 
 // GRU candidate recurrent segment: acc[q] += (w[j] * state[j][q]) * r[j][q]
-template <int n, int S, int SL>
+template <int n, int S, int SL, bool FMA>
 __device__ __forceinline__ void mv_seg_r(const int8_t *__restrict__ wc, const float *sT, const float *rT, int s0,
                                          float (&acc)[SL]) {
   typedef typename VecT<SL>::T V;
@@ -850,7 +870,7 @@ __device__ __forceinline__ void mv_seg_r(const int8_t *__restrict__ wc, const fl
       rv[u] = *reinterpret_cast<const V *>(rT + (jb * 8 + u) * S + s0);
     }
 #pragma unroll
-    for (int u = 0; u < 8; u++) mac_r<SL>(acc, wbyte(w8, u), sv[u], rv[u]);
+    for (int u = 0; u < 8; u++) mac_r<SL, FMA>(acc, wbyte(w8, u), sv[u], rv[u]);
   }
 }
 
@@ -859,25 +879,25 @@ struct RnnIn {
   const float *v0, *v1, *v2;
 };
 
-template <int m, int S, int SL>
+template <int m, int S, int SL, bool FMA>
 __device__ __forceinline__ void rnn_inputs(const int8_t *wc, const RnnIn &in, int s0, float (&acc)[SL]) {
   constexpr int n0 = rnnimg::kSegs[m][0];
-  mv_seg<n0, S, SL>(wc, in.v0, s0, acc);
+  mv_seg<n0, S, SL, FMA>(wc, in.v0, s0, acc);
   if constexpr (m == 3 || m == 4 || m == 5 || m == 6) {
     constexpr int n1 = rnnimg::kSegs[m][1], n2 = rnnimg::kSegs[m][2];
-    mv_seg<n1, S, SL>(wc + rnnimg::seg_off(m, 1), in.v1, s0, acc);
-    mv_seg<n2, S, SL>(wc + rnnimg::seg_off(m, 2), in.v2, s0, acc);
+    mv_seg<n1, S, SL, FMA>(wc + rnnimg::seg_off(m, 1), in.v1, s0, acc);
+    mv_seg<n2, S, SL, FMA>(wc + rnnimg::seg_off(m, 2), in.v2, s0, acc);
   }
 }
 
 // input segments [G0, G1) of matrix m (a sum split across phases continues
 // where the stored partial sum stopped: the same adds in the same order)
-template <int m, int S, int SL, int G0, int G1>
+template <int m, int S, int SL, int G0, int G1, bool FMA>
 __device__ __forceinline__ void rnn_segs(const int8_t *wc, const RnnIn &in, int s0, float (&acc)[SL]) {
-  if constexpr (G0 <= 0 && G1 > 0) mv_seg<rnnimg::kSegs[m][0], S, SL>(wc, in.v0, s0, acc);
+  if constexpr (G0 <= 0 && G1 > 0) mv_seg<rnnimg::kSegs[m][0], S, SL, FMA>(wc, in.v0, s0, acc);
   if constexpr (m == 3 || m == 4 || m == 5 || m == 6) {
-    if constexpr (G0 <= 1 && G1 > 1) mv_seg<rnnimg::kSegs[m][1], S, SL>(wc + rnnimg::seg_off(m, 1), in.v1, s0, acc);
-    if constexpr (G0 <= 2 && G1 > 2) mv_seg<rnnimg::kSegs[m][2], S, SL>(wc + rnnimg::seg_off(m, 2), in.v2, s0, acc);
+    if constexpr (G0 <= 1 && G1 > 1) mv_seg<rnnimg::kSegs[m][1], S, SL, FMA>(wc + rnnimg::seg_off(m, 1), in.v1, s0, acc);
+    if constexpr (G0 <= 2 && G1 > 2) mv_seg<rnnimg::kSegs[m][2], S, SL, FMA>(wc + rnnimg::seg_off(m, 2), in.v2, s0, acc);
   }
 }
 template <int SL>
@@ -907,7 +927,7 @@ __device__ __forceinline__ void acc_store(const float (&acc)[SL], float *p) {
 // (tasks t = tid, tid + NT, ...; NT = 0: the single task tid)
 // (PART 3: b + input segment 0 only, stored to preT [c][S]; PART 5: from
 // preT, the remaining input segments and the state)
-template <int m, int S, int G, int NT, int PART = 0>
+template <bool FMA, int m, int S, int G, int NT, int PART = 0>
 __device__ __forceinline__ void rnn_gates(const int8_t *W, const RnnIn &in, const float *stT, float *outT, int act,
                                           const float *tt, int tid, float *preT = nullptr) {
   constexpr int SL = S / G, cols = rnnimg::kCols[m];
@@ -919,20 +939,20 @@ __device__ __forceinline__ void rnn_gates(const int8_t *W, const RnnIn &in, cons
     float acc[SL];
     if constexpr (PART == 5) {
       acc_load<SL>(acc, preT + c * S + s0);
-      rnn_segs<m, S, SL, 1, 3>(wc, in, s0, acc);
+      rnn_segs<m, S, SL, 1, 3, FMA>(wc, in, s0, acc);
     } else {
       const float b = (float)W[ob + c];
 #pragma unroll
       for (int q = 0; q < SL; q++) acc[q] = b;
       if constexpr (PART == 3) {
-        rnn_segs<m, S, SL, 0, 1>(wc, in, s0, acc);
+        rnn_segs<m, S, SL, 0, 1, FMA>(wc, in, s0, acc);
         acc_store<SL>(acc, preT + c * S + s0);
         continue;
       } else {
-        rnn_inputs<m, S, SL>(wc, in, s0, acc);
+        rnn_inputs<m, S, SL, FMA>(wc, in, s0, acc);
       }
     }
-    if constexpr (gst >= 0) mv_seg<rnnimg::kSegs[m][gst], S, SL>(wc + rnnimg::seg_off(m, gst), stT, s0, acc);
+    if constexpr (gst >= 0) mv_seg<rnnimg::kSegs[m][gst], S, SL, FMA>(wc + rnnimg::seg_off(m, gst), stT, s0, acc);
 #pragma unroll
     for (int q = 0; q < SL; q++) outT[c * S + s0 + q] = activate(tt, act, kWs * acc[q]);
   }
@@ -944,7 +964,7 @@ __device__ __forceinline__ void rnn_gates(const int8_t *W, const RnnIn &in, cons
 // gate, so it can run one phase early: PART 1 stores the prefix to preT
 // ([c][S]) and returns, PART 2 starts from preT and adds the recurrent terms
 // -- the same sequence of f32 adds as PART 0, split at a store.
-template <int m, int S, int G, int NT, int PART = 0>
+template <bool FMA, int m, int S, int G, int NT, int PART = 0>
 __device__ __forceinline__ void rnn_cand(const int8_t *W, const RnnIn &in, const float *stT, const float *zrT,
                                          float *newT, const int *actv, int act, const float *tt, int tid,
                                          float *preT = nullptr) {
@@ -957,21 +977,21 @@ __device__ __forceinline__ void rnn_cand(const int8_t *W, const RnnIn &in, const
     float acc[SL];
     if constexpr (PART == 2 || PART == 4) {
       acc_load<SL>(acc, preT + c * S + s0);
-      if constexpr (PART == 4) rnn_segs<m, S, SL, 1, 3>(wc, in, s0, acc);
+      if constexpr (PART == 4) rnn_segs<m, S, SL, 1, 3, FMA>(wc, in, s0, acc);
     } else {
       const float b = (float)W[ob + c];
 #pragma unroll
       for (int q = 0; q < SL; q++) acc[q] = b;
       if constexpr (PART == 3)
-        rnn_segs<m, S, SL, 0, 1>(wc, in, s0, acc);
+        rnn_segs<m, S, SL, 0, 1, FMA>(wc, in, s0, acc);
       else
-        rnn_inputs<m, S, SL>(wc, in, s0, acc);
+        rnn_inputs<m, S, SL, FMA>(wc, in, s0, acc);
     }
     if constexpr (PART == 1 || PART == 3 || PART == 4) {
       acc_store<SL>(acc, preT + c * S + s0);
       continue;
     }
-    mv_seg_r<rnnimg::kSegs[m][gst], S, SL>(wc + rnnimg::seg_off(m, gst), stT, zrT + N * S, s0, acc);
+    mv_seg_r<rnnimg::kSegs[m][gst], S, SL, FMA>(wc + rnnimg::seg_off(m, gst), stT, zrT + N * S, s0, acc);
 #pragma unroll
     for (int q = 0; q < SL; q++) {
       const int o = c * S + s0 + q;
@@ -1016,7 +1036,11 @@ __device__ __forceinline__ void rnn_cand(const int8_t *W, const RnnIn &in, const
 #define FVAD_PRIO 134
 #endif
 constexpr int kR3S = 8, kR3G = 2, kR3NT = 1024;
-__global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) {
+// FMA = false: k_rnn3; true: k_rnn3f (FVAD_MODE_F32_FAST), the same plan with
+// every GRU and dense term a fused multiply-add.  (a by value, as a kernel
+// takes it: k_rnn3 then compiles to the instructions it had as a plain kernel)
+template <bool FMA>
+__device__ __forceinline__ void rnn3_body(StagedArgs a) {
   constexpr int S = kR3S, G = kR3G, NT = kR3NT;
   struct Lds {
     alignas(16) float featT[8][44 * S];  // frame f in slot f & 7
@@ -1244,20 +1268,20 @@ __global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) {
     const int wv = tq >> 6, ln = tq & 63;
     if (wv < 6) {
       if (fd >= 0 && fd < maxnf)
-        rnn_gates<5, S, G, 0, 5>(L.W, RnnIn{L.gvT[fd & 3], L.gnT[fd & 1], L.featT[fd & 7]}, L.gdT[(fd + 1) & 1],
+        rnn_gates<FMA, 5, S, G, 0, 5>(L.W, RnnIn{L.gvT[fd & 3], L.gnT[fd & 1], L.featT[fd & 7]}, L.gdT[(fd + 1) & 1],
                                  L.zrd, kActSigmoid, L.tt, tq, L.zpre);
     } else if (wv == 6 || wv == 7 || wv == 10) {
       if (fn >= 0 && fn < maxnf)
-        rnn_gates<3, S, G, 0>(L.W, RnnIn{L.doutT[fn & 3], L.gvT[fn & 3], L.featT[fn & 7]}, L.gnT[(fn + 1) & 1], L.zrn,
+        rnn_gates<FMA, 3, S, G, 0>(L.W, RnnIn{L.doutT[fn & 3], L.gvT[fn & 3], L.featT[fn & 7]}, L.gnT[(fn + 1) & 1], L.zrn,
                               kActSigmoid, L.tt, (wv == 10 ? 128 : 64 * (wv - 6)) + ln);
     } else if (wv == 11 || wv == 14) {
       if (fv >= 0 && fv < maxnf)
-        rnn_gates<1, S, G, 0>(L.W, RnnIn{L.doutT[fv & 3], nullptr, nullptr}, L.gvT[(fv + 3) & 3], L.zrv, kActSigmoid,
+        rnn_gates<FMA, 1, S, G, 0>(L.W, RnnIn{L.doutT[fv & 3], nullptr, nullptr}, L.gvT[(fv + 3) & 3], L.zrv, kActSigmoid,
                               L.tt, (wv == 14 ? 64 : 0) + ln);
     } else if (wv == 12 || wv == 13 || wv == 15) {
       // denoise candidate input prefixes of frame t-3
       if (fd >= 0 && fd < maxnf)
-        rnn_cand<6, S, G, 0, 4>(L.W, RnnIn{L.gvT[fd & 3], L.gnT[fd & 1], L.featT[fd & 7]}, nullptr, nullptr, nullptr,
+        rnn_cand<FMA, 6, S, G, 0, 4>(L.W, RnnIn{L.gvT[fd & 3], L.gnT[fd & 1], L.featT[fd & 7]}, nullptr, nullptr, nullptr,
                                 nullptr, 0, nullptr, (wv == 15 ? 128 : 64 * (wv - 12)) + ln, L.dhp[fd & 1]);
     } else if (wv == 8 && ln < 48) {  // gain smoothing of frame t-5
       gains(t - 5, ln, 48);
@@ -1276,46 +1300,46 @@ __global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) {
     const int fo = t - 4;
     if (wv < 3) {
       if (fd >= 0 && fd < maxnf)
-        rnn_cand<6, S, G, 0, 2>(L.W, RnnIn{nullptr, nullptr, nullptr}, L.gdT[(fd + 1) & 1], L.zrd, L.gdT[fd & 1],
+        rnn_cand<FMA, 6, S, G, 0, 2>(L.W, RnnIn{nullptr, nullptr, nullptr}, L.gdT[(fd + 1) & 1], L.zrd, L.gdT[fd & 1],
                                 L.act[fd & 7], ra[6], L.tt, tq, L.dhp[fd & 1]);
     } else if (wv == 3 || wv == 6) {
       if (FVAD_PRIO & 2) __builtin_amdgcn_s_setprio(3);
       if (fn >= 0 && fn < maxnf)
-        rnn_cand<4, S, G, 0>(L.W, RnnIn{L.doutT[fn & 3], L.gvT[fn & 3], L.featT[fn & 7]}, L.gnT[(fn + 1) & 1], L.zrn,
+        rnn_cand<FMA, 4, S, G, 0>(L.W, RnnIn{L.doutT[fn & 3], L.gvT[fn & 3], L.featT[fn & 7]}, L.gnT[(fn + 1) & 1], L.zrn,
                              L.gnT[fn & 1], L.act[fn & 7], ra[4], L.tt, (wv == 6 ? 64 : 0) + ln);
       if (FVAD_PRIO & 2) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 5) {
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(2);
       if (fv >= 0 && fv < maxnf)
-        rnn_cand<2, S, G, 0>(L.W, RnnIn{L.doutT[fv & 3], nullptr, nullptr}, L.gvT[(fv + 3) & 3], L.zrv, L.gvT[fv & 3],
+        rnn_cand<FMA, 2, S, G, 0>(L.W, RnnIn{L.doutT[fv & 3], nullptr, nullptr}, L.gvT[(fv + 3) & 3], L.zrv, L.gvT[fv & 3],
                              L.act[fv & 7], ra[2], L.tt, ln);
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 7) {
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(2);
       if (t < maxnf)
-        rnn_gates<0, S, G, 0>(L.W, RnnIn{L.featT[t & 7], nullptr, nullptr}, nullptr, L.doutT[t & 3], ra[0], L.tt, ln);
+        rnn_gates<FMA, 0, S, G, 0>(L.W, RnnIn{L.featT[t & 7], nullptr, nullptr}, nullptr, L.doutT[t & 3], ra[0], L.tt, ln);
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 4) {
       if (FVAD_PRIO & 4) __builtin_amdgcn_s_setprio(2);
       if (fo >= 0 && fo < maxnf)
-        rnn_gates<7, S, G, 0>(L.W, RnnIn{L.gdT[fo & 1], nullptr, nullptr}, nullptr, L.gout[fo & 1], ra[7], L.tt, ln);
+        rnn_gates<FMA, 7, S, G, 0>(L.W, RnnIn{L.gdT[fo & 1], nullptr, nullptr}, nullptr, L.gout[fo & 1], ra[7], L.tt, ln);
       if (FVAD_PRIO & 4) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 8 && ln < G) {
       // vad_output(t-2) -> L.vo, stored by the next step's P1
       if (fn >= 0 && fn < maxnf)
-        rnn_gates<8, S, G, 0>(L.W, RnnIn{L.gvT[fn & 3], nullptr, nullptr}, nullptr, L.vo, ra[8], L.tt, ln);
+        rnn_gates<FMA, 8, S, G, 0>(L.W, RnnIn{L.gvT[fn & 3], nullptr, nullptr}, nullptr, L.vo, ra[8], L.tt, ln);
     } else if (tq >= kP2Feat && tq < kP2Feat + 192) {  // features of t+1 on waves 9..11
       for (int idx = tq - kP2Feat; t + 1 < maxnf && idx < kFeatItems; idx += 192) feat_c(t + 1, idx);
     } else if (wv >= 12 && wv <= 14) {  // denoise z|r of frame t-2: b + the vad-state segment
       const int fz = t - 2;
       if (fz >= 0 && fz < maxnf)
-        rnn_gates<5, S, G, 192, 3>(L.W, RnnIn{L.gvT[fz & 3], nullptr, nullptr}, nullptr, nullptr, kActSigmoid, L.tt,
+        rnn_gates<FMA, 5, S, G, 192, 3>(L.W, RnnIn{L.gvT[fz & 3], nullptr, nullptr}, nullptr, nullptr, kActSigmoid, L.tt,
                                    tq - 768, L.zpre);
     } else if (wv == 15) {  // denoise candidates of frame t-2: b + the vad-state segment
       const int fz = t - 2;
       if (FVAD_PRIO & 128) __builtin_amdgcn_s_setprio(2);
       if (fz >= 0 && fz < maxnf)
-        rnn_cand<6, S, G, 64, 3>(L.W, RnnIn{L.gvT[fz & 3], nullptr, nullptr}, nullptr, nullptr, nullptr, nullptr, 0,
+        rnn_cand<FMA, 6, S, G, 64, 3>(L.W, RnnIn{L.gvT[fz & 3], nullptr, nullptr}, nullptr, nullptr, nullptr, nullptr, 0,
                                  nullptr, ln, L.dhp[fz & 1]);
       if (FVAD_PRIO & 128) __builtin_amdgcn_s_setprio(0);
     }
@@ -1369,6 +1393,8 @@ __global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) {
   if (tid < S && sb + tid < a.n_streams && L.nfs[tid] > 0)
     reinterpret_cast<int *>(a.state)[(size_t)(sb + tid) * st::kWords + st::kMemId] = L.memid[tid];
 }
+__global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) { rnn3_body<false>(a); }
+__global__ void __launch_bounds__(kR3NT) k_rnn3f(StagedArgs a) { rnn3_body<true>(a); }
 
 // ---------------------------------------------------------------------------
 // k_ola: out = x[0..479] + synthesis_mem; denoised * 1/32767; re-block ring;
@@ -2480,6 +2506,8 @@ hipError_t launch_staged(const StagedArgs &a, int n_cu, hipStream_t stream, hipE
   REC(8);
   if (a.gru16_frags)  // FVAD_MODE_FP16: the GRU stack on the matrix cores (configs[4])
     FVAD_LAUNCH_TRY(launch_gru16(a, stream));
+  else if (a.fma)  // FVAD_MODE_F32_FAST
+    FVAD_KERNEL_TRY(k_rnn3f, dim3((a.n_streams + kR3S - 1) / kR3S), dim3(kR3NT), 0, stream, a);
   else
     FVAD_KERNEL_TRY(k_rnn3, dim3((a.n_streams + kR3S - 1) / kR3S), dim3(kR3NT), 0, stream, a);
   REC(9);

@@ -181,6 +181,9 @@ def staged_kernels(n_channels=2, fft_size=2048):
     # FVAD_MODE_FP16_FUSED: k_pspecw's work and k_gru16's in one kernel; features
     # 34..40 pass in LDS, so the f34 row (8 floats) is neither written nor read
     k["k_fused16"] = (k["k_pspecw"][0] + k["k_rnn3"][0], k["k_pspecw"][1] + k["k_rnn3"][1] - 2 * 8 * 4)
+    # FVAD_MODE_F32_FAST: k_rnn3's algorithmic work on the same bytes (a fused
+    # multiply-add still counts as its two flops)
+    k["k_rnn3f"] = k["k_rnn3"]
     return {n: {"flops": f, "bytes": b} for n, (f, b) in k.items()}
 
 

@@ -112,7 +112,8 @@ typedef struct {
   int band_lo[FVAD_MAX_BANDS]; /* inclusive FFT-B bin ranges (FFT.freqToBin) */
   int band_hi[FVAD_MAX_BANDS];
   int want_denoised;    /* keep denoised PCM (VAD.zig temp_denoiser_segment) */
-  int mode;             /* FVAD_MODE_STAGED (default), FVAD_MODE_FUSED, FVAD_MODE_FP16 or FVAD_MODE_FP16_FUSED */
+  int mode;             /* FVAD_MODE_STAGED (default), FVAD_MODE_FUSED, FVAD_MODE_FP16, FVAD_MODE_FP16_FUSED or
+                         * FVAD_MODE_F32_FAST */
   int use_denoiser;     /* VAD.Config.use_denoiser (default 1).  0: fft_size frames of raw input go
                          * straight to FFT B (VAD.zig:206-212,239-249); per-tick vad / ratio are -1,
                          * the window ratio is preAnalyzeSegment's over the frame, window vad -1 */
@@ -128,11 +129,18 @@ typedef struct {
  * the stated tolerance (vad |d| <= 2e-2), not bit-exact.
  * fp16_fused: configs[4]'s fused FFT -> feature -> GRU kernel -- fp16 with
  * the pitch-spectrum FFT and its features computed inside the GRU kernel
- * (k_fused16 replaces k_pspecw + k_gru16); results identical to fp16's. */
+ * (k_fused16 replaces k_pspecw + k_gru16); results identical to fp16's.
+ * f32_fast: the staged pipeline in f32 with every term of the GRU / dense
+ * sums a fused multiply-add (k_rnn3f replaces k_rnn3); everything before the
+ * GRU stack -- spectra, features, pitch, volume ratios -- stays bit-exact, as
+ * do FFT B and the window bookkeeping.  Within the fp32 tolerance (vad |d| <= 1e-4, denoised rel-RMS
+ * <= 1e-5, band sums rel <= 1e-5, identical segments), not bit-exact.  With
+ * use_denoiser = 0 it is the staged path. */
 #define FVAD_MODE_STAGED 0
 #define FVAD_MODE_FUSED 1
 #define FVAD_MODE_FP16 2
 #define FVAD_MODE_FP16_FUSED 3
+#define FVAD_MODE_F32_FAST 4
 #define FVAD_MAX_TIMES 16
 
 void fvad_engine_config_default(fvad_engine_config *cfg, int n_streams, int n_channels);
