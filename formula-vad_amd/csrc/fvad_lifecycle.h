@@ -1,0 +1,98 @@
+// Per-stream lifecycle (fvad_engine_reset_streams / save_streams /
+// restore_streams): argument blocks and launchers of the clear, gather and
+// scatter kernels (fvad_lifecycle.hip), and the layout of one stream's record
+// in a stream blob (include/fvad.h documents the blob's header).
+//
+// Everything a stream carries between pushes, all indexed by stream:
+//   state  [s][st::kWords]            the rnnoise / re-block record
+//   ring   [s][c][ring_len]           denoised samples awaiting FFT B
+//   per machine m: VadmState [m][s], the long-term row [s][lt_pitch], the
+//   short-term and ratio columns [i][s], the segment row [m][s][seg_cap]
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "fvad_staged.h"
+
+namespace fvad {
+
+// The listed streams reach the device as kernel arguments (no copy, nothing
+// whose lifetime a later call could end): kListMax indices per launch, longer
+// lists take several launches.
+constexpr int kListMax = 256;
+struct IdList {
+  int n;
+  int id[kListMax];
+};
+
+constexpr int kVadmStateWords = (int)(sizeof(VadmState) / 4);
+constexpr int kVadmSegWords = (int)(sizeof(VadmSeg) / 4);
+static_assert(sizeof(VadmState) % 16 == 0, "VadmState rows are copied as float4");
+static_assert(sizeof(VadmSeg) % 4 == 0, "VadmSeg rows are copied as words");
+static_assert(st::kWords % 64 == 0 && st::kPitch == 0 && kPitchBuf % 4 == 0 && st::kSyn % 4 == 0,
+              "the state record's float4 parts");
+
+// One stream's record in a blob, offsets in 32-bit words, every section a
+// multiple of 4 words (16-byte accesses):
+//   [0, kWords)                 the state record
+//   o_ring + c * pend_pad       channel c's pending window part in sample order: the samples
+//                               since the last completed window, pend = samples % fft_size of
+//                               them (from the record's own counter), zeros after
+//   o_mach[m]                   machine m: VadmState | long-term row [lt_pitch] |
+//                               short-term [pad4(n_st)] | ratio [pad4(n_r)] |
+//                               segments [pad4(6 * seg_cap)] (min(n_segs, seg_cap) stored, zeros after)
+struct BlobLayout {
+  int n_channels, n_mach, seg_cap, fft_size, use_denoiser;
+  long long pend_pad, o_ring, o_mach[kMaxBandCfg], words;
+};
+constexpr long long pad4(long long x) { return (x + 3) & ~3LL; }
+inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, const VadmArgs &v, int seg_cap) {
+  BlobLayout L{};
+  L.n_channels = n_channels;
+  L.n_mach = v.n;
+  L.seg_cap = seg_cap;
+  L.fft_size = fft_size;
+  L.use_denoiser = use_denoiser;
+  L.pend_pad = pad4((long long)fft_size - 1);
+  L.o_ring = st::kWords;
+  long long o = L.o_ring + (long long)n_channels * L.pend_pad;
+  for (int m = 0; m < v.n; m++) {
+    L.o_mach[m] = o;
+    o += kVadmStateWords + pad4(v.c[m].lt_pitch) + pad4(v.c[m].n_st) + pad4(v.c[m].n_r) +
+         pad4((long long)kVadmSegWords * seg_cap);
+  }
+  L.words = o;
+  return L;
+}
+
+// k_stream_clear: which words of the state record a launch clears
+enum ClearMode {
+  kClearAll = 0,   // the whole record and the ring rows (fused engines, use_denoiser = 0)
+  kClearMain = 1,  // every word but st::kPitch / st::kHp, and the ring rows (the engine stream's kernels own them)
+  kClearPrep = 2,  // st::kPitch and st::kHp only (k_prep3's, on the prep stream)
+};
+struct ClearArgs {
+  float *state, *ring;
+  int ring_len, n_channels, mode;
+  IdList ids;
+};
+struct VClearArgs {
+  VadmArgs vadm;
+  int n_streams;
+  VadmState init[kMaxBandCfg];  // a machine's state after fvad_engine_reset
+  IdList ids;
+};
+struct XferArgs {
+  float *state, *ring;
+  int ring_len, n_streams;
+  VadmArgs vadm;
+  BlobLayout lay;
+  float *blob;        // device staging: records of lay.words each
+  IdList slots, recs;  // stream slots[i] <-> record recs[i]
+};
+
+hipError_t launch_stream_clear(const ClearArgs &a, hipStream_t stream);
+hipError_t launch_stream_vclear(const VClearArgs &a, hipStream_t stream);
+hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream);
+hipError_t launch_stream_scatter(const XferArgs &a, hipStream_t stream);
+
+}  // namespace fvad

@@ -1,0 +1,190 @@
+// Per-stream lifecycle kernels: clear, gather and scatter over the engine's
+// per-stream layouts (fvad_lifecycle.h).  One workgroup per (listed stream,
+// part), float4 accesses where the layout is 16-byte aligned (the state
+// record, the long-term row, VadmState, the blob's sections); the re-block
+// ring's pending part starts at any even sample and the short-term / ratio
+// buffers are [i][stream] columns, so those go word by word.  No LDS.
+//
+// Every index a kernel uses was checked on the host (fvad_engine.cpp): the
+// listed slots are < n_streams, the record indices < the staging buffer's
+// count, and a restored record's counters and write indices are in range.
+#include <hip/hip_runtime.h>
+
+#include "fvad_lifecycle.h"
+
+namespace fvad {
+
+namespace {
+constexpr int kNT = 256;
+
+// samples the stream of a state record has consumed: frames_done frames with
+// the denoiser, st::kNdSamples (u64) without
+__device__ __forceinline__ unsigned long long record_samples(const float *rec, int use_denoiser) {
+  if (use_denoiser) return (unsigned long long)reinterpret_cast<const int *>(rec)[st::kFramesDone] * kFrame;
+  return *reinterpret_cast<const unsigned long long *>(rec + st::kNdSamples);
+}
+
+__device__ __forceinline__ void copy4(float *dst, const float *src, long long words, int tid) {
+  for (long long q = tid; q < words / 4; q += kNT)
+    reinterpret_cast<float4 *>(dst)[q] = reinterpret_cast<const float4 *>(src)[q];
+}
+__device__ __forceinline__ void zero4(float *dst, long long words, int tid) {
+  for (long long q = tid; q < words / 4; q += kNT) reinterpret_cast<float4 *>(dst)[q] = make_float4(0, 0, 0, 0);
+}
+}  // namespace
+
+// part 0: the state record's words of a.mode; part 1 + c: channel c's ring row
+__global__ void __launch_bounds__(kNT) k_stream_clear(ClearArgs a) {
+  const int s = a.ids.id[blockIdx.x], part = blockIdx.y, tid = threadIdx.x;
+  if (part > 0) {
+    zero4(a.ring + ((size_t)s * a.n_channels + (part - 1)) * a.ring_len, a.ring_len, tid);
+    return;
+  }
+  float *stp = a.state + (size_t)s * st::kWords;
+  if (a.mode == kClearAll) {
+    zero4(stp, st::kWords, tid);
+  } else if (a.mode == kClearPrep) {
+    zero4(stp + st::kPitch, kPitchBuf, tid);
+    if (tid < 2) stp[st::kHp + tid] = 0.0f;
+  } else {
+    // [kSyn, kWords) but the two high-pass words
+    for (int q = st::kSyn / 4 + tid; q < st::kWords / 4; q += kNT) {
+      if (q != st::kHp / 4) {
+        reinterpret_cast<float4 *>(stp)[q] = make_float4(0, 0, 0, 0);
+      } else {
+        for (int w = 4 * q; w < 4 * q + 4; w++)
+          if (w != st::kHp && w != st::kHp + 1) stp[w] = 0.0f;
+      }
+    }
+  }
+}
+
+// machine blockIdx.y of a listed stream: its initial state, empty rolling
+// buffers (entries 0.0f, as vadm_reset's memset), no segments (n_segs = 0)
+__global__ void __launch_bounds__(kNT) k_stream_vclear(VClearArgs a) {
+  const int s = a.ids.id[blockIdx.x], m = blockIdx.y, tid = threadIdx.x;
+  const VadmConst &K = a.vadm.c[m];
+  const size_t B = a.n_streams;
+  if (tid == 0) a.vadm.st[(size_t)m * B + s] = a.init[m];
+  zero4(a.vadm.buf + K.lt_off + (size_t)s * K.lt_pitch, K.lt_pitch, tid);
+  for (int i = tid; i < K.n_st; i += kNT) a.vadm.buf[K.st_off + (size_t)i * B + s] = 0.0f;
+  for (int i = tid; i < K.n_r; i += kNT) a.vadm.buf[K.r_off + (size_t)i * B + s] = 0.0f;
+}
+
+// stream slots[i] -> record recs[i].  part 0: state; 1 + c: channel c's
+// pending window part; 1 + C + m: machine m
+__global__ void __launch_bounds__(kNT) k_stream_gather(XferArgs a) {
+  const int s = a.slots.id[blockIdx.x], part = blockIdx.y, tid = threadIdx.x;
+  const BlobLayout &L = a.lay;
+  const int C = L.n_channels;
+  float *rec = a.blob + (size_t)a.recs.id[blockIdx.x] * L.words;
+  const float *stp = a.state + (size_t)s * st::kWords;
+  if (part == 0) {
+    copy4(rec, stp, st::kWords, tid);
+  } else if (part <= C) {
+    const int c = part - 1;
+    const unsigned long long total = record_samples(stp, L.use_denoiser);
+    const long long pend = (long long)(total % (unsigned)L.fft_size);
+    const unsigned long long w0 = total - (unsigned long long)pend;
+    const float *ring = a.ring + ((size_t)s * C + c) * a.ring_len;
+    float *dst = rec + L.o_ring + (size_t)c * L.pend_pad;
+    for (long long j = tid; j < L.pend_pad; j += kNT)
+      dst[j] = j < pend ? ring[(w0 + (unsigned long long)j) % (unsigned)a.ring_len] : 0.0f;
+  } else {
+    const int m = part - 1 - C;
+    const VadmConst &K = a.vadm.c[m];
+    const size_t B = a.n_streams, idx = (size_t)m * B + s;
+    float *dst = rec + L.o_mach[m];
+    copy4(dst, reinterpret_cast<const float *>(a.vadm.st + idx), kVadmStateWords, tid);
+    dst += kVadmStateWords;
+    copy4(dst, a.vadm.buf + K.lt_off + (size_t)s * K.lt_pitch, K.lt_pitch, tid);
+    dst += pad4(K.lt_pitch);
+    for (int i = tid; i < (int)pad4(K.n_st); i += kNT) dst[i] = i < K.n_st ? a.vadm.buf[K.st_off + (size_t)i * B + s] : 0.0f;
+    dst += pad4(K.n_st);
+    for (int i = tid; i < (int)pad4(K.n_r); i += kNT) dst[i] = i < K.n_r ? a.vadm.buf[K.r_off + (size_t)i * B + s] : 0.0f;
+    dst += pad4(K.n_r);
+    // the stored segments (the list keeps the first seg_cap), zeros after
+    const unsigned stored = min(a.vadm.st[idx].n_segs, (unsigned)a.vadm.seg_cap);
+    const unsigned *seg = reinterpret_cast<const unsigned *>(a.vadm.seg + idx * a.vadm.seg_cap);
+    unsigned *sd = reinterpret_cast<unsigned *>(dst);
+    const long long nw = (long long)kVadmSegWords * stored;
+    for (long long w = tid; w < pad4((long long)kVadmSegWords * L.seg_cap); w += kNT) sd[w] = w < nw ? seg[w] : 0u;
+  }
+}
+
+// record recs[i] -> stream slots[i]: the reverse.  The pending window part
+// goes to this engine's ring positions (absolute sample mod ring_len); a
+// smaller segment capacity keeps the first seg_cap segments and the true total.
+__global__ void __launch_bounds__(kNT) k_stream_scatter(XferArgs a) {
+  const int s = a.slots.id[blockIdx.x], part = blockIdx.y, tid = threadIdx.x;
+  const BlobLayout &L = a.lay;
+  const int C = L.n_channels;
+  const float *rec = a.blob + (size_t)a.recs.id[blockIdx.x] * L.words;
+  if (part == 0) {
+    copy4(a.state + (size_t)s * st::kWords, rec, st::kWords, tid);
+  } else if (part <= C) {
+    const int c = part - 1;
+    const unsigned long long total = record_samples(rec, L.use_denoiser);
+    const long long pend = (long long)(total % (unsigned)L.fft_size);
+    const unsigned long long w0 = total - (unsigned long long)pend;
+    float *ring = a.ring + ((size_t)s * C + c) * a.ring_len;
+    const float *src = rec + L.o_ring + (size_t)c * L.pend_pad;
+    for (long long j = tid; j < pend; j += kNT) ring[(w0 + (unsigned long long)j) % (unsigned)a.ring_len] = src[j];
+  } else {
+    const int m = part - 1 - C;
+    const VadmConst &K = a.vadm.c[m];
+    const size_t B = a.n_streams, idx = (size_t)m * B + s;
+    const float *src = rec + L.o_mach[m];
+    const unsigned n_segs = reinterpret_cast<const VadmState *>(src)->n_segs;
+    copy4(reinterpret_cast<float *>(a.vadm.st + idx), src, kVadmStateWords, tid);
+    src += kVadmStateWords;
+    copy4(a.vadm.buf + K.lt_off + (size_t)s * K.lt_pitch, src, K.lt_pitch, tid);
+    src += pad4(K.lt_pitch);
+    for (int i = tid; i < K.n_st; i += kNT) a.vadm.buf[K.st_off + (size_t)i * B + s] = src[i];
+    src += pad4(K.n_st);
+    for (int i = tid; i < K.n_r; i += kNT) a.vadm.buf[K.r_off + (size_t)i * B + s] = src[i];
+    src += pad4(K.n_r);
+    const unsigned keep = min(min(n_segs, (unsigned)L.seg_cap), (unsigned)a.vadm.seg_cap);
+    unsigned *seg = reinterpret_cast<unsigned *>(a.vadm.seg + idx * a.vadm.seg_cap);
+    const unsigned *ss = reinterpret_cast<const unsigned *>(src);
+    const long long nw = (long long)kVadmSegWords * keep;
+    for (long long w = tid; w < (long long)kVadmSegWords * a.vadm.seg_cap; w += kNT) seg[w] = w < nw ? ss[w] : 0u;
+  }
+}
+
+namespace {
+hipError_t launched() { return hipGetLastError(); }
+}  // namespace
+
+hipError_t launch_stream_clear(const ClearArgs &a, hipStream_t stream) {
+  if (a.ids.n < 1) return hipSuccess;
+  (void)hipGetLastError();
+  const unsigned parts = a.mode == kClearPrep ? 1u : 1u + (unsigned)a.n_channels;
+  hipLaunchKernelGGL(k_stream_clear, dim3((unsigned)a.ids.n, parts), dim3(kNT), 0, stream, a);
+  return launched();
+}
+
+hipError_t launch_stream_vclear(const VClearArgs &a, hipStream_t stream) {
+  if (a.ids.n < 1 || a.vadm.n < 1) return hipSuccess;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_stream_vclear, dim3((unsigned)a.ids.n, (unsigned)a.vadm.n), dim3(kNT), 0, stream, a);
+  return launched();
+}
+
+hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream) {
+  if (a.slots.n < 1) return hipSuccess;
+  (void)hipGetLastError();
+  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach;
+  hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)a.slots.n, parts), dim3(kNT), 0, stream, a);
+  return launched();
+}
+
+hipError_t launch_stream_scatter(const XferArgs &a, hipStream_t stream) {
+  if (a.slots.n < 1) return hipSuccess;
+  (void)hipGetLastError();
+  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach;
+  hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)a.slots.n, parts), dim3(kNT), 0, stream, a);
+  return launched();
+}
+
+}  // namespace fvad

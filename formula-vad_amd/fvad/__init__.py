@@ -28,7 +28,8 @@ FRAME = 480
 
 
 class FvadError(RuntimeError):
-    pass
+    """code: the FVAD_E* status of the failed call (None when there is none)."""
+    code = None
 
 
 class EngineConfig(C.Structure):
@@ -96,8 +97,22 @@ class VadmSnapshot(C.Structure):
 
 
 DEBUG_VADM_PAR_SERIAL_EVERY, DEBUG_VADM_ALWAYS_PAR, DEBUG_VADM_LT_FULL, DEBUG_VADM_DEFER_MAX = 1, 2, 3, 4
-DEBUG_VADM_BOUND_SCALE, DEBUG_VADM_COUNT, DEBUG_VADM_NEGATE_AT = 5, 6, 7
+DEBUG_VADM_BOUND_SCALE, DEBUG_VADM_COUNT, DEBUG_VADM_NEGATE_AT, DEBUG_RESET_TIMES = 5, 6, 7, 8
 SHARE_PREP, SHARE_SIDE = 1, 2  # fvad_engine_share_streams
+
+# stream blobs (fvad_engine_save_streams): include/fvad.h documents the layout
+STREAM_BLOB_MAGIC, STREAM_BLOB_VERSION, STREAM_BLOB_HEADER_BYTES = 0x42535646, 1, 128
+
+
+class StreamBlobHeader(C.Structure):
+    """fvad_stream_blob_header (include/fvad.h)."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("count", C.c_uint32),
+                ("stream_bytes", C.c_uint64), ("mode", C.c_uint32), ("n_channels", C.c_uint32),
+                ("fft_size", C.c_uint32), ("use_denoiser", C.c_uint32), ("n_bands", C.c_uint32),
+                ("n_machines", C.c_uint32), ("seg_capacity", C.c_uint32), ("state_words", C.c_uint32),
+                ("config_hash", C.c_uint64), ("model_hash", C.c_uint64), ("sample_rate", C.c_uint32),
+                ("reserved", C.c_uint32 * 13)]
+
 
 READ_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_int, C.POINTER(F32P), C.c_size_t)
 
@@ -156,6 +171,12 @@ SYMBOLS = [
     ("fvad_engine_create", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fvad_engine_destroy", None, [C.c_void_p]),
     ("fvad_engine_reset", C.c_int, [C.c_void_p]),
+    ("fvad_engine_reset_streams", C.c_int, [C.c_void_p, I32P, C.c_int]),
+    ("fvad_engine_save_size", C.c_size_t, [C.c_void_p, C.c_int]),
+    ("fvad_engine_save_streams", C.c_int, [C.c_void_p, I32P, C.c_int, C.c_void_p, C.c_size_t]),
+    ("fvad_engine_restore_streams", C.c_int, [C.c_void_p, I32P, C.c_int, C.c_void_p, C.c_size_t, I32P]),
+    ("fvad_stream_blob_info", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("fvad_engine_reset_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("fvad_engine_push", C.c_int, [C.c_void_p, F32P, C.c_int, I32P, C.c_void_p]),
     ("fvad_engine_push_ex", C.c_int, [C.c_void_p, F32P, C.c_int, I32P, I32P, C.c_void_p]),
     ("fvad_engine_submit_ex", C.c_int, [C.c_void_p, F32P, C.c_int, I32P, I32P]),
@@ -243,7 +264,27 @@ def last_error():
 
 def _check(rc, what):
     if rc != FVAD_OK:
-        raise FvadError("%s failed (%d): %s" % (what, rc, last_error()))
+        err = FvadError("%s failed (%d): %s" % (what, rc, last_error()))
+        err.code = rc
+        raise err
+
+
+EINVAL, EFORMAT = -1, -5
+
+
+def _ids(ids):
+    a = np.ascontiguousarray(list(ids) if not isinstance(ids, np.ndarray) else ids, np.int64)
+    if a.ndim != 1 or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+        raise ValueError("stream indices: a flat list of 32-bit integers")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def stream_blob_info(blob):
+    """fvad_stream_blob_info: the validated header of a stream blob as a dict (host only)."""
+    b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if not isinstance(blob, np.ndarray) else blob, np.uint8)
+    h = StreamBlobHeader()
+    _check(lib().fvad_stream_blob_info(b.ctypes.data_as(C.c_void_p), b.size, C.byref(h)), "fvad_stream_blob_info")
+    return {n: getattr(h, n) for n, _ in h._fields_ if n != "reserved"}
 
 
 def fptr(a):
@@ -412,6 +453,38 @@ class Engine:
     def reset(self):
         _check(lib().fvad_engine_reset(self.h), "fvad_engine_reset")
 
+    def reset_streams(self, ids):
+        """The listed streams as fvad_engine_reset leaves them, between the pushes
+        submitted before and after the call; never waits for the device."""
+        a = _ids(ids)
+        _check(lib().fvad_engine_reset_streams(self.h, a.ctypes.data_as(I32P), a.size), "fvad_engine_reset_streams")
+
+    def save_streams(self, ids):
+        """The listed streams' whole state as a blob (np.uint8; a sync point)."""
+        a = _ids(ids)
+        blob = np.zeros(lib().fvad_engine_save_size(self.h, a.size), np.uint8)
+        _check(lib().fvad_engine_save_streams(self.h, a.ctypes.data_as(I32P), a.size,
+                                              blob.ctypes.data_as(C.c_void_p), blob.size), "fvad_engine_save_streams")
+        return blob
+
+    def restore_streams(self, ids, blob, index=None):
+        """Record index[i] of the blob (default i) into slot ids[i] (a sync point)."""
+        a = _ids(ids)
+        b = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if not isinstance(blob, np.ndarray) else blob, np.uint8)
+        ix = _ids(index) if index is not None else None
+        if ix is not None and ix.size != a.size:
+            raise ValueError("index: one record per listed stream")
+        _check(lib().fvad_engine_restore_streams(self.h, a.ctypes.data_as(I32P), a.size, b.ctypes.data_as(C.c_void_p),
+                                                 b.size, ix.ctypes.data_as(I32P) if ix is not None else None),
+               "fvad_engine_restore_streams")
+
+    def reset_times(self):
+        """DEBUG_RESET_TIMES' samples: ({stream: ms average}, {stream: runs})."""
+        ms, n = (C.c_double * 3)(), (C.c_int * 3)()
+        _check(lib().fvad_engine_reset_times(self.h, ms, n), "fvad_engine_reset_times")
+        names = ("main", "prep", "side")
+        return dict(zip(names, ms)), dict(zip(names, n))
+
     def load_synthetic(self, n_ticks, base=0, pushes=1):
         """pushes distinct resident pushes of n_ticks (run_resident cycles through them)."""
         _check(lib().fvad_engine_load_synthetic_ex(self.h, n_ticks, pushes, base), "fvad_engine_load_synthetic_ex")
@@ -576,6 +649,18 @@ class EngineGroup:
     def segments(self, stream, machine=0):
         g = max(i for i, f in enumerate(self.first) if f <= stream)
         return self.engines[g].segments(stream - self.first[g], machine)
+
+    def reset_streams(self, global_ids):
+        """Engine.reset_streams over the group's stream numbering."""
+        ids = _ids(global_ids)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.B):
+            raise ValueError("stream index out of range")
+        if len(set(ids.tolist())) != ids.size:
+            raise ValueError("duplicate stream index")
+        for e, f, n in zip(self.engines, self.first, self.sizes):
+            mine = ids[(ids >= f) & (ids < f + n)] - f
+            if mine.size:
+                e.reset_streams(mine)
 
 class Denoiser:
     """src/Denoiser.zig over the rnnoise_* C ABI (GPU, batch of one)."""

@@ -150,6 +150,94 @@ void fvad_engine_destroy(fvad_engine *e);
 /* reset every stream to a freshly created rnnoise / VAD state */
 int fvad_engine_reset(fvad_engine *e);
 
+/* Stream lifecycle: reset, save and restore single streams of a live engine
+ * (a serving host's streams start, stop and move at different times).
+ * `streams` lists n distinct indices in [0, n_streams); n == 0 is a no-op
+ * (FVAD_OK).  A duplicate or out-of-range index is FVAD_EINVAL and nothing is
+ * touched.
+ *
+ * fvad_engine_reset_streams: the listed streams become exactly what
+ * fvad_engine_reset makes them -- rnnoise state, high-pass memory, pitch
+ * history, the tick / sample counters (sample indices restart at 0), the
+ * window volume accumulator, the re-block ring rows and, per attached machine,
+ * its initial state, empty rolling averages and an empty segment list; every
+ * other stream is untouched.  Every engine mode.  It takes effect between the
+ * pushes submitted before the call and those submitted after it: earlier
+ * pushes still in flight (submit without collect, run_resident without sync)
+ * keep their outputs, their device VADMachine pass included.  It never waits
+ * for the device: a few small kernels go onto the engine's own streams, each
+ * behind the work that owns what it clears, so a host may call it between
+ * every pair of pushes.  The position in a resident input cycle
+ * (fvad_engine_load_synthetic_ex) belongs to the engine, not to a stream, and
+ * stays.  While the test hook FVAD_DEBUG_VADM_LT_FULL is set on an engine
+ * with machines it returns FVAD_EINVAL (that hook's initial state is a
+ * whole-engine timing fixture).
+ *
+ * fvad_engine_save_streams / fvad_engine_restore_streams move streams between
+ * engines as a blob: a checkpoint, or a migration to another slot, engine or
+ * GPU.  Both are sync points like fvad_engine_segments (they wait for every
+ * queued push and run the pending machine pass as final) and may block.  A
+ * blob restores into an engine that may differ in n_streams, max_ticks,
+ * device, seg_capacity and slot, and must agree in mode, n_channels, fft_size,
+ * use_denoiser, sample_rate, the band table, the machine configs (count and
+ * every field) and the model.  Record index[i] of the blob (i when index is
+ * NULL) goes to slot streams[i]; the stream then continues as if it had never
+ * moved.  A target with a smaller seg_capacity keeps the first seg_capacity
+ * segments and the true total, as the list does on overflow.
+ *
+ * A restore validates everything on the host before it writes a device byte:
+ * the header against len, every compatibility field and both hashes, the
+ * counters and write indices of the records it will use (FVAD_EFORMAT), and
+ * the stream list and index (FVAD_EINVAL).  After an error the engine is
+ * exactly as it was.  save returns FVAD_EINVAL when cap <
+ * fvad_engine_save_size(e, n).
+ *
+ * Blob layout (little endian): a fvad_stream_blob_header of header_bytes
+ * (128), then count records of stream_bytes each.  A record, in 32-bit words,
+ * every section padded to 4 words:
+ *   the stream's state record (state_words words);
+ *   per channel, P = (fft_size + 2) & ~3 words: the pending part of the
+ *     current FFT window in sample order -- samples % fft_size of them (the
+ *     state record holds the counter), zeros after.  Not the ring itself: the
+ *     ring is indexed by absolute sample mod its length, which depends on
+ *     max_ticks;
+ *   per machine: its state (40 words), the long-term average's entries
+ *     (padded to 4), the short-term's, the volume ratio's, and seg_capacity
+ *     segments of 6 words (min(total, seg_capacity) stored, zeros after). */
+#define FVAD_STREAM_BLOB_MAGIC 0x42535646u /* "FVSB" */
+#define FVAD_STREAM_BLOB_VERSION 1
+#define FVAD_STREAM_BLOB_HEADER_BYTES 128
+typedef struct {
+  uint32_t magic;         /*   0 FVAD_STREAM_BLOB_MAGIC */
+  uint32_t version;       /*   4 FVAD_STREAM_BLOB_VERSION */
+  uint32_t header_bytes;  /*   8 FVAD_STREAM_BLOB_HEADER_BYTES */
+  uint32_t count;         /*  12 stream records that follow */
+  uint64_t stream_bytes;  /*  16 bytes per record */
+  uint32_t mode;          /*  24 the saving engine's config ... */
+  uint32_t n_channels;    /*  28 */
+  uint32_t fft_size;      /*  32 */
+  uint32_t use_denoiser;  /*  36 */
+  uint32_t n_bands;       /*  40 */
+  uint32_t n_machines;    /*  44 attached device VADMachines */
+  uint32_t seg_capacity;  /*  48 of the saving engine (0 without machines) */
+  uint32_t state_words;   /*  52 32-bit words of a stream's state record */
+  uint64_t config_hash;   /*  56 FNV-1a 64 of mode, n_channels, fft_size, use_denoiser, sample_rate,
+                           *     n_bands, the band ranges, n_machines and every machine config field */
+  uint64_t model_hash;    /*  64 FNV-1a 64 of fvad_model_blob's bytes */
+  uint32_t sample_rate;   /*  72 */
+  uint32_t reserved[13];  /*  76 zero */
+} fvad_stream_blob_header;
+int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams, int n);
+/* bytes a save of n streams needs (0 for a NULL engine or n < 0) */
+size_t fvad_engine_save_size(const fvad_engine *e, int n);
+int fvad_engine_save_streams(fvad_engine *e, const int32_t *streams, int n, void *blob, size_t cap);
+int fvad_engine_restore_streams(fvad_engine *e, const int32_t *streams, int n, const void *blob, size_t len,
+                                const int32_t *index);
+/* Parses and validates a blob's header on the host alone (no GPU): magic,
+ * version, header_bytes, and header_bytes + count * stream_bytes <= len;
+ * FVAD_EFORMAT otherwise.  *out receives the header. */
+int fvad_stream_blob_info(const void *blob, size_t len, fvad_stream_blob_header *out);
+
 /* Per-tick outputs, host arrays owned by the caller, indexed [tick][stream]...
  * Any pointer may be NULL to skip that output.  The window outputs have W =
  * fvad_engine_windows_per_tick(e) slots per (tick, stream): W = 1 for fft_size
@@ -371,7 +459,15 @@ int fvad_engine_share_streams(fvad_engine *e, fvad_engine *other, int which);
 #define FVAD_DEBUG_VADM_BOUND_SCALE 5
 #define FVAD_DEBUG_VADM_COUNT 6
 #define FVAD_DEBUG_VADM_NEGATE_AT 7
+/*   FVAD_DEBUG_RESET_TIMES  value 1: fvad_engine_reset_streams brackets each of
+ *     its launches with a timing event pair (fvad_engine_reset_times) */
+#define FVAD_DEBUG_RESET_TIMES 8
 int fvad_engine_set_debug(fvad_engine *e, int key, int value);
+/* FVAD_DEBUG_RESET_TIMES' samples: average event time (ms) of a
+ * fvad_engine_reset_streams call's launches on [0] the engine stream, [1] the
+ * prep stream, [2] the side stream, and how many each averages (the last 64
+ * calls at most); synchronises the engine and clears the samples */
+int fvad_engine_reset_times(fvad_engine *e, double *ms_avg, int *n_runs);
 /* FVAD_DEBUG_VADM_COUNT's counters, out[0..min(n, 4)): long-term tests decided
  * from an exact average, tests the bound settled from the estimate, tests it
  * left open (an exact fold), folds at the end of a push.  Returns the count
