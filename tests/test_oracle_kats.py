@@ -4,6 +4,8 @@ reference's own tests hold, plus KATs derived from the reference semantics
 import numpy as np
 import pytest
 
+from parity_util import LAYERS, write_text_model  # noqa: F401  (the text model writer lives with the test models)
+
 
 # ---------------- reference unit tests, ported as expected values ----------------
 
@@ -170,23 +172,6 @@ def test_model_text_roundtrip(oracle_mod, tmp_path):
     write_text_model(m.blob(), path)
     m2 = O.Model(path=str(path))
     assert np.array_equal(m.blob(), m2.blob())
-
-
-LAYERS = [(42, 24, 0, False), (24, 24, 2, True), (90, 48, 2, True), (114, 96, 2, True), (96, 22, 1, False),
-          (24, 1, 1, False)]
-
-
-def write_text_model(blob, path):
-    lines = ["rnnoise-nu model file version 1"]
-    o = 0
-    for nin, nout, act, gru in LAYERS:
-        g = 3 if gru else 1
-        sizes = [nin * nout * g] + ([nout * nout * 3] if gru else []) + [nout * g]
-        lines.append("%d %d %d" % (nin, nout, act))
-        for n in sizes:
-            lines.append(" ".join(str(int(v)) for v in blob[o:o + n]))
-            o += n
-    path.write_text("\n".join(lines) + "\n")
 
 
 def test_audacity_parse(oracle_mod):
