@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <memory>
 #include <string>
 #include <thread>
@@ -139,6 +140,37 @@ struct fvad_engine {
   int vadm_slot = 0;
   bool dbg_always_par = false;  // test hook FVAD_DEBUG_VADM_ALWAYS_PAR
   bool dbg_lt_full = false;     // test hook FVAD_DEBUG_VADM_LT_FULL
+  // Speech event feed (fvad_engine_enable_events).  The
+  // machine kernels stage events per lane in HBM (vadm.ev_stage), k_vadm_events
+  // packs them behind each pass into a ring in pinned host memory and writes
+  // the pass's header slot there; ev_flight holds, oldest first, the passes
+  // whose `done` event (recorded behind k_vadm_events) has not been seen
+  // complete yet.  poll_events reads the ring only up to the end cursor of the
+  // last retired pass: the host never looks at ring or header bytes of a pass
+  // before its event has completed (an event's completion releases the
+  // kernel's stores to the system, whichever coherence the allocation has).
+  struct EvPass {
+    uint64_t pass, push;
+    hipEvent_t done;
+  };
+  static constexpr int kEvHeaders = 64;  // header slots: passes in flight at most (an older one is waited for)
+  bool events_on = false;
+  unsigned long long *d_ev_cursor = nullptr;   // device: [0] write cursor, [1] lost
+  fvad_event *h_ev_ring = nullptr;             // pinned, written by the device through dv_ev_ring
+  fvad::VadmEvent *dv_ev_ring = nullptr;
+  fvad::VadmEventHeader *h_ev_hdr = nullptr, *dv_ev_hdr = nullptr;  // [kEvHeaders], slot pass % kEvHeaders
+  size_t ev_ring_cap = 0;
+  uint64_t ev_read = 0, ev_end = 0, ev_lost = 0;  // host read cursor; ring valid up to ev_end; lost so far
+  uint64_t ev_pass_next = 0;
+  uint64_t ev_pushes_done = 0;  // pushes up to here have every event in the ring's valid part
+  std::deque<EvPass> ev_flight;
+  std::vector<hipEvent_t> ev_pool;  // retired passes' events, re-used
+  uint64_t push_count = 0, vpend_push = 0;  // pushes launched since create / reset; the pending pass's
+  int dbg_events_chunk = 0;  // test hook FVAD_DEBUG_EVENTS_CHUNK
+  hipEvent_t ev_et[2][2] = {};  // k_vadm_events timing pairs, by vadm_slot
+  bool et_pending[2] = {false, false};
+  double et_ms_sum = 0;
+  int et_timed = 0;
   // test hook (fvad_engine_output_log): the per-tick outputs of the next
   // log_cap pushes, copied on the engine stream as each push ends
   float *d_log = nullptr;
@@ -397,6 +429,16 @@ void free_all(fvad_engine *e) {
     if (ev) (void)hipEventDestroy(ev);
   if (e->d_pcm16) (void)hipFree(e->d_pcm16);
   if (e->d_blob) (void)hipFree(e->d_blob);
+  void *evd[] = {e->vadm.ev_stage, e->vadm.ev_count, e->d_ev_cursor};
+  for (void *p : evd)
+    if (p) (void)hipFree(p);
+  if (e->h_ev_ring) (void)hipHostFree(e->h_ev_ring);
+  if (e->h_ev_hdr) (void)hipHostFree(e->h_ev_hdr);
+  for (auto &p : e->ev_flight) (void)hipEventDestroy(p.done);
+  for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
+  for (auto &pair : e->ev_et)
+    for (hipEvent_t ev : pair)
+      if (ev) (void)hipEventDestroy(ev);
   for (auto &slot : e->rt_ev)
     for (auto &pair : slot)
       for (hipEvent_t ev : pair)
@@ -428,6 +470,7 @@ void free_all(fvad_engine *e) {
 
 int vadm_reset(fvad_engine *e);
 int vadm_flush(fvad_engine *e, bool fast);
+int events_reset(fvad_engine *e);
 
 extern "C" int fvad_engine_reset(fvad_engine *e) {
   if (!e) return fail(FVAD_EINVAL, "null engine");
@@ -439,9 +482,11 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
     e->vowed = false;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipStreamSynchronize(e->side));
-    const int rc = vadm_reset(e);
+    int rc = vadm_reset(e);
+    if (!rc && e->events_on) rc = events_reset(e);
     if (rc) return rc;
   }
+  e->push_count = 0;
   HIP_TRY(hipMemsetAsync(e->d_state, 0, sizeof(float) * fvad::st::kWords * (size_t)e->cfg.n_streams, e->stream));
   e->res_next = 0;  // fresh streams start at the resident cycle's first push (t = 0)
   if (e->d_work) HIP_TRY(hipMemsetAsync(e->d_work, 0, sizeof(unsigned) * fvad::kWorkCounters, e->stream));
@@ -725,6 +770,88 @@ int launch_fused(fvad_engine *e, int n_ticks, bool use_ticks, bool timed) {
 // DESIGN §8 r4)
 hipError_t wait_event(hipStream_t stream, hipEvent_t ev) { return hipStreamWaitEvent(stream, ev, 0); }
 
+// Event feed: the passes whose `done` event has completed leave ev_flight, the
+// newest one's header giving the ring's valid end and the lost count.  Never
+// blocks unless wait_oldest (the header slots are all taken).
+int events_retire(fvad_engine *e, bool wait_oldest) {
+  while (!e->ev_flight.empty()) {
+    const fvad_engine::EvPass p = e->ev_flight.front();
+    const hipError_t q = hipEventQuery(p.done);
+    if (q == hipErrorNotReady) {
+      (void)hipGetLastError();
+      if (!wait_oldest) break;
+      HIP_TRY(hipEventSynchronize(p.done));
+    } else if (q != hipSuccess) {
+      return fail(FVAD_EDEVICE, std::string("hipEventQuery (event feed): ") + hipGetErrorString(q));
+    }
+    wait_oldest = false;
+    const volatile fvad::VadmEventHeader *h = e->h_ev_hdr + p.pass % fvad_engine::kEvHeaders;
+    if (h->pass != p.pass) return fail(FVAD_EDEVICE, "event feed: a finished pass left no header");
+    e->ev_end = h->end;
+    e->ev_lost = h->lost;
+    e->ev_pushes_done = p.push + 1;
+    e->ev_pool.push_back(p.done);
+    e->ev_flight.pop_front();
+  }
+  return FVAD_OK;
+}
+
+// k_vadm_events behind the machine pass just queued on the side stream
+int enqueue_events(fvad_engine *e, const fvad::VadmArgs &v, uint64_t push, int slot, bool timed) {
+  int rc = events_retire(e, false);
+  if (!rc && e->ev_flight.size() >= (size_t)fvad_engine::kEvHeaders) rc = events_retire(e, true);
+  if (rc) return rc;
+  hipEvent_t done = nullptr;
+  if (!e->ev_pool.empty()) {
+    done = e->ev_pool.back();
+    e->ev_pool.pop_back();
+  } else {
+    HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+  }
+  e->ev_pool.push_back(done);  // (back in the pool if a call below fails)
+  fvad::VadmEventArgs a{};
+  a.stage = v.ev_stage;
+  a.count = v.ev_count;
+  a.ev_cap = v.ev_cap;
+  a.n_lanes = e->cfg.n_streams * v.n;
+  a.n_machines = v.n;
+  a.chunk = e->dbg_events_chunk;
+  a.ring = e->dv_ev_ring;
+  a.ring_cap = e->ev_ring_cap;
+  a.cursor = e->d_ev_cursor;
+  a.pass = e->ev_pass_next;
+  a.header = e->dv_ev_hdr + a.pass % fvad_engine::kEvHeaders;
+  a.push = push;
+  a.host_read = e->ev_read;
+  if (timed) {
+    e->et_pending[slot] = false;
+    HIP_TRY(hipEventRecord(e->ev_et[slot][0], e->side));
+  }
+  HIP_TRY(fvad::launch_vadm_events(a, e->side));
+  if (timed) {
+    HIP_TRY(hipEventRecord(e->ev_et[slot][1], e->side));
+    e->et_pending[slot] = true;
+  }
+  HIP_TRY(hipEventRecord(done, e->side));
+  e->ev_pool.pop_back();
+  e->ev_flight.push_back({a.pass, push, done});
+  e->ev_pass_next++;
+  return FVAD_OK;
+}
+
+// the feed as after enable: nothing queued, cursors, pass and lost counts zero
+// (the side stream is idle)
+int events_reset(fvad_engine *e) {
+  for (auto &p : e->ev_flight) e->ev_pool.push_back(p.done);
+  e->ev_flight.clear();
+  HIP_TRY(hipMemset(e->d_ev_cursor, 0, 2 * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(e->vadm.ev_count, 0, sizeof(unsigned) * (size_t)e->cfg.n_streams * e->vadm.n));
+  std::memset(e->h_ev_hdr, 0xff, sizeof(fvad::VadmEventHeader) * fvad_engine::kEvHeaders);
+  e->ev_read = e->ev_end = e->ev_lost = e->ev_pass_next = e->ev_pushes_done = 0;
+  for (bool &p : e->et_pending) p = false;
+  return FVAD_OK;
+}
+
 // k_vadm of one push on the side stream (its waits already queued), with
 // its timing pair and the events later pushes wait for
 int enqueue_vadm(fvad_engine *e, const fvad::StagedArgs &v, int b, bool timed, bool fast) {
@@ -750,6 +877,14 @@ int enqueue_vadm(fvad_engine *e, const fvad::StagedArgs &v, int b, bool timed, b
     HIP_TRY(hipEventRecord(e->ev_vt[slot][1], e->side));
     e->vadm_pending[slot] = true;
     e->vadm_kind[slot] = par ? 1 : 0;
+  }
+  if (vf.vadm.ev_stage) {
+    // the window outputs are free once the machines have read them: the
+    // next push but one does not wait for the event pass
+    HIP_TRY(hipEventRecord(e->ev_vadm_b[b], e->side));
+    if (const int rc = enqueue_events(e, vf.vadm, e->vpend_push, slot, timed)) return rc;
+    HIP_TRY(hipEventRecord(e->ev_vadm, e->side));
+    return FVAD_OK;
   }
   HIP_TRY(hipEventRecord(e->ev_vadm, e->side));
   HIP_TRY(hipEventRecord(e->ev_vadm_b[b], e->side));
@@ -912,7 +1047,9 @@ int launch_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bo
     e->vpend_args = v;
     e->vpend_b = b;
     e->vpend_timed = timed;
+    e->vpend_push = e->push_count;
   }
+  e->push_count++;
   if (e->log_n < e->log_cap) {  // test hook: this push's outputs into the log (read after a sync)
     const size_t B = c.n_streams, TB = (size_t)n_ticks * B, TBW = TB * e->wpt, MT = (size_t)c.max_ticks * B,
                  MW = MT * e->wpt;
@@ -973,6 +1110,14 @@ int collect_vadm_timing(fvad_engine *e) {
     e->vadm_ms_sum[e->vadm_kind[k]] += ms;
     e->vadm_timed[e->vadm_kind[k]]++;
     e->vadm_pending[k] = false;
+  }
+  for (int k = 0; k < 2; k++) {  // k_vadm_events' samples
+    if (!e->et_pending[k] || hipEventQuery(e->ev_et[k][1]) != hipSuccess) continue;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev_et[k][0], e->ev_et[k][1]));
+    e->et_ms_sum += ms;
+    e->et_timed++;
+    e->et_pending[k] = false;
   }
   return FVAD_OK;
 }
@@ -1503,6 +1648,8 @@ extern "C" int fvad_engine_clear_times(fvad_engine *e) {
     e->vadm_ms_sum[k] = 0;
     e->vadm_timed[k] = 0;
   }
+  e->et_ms_sum = 0;
+  e->et_timed = 0;
   e->n_timed = 0;
   e->res_count = 0;
   return FVAD_OK;
@@ -1708,6 +1855,108 @@ extern "C" size_t fvad_engine_segments_range(fvad_engine *e, int stream, int mac
 }
 
 // ---------------------------------------------------------------------------
+// Speech event feed
+// ---------------------------------------------------------------------------
+static_assert(sizeof(fvad_event) == 48 && sizeof(fvad::VadmEvent) == sizeof(fvad_event), "fvad_event is 48 bytes");
+static_assert(offsetof(fvad_event, push) == offsetof(fvad::VadmEvent, push) &&
+                  offsetof(fvad_event, sample_to) == offsetof(fvad::VadmEvent, sample_to) &&
+                  offsetof(fvad_event, debug_avg_speech_vol_ratio) ==
+                      offsetof(fvad::VadmEvent, debug_avg_speech_vol_ratio),
+              "the device's event record is fvad_event");
+
+extern "C" int fvad_engine_enable_events(fvad_engine *e, size_t ring_capacity) {
+  if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (e->vadm.n == 0) return fail(FVAD_EINVAL, "no VADMachines attached");
+  if (e->events_on) return fail(FVAD_EINVAL, "events already enabled");
+  for (const auto &sl : e->slots)
+    if (sl.pending) return fail(FVAD_EINVAL, "submitted pushes not collected yet");
+  if (ring_capacity == 0) ring_capacity = 65536;
+  if (ring_capacity > (size_t)1 << 26) return fail(FVAD_EINVAL, "ring_capacity above 2^26 events");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  // a push whose machine pass is still pending runs it now, without events
+  if (e->vpend)
+    if (const int rc = vadm_flush(e, false)) return rc;
+  const size_t lanes = (size_t)e->cfg.n_streams * e->vadm.n;
+  const int ev_cap = e->wmax;  // windows of one stream in a push at most (one event each at most)
+  fvad::VadmEvRec *stage = nullptr;
+  unsigned *count = nullptr;
+  unsigned long long *cursor = nullptr;
+  void *ring = nullptr, *hdr = nullptr;
+  hipEvent_t et[4] = {};
+  auto undo = [&](int code, const char *what) {
+    void *d[] = {stage, count, cursor};
+    for (void *p : d)
+      if (p) (void)hipFree(p);
+    if (ring) (void)hipHostFree(ring);
+    if (hdr) (void)hipHostFree(hdr);
+    for (hipEvent_t ev : et)
+      if (ev) (void)hipEventDestroy(ev);
+    (void)hipGetLastError();
+    return fail(code, what);
+  };
+  if (hipMalloc(reinterpret_cast<void **>(&stage), lanes * ev_cap * sizeof(fvad::VadmEvRec)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&count), lanes * sizeof(unsigned)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&cursor), 2 * sizeof(unsigned long long)) != hipSuccess ||
+      hipHostMalloc(&ring, ring_capacity * sizeof(fvad_event), hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc(&hdr, sizeof(fvad::VadmEventHeader) * fvad_engine::kEvHeaders, hipHostMallocDefault) != hipSuccess)
+    return undo(FVAD_ENOMEM, "allocation failed (event feed)");
+  void *dv_ring = nullptr, *dv_hdr = nullptr;
+  if (hipHostGetDevicePointer(&dv_ring, ring, 0) != hipSuccess || hipHostGetDevicePointer(&dv_hdr, hdr, 0) != hipSuccess)
+    return undo(FVAD_EDEVICE, "hipHostGetDevicePointer failed (event feed)");
+  for (hipEvent_t &ev : et)
+    if (hipEventCreate(&ev) != hipSuccess) return undo(FVAD_EDEVICE, "event creation failed (event feed)");
+  if (hipMemset(count, 0, lanes * sizeof(unsigned)) != hipSuccess ||
+      hipMemset(cursor, 0, 2 * sizeof(unsigned long long)) != hipSuccess)
+    return undo(FVAD_EDEVICE, "hipMemset failed (event feed)");
+  std::memset(hdr, 0xff, sizeof(fvad::VadmEventHeader) * fvad_engine::kEvHeaders);
+  e->vadm.ev_stage = stage;
+  e->vadm.ev_count = count;
+  e->vadm.ev_cap = ev_cap;
+  e->d_ev_cursor = cursor;
+  e->h_ev_ring = static_cast<fvad_event *>(ring);
+  e->dv_ev_ring = static_cast<fvad::VadmEvent *>(dv_ring);
+  e->h_ev_hdr = static_cast<fvad::VadmEventHeader *>(hdr);
+  e->dv_ev_hdr = static_cast<fvad::VadmEventHeader *>(dv_hdr);
+  e->ev_ring_cap = ring_capacity;
+  e->ev_read = e->ev_end = e->ev_lost = e->ev_pass_next = 0;
+  for (int k = 0; k < 4; k++) e->ev_et[k / 2][k % 2] = et[k];
+  e->events_on = true;
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_poll_events(fvad_engine *e, fvad_event *out, size_t cap, size_t *n, uint64_t *lost) {
+  if (n) *n = 0;
+  if (!e || !n || (cap > 0 && !out)) return fail(FVAD_EINVAL, "invalid argument");
+  if (!e->events_on) return fail(FVAD_EINVAL, "events not enabled");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  if (const int rc = events_retire(e, false)) return rc;
+  const size_t k = (size_t)std::min<uint64_t>(cap, e->ev_end - e->ev_read);
+  for (size_t i = 0; i < k; i++) out[i] = e->h_ev_ring[(e->ev_read + i) % e->ev_ring_cap];
+  e->ev_read += k;
+  *n = k;
+  if (lost) *lost = e->ev_lost;
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_event_progress(fvad_engine *e, uint64_t *pushes_done) {
+  if (!e || !pushes_done) return fail(FVAD_EINVAL, "null argument");
+  if (!e->events_on) return fail(FVAD_EINVAL, "events not enabled");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  if (const int rc = events_retire(e, false)) return rc;
+  *pushes_done = e->ev_pushes_done;
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_event_times(fvad_engine *e, double *ms_avg, int *n_runs) {
+  if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
+  if (!e->events_on) return fail(FVAD_EINVAL, "events not enabled");
+  if (const int rc = fvad_engine_sync(e)) return rc;
+  *ms_avg = e->et_timed ? e->et_ms_sum / e->et_timed : 0.0;
+  if (n_runs) *n_runs = e->et_timed;
+  return FVAD_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Checker access: the whole device machine state and the test hooks
 // ---------------------------------------------------------------------------
 namespace {
@@ -1818,6 +2067,10 @@ extern "C" int fvad_engine_set_debug(fvad_engine *e, int key, int value) {
       return vadm_reset(e);
     case FVAD_DEBUG_RESET_TIMES:
       e->dbg_reset_times = value != 0;
+      return FVAD_OK;
+    case FVAD_DEBUG_EVENTS_CHUNK:
+      if (value < 0) return fail(FVAD_EINVAL, "value >= 0 required");
+      e->dbg_events_chunk = value;
       return FVAD_OK;
     default:
       return fail(FVAD_EINVAL, "unknown debug key");

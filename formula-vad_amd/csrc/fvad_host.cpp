@@ -249,6 +249,14 @@ extern "C" size_t fvad_vadm_segments(const fvad_vadm *v, fvad_segment *out, size
   return segs.size();
 }
 
+extern "C" int fvad_vadm_state(const fvad_vadm *v, int *speech_state, uint64_t *speech_start, uint64_t *speech_end) {
+  if (!v) return FVAD_EINVAL;
+  if (speech_state) *speech_state = (int)v->m.state;
+  if (speech_start) *speech_start = v->m.speech_start;
+  if (speech_end) *speech_end = v->m.speech_end;
+  return FVAD_OK;
+}
+
 namespace {
 struct StreamMachines {
   std::vector<VADMachine> machines;  // [0] = main; they run on the device (k_vadm_hbm)

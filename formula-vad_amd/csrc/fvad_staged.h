@@ -60,6 +60,36 @@ struct VadmSeg {
   unsigned long long sample_from, sample_to;
   float debug_rnn_vad, debug_avg_speech_vol_ratio;
 };
+// Speech events (fvad_engine_enable_events).  A machine pass stages its events
+// per lane (lane = stream * n_machines + machine: ev_cap records and a count),
+// k_vadm_events then packs them into the engine's ring in lane order.
+struct VadmEvRec {  // 32 bytes
+  unsigned kind, seq;  // FVAD_EVENT_*; segments the machine had emitted before
+  unsigned long long sample_from, sample_to;
+  float debug_rnn_vad, debug_avg_speech_vol_ratio;
+};
+struct VadmEvent {  // fvad_event (include/fvad.h), 48 bytes
+  unsigned kind;
+  int stream, machine;
+  unsigned seq;
+  unsigned long long push, sample_from, sample_to;
+  float debug_rnn_vad, debug_avg_speech_vol_ratio;
+};
+struct VadmEventHeader {  // what a finished k_vadm_events tells the host
+  unsigned long long pass, end, lost, n;  // pass ordinal, ring cursor after it, events lost so far, events it staged
+};
+struct VadmEventArgs {
+  VadmEvRec *stage;   // [lane][ev_cap]
+  unsigned *count;    // [lane], left at 0 for the next pass
+  int ev_cap, n_lanes, n_machines;
+  int chunk;          // test hook (FVAD_DEBUG_EVENTS_CHUNK): lanes per iteration; 0 = the workgroup's size
+  VadmEvent *ring;    // [ring_cap], written at cursor % ring_cap
+  unsigned long long ring_cap;
+  unsigned long long *cursor;  // device: [0] write cursor, [1] events lost
+  VadmEventHeader *header;
+  unsigned long long pass, push;
+  unsigned long long host_read;  // the host's read cursor when the pass was enqueued (<= the true one)
+};
 struct VadmArgs {
   int n;  // machines (0: k_vadm not launched)
   VadmConst c[kMaxBandCfg];
@@ -76,6 +106,9 @@ struct VadmArgs {
   unsigned long long *count;  // test hook (FVAD_DEBUG_VADM_COUNT): null, or [kVadmCounts] device counters
   long long negate_at;   // test hook (FVAD_DEBUG_VADM_NEGATE_AT): window number whose band minimum enters
                          //   the machine negated (lt_neg's path); -1 = none
+  VadmEvRec *ev_stage;   // null (no event feed), or the pass's staging area [lane][ev_cap]
+  unsigned *ev_count;    // [lane] records staged
+  int ev_cap;            // records per lane: the windows a stream can complete in one push (one event each at most)
 };
 // the lazy long-term walk's counters (FVAD_DEBUG_VADM_COUNT): long-term tests
 // decided from an exact average, from the estimate, left open by the bound (an
@@ -182,6 +215,9 @@ hipError_t launch_wave(WaveKernel which, const StagedArgs &a, int n_cu, hipStrea
 // else queued) where it applies, else k_vadm_hbm (32 waves, overlaps quietly);
 // *ran_par (nullable): which of the two was launched
 hipError_t launch_vadm(const StagedArgs &a, hipStream_t stream, bool fast = false, bool *ran_par = nullptr);
+// k_vadm_events: the events the machine pass before it on `stream` staged,
+// packed into the ring in (stream, machine, production) order
+hipError_t launch_vadm_events(const VadmEventArgs &a, hipStream_t stream);
 // use_denoiser = 0 (VAD.zig:206-212,239-249): k_ndring, k_ndmeta, FFT B
 hipError_t launch_nodenoise(const StagedArgs &a, int n_cu, hipStream_t stream);
 // k_fftb's scratch need: 0 when a transform fits in LDS, else float2 per workgroup

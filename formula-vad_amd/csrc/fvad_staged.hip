@@ -1800,9 +1800,48 @@ __device__ __forceinline__ bool vadm_short(VadmState &S, const VadmConst &K, flo
   const double threshold = base * (double)K.thr_factor;
   return st_avg > threshold && r_avg > (double)K.ratio_thr;
 }
+// The event feed's staging area of one lane (stream, machine): ev_cap records
+// and their count in HBM, touched only in the two arms that produce an event.
+// A window produces at most one event -- the Opening -> Open arm and the
+// Closing -> Closed arm (onSpeechEnd) are different cases of one switch -- so a
+// lane stages at most as many records as its stream completes windows in the
+// push, and ev_cap is the engine's bound on those (its wmax, which also sizes
+// win_tick / win_start); the k < cap test below can therefore not drop one.
+struct VadmEvLane {
+  VadmEvRec *rec;  // null: no event feed
+  unsigned *n;
+  int cap;
+};
+__device__ __forceinline__ VadmEvLane vadm_ev_lane(const VadmArgs &v, int m, int s) {
+  VadmEvLane l{nullptr, nullptr, 0};
+  if (v.ev_stage) {
+    const size_t lane = (size_t)s * v.n + m;
+    l.rec = v.ev_stage + lane * v.ev_cap;
+    l.n = v.ev_count + lane;
+    l.cap = v.ev_cap;
+  }
+  return l;
+}
+__device__ __forceinline__ void vadm_ev_put(const VadmEvLane &l, unsigned kind, unsigned seq, unsigned long long from,
+                                            unsigned long long to, float rnn_vad, float vol_ratio) {
+  const unsigned k = *l.n;
+  if (k < (unsigned)l.cap) {
+    VadmEvRec r;
+    r.kind = kind;
+    r.seq = seq;
+    r.sample_from = from;
+    r.sample_to = to;
+    r.debug_rnn_vad = rnn_vad;
+    r.debug_avg_speech_vol_ratio = vol_ratio;
+    l.rec[k] = r;
+    *l.n = k + 1;
+  }
+}
+enum { kVeSpeechOpen = 1, kVeSegment = 2 };  // FVAD_EVENT_SPEECH_OPEN, FVAD_EVENT_SEGMENT (include/fvad.h)
+
 // the speech-state transition, segment output and tracking of one window
 __device__ __forceinline__ void vadm_fsm(VadmState &S, const VadmConst &K, unsigned long long index, bool met,
-                                         float vad, float vr, VadmSeg *seg, int seg_cap) {
+                                         float vad, float vr, VadmSeg *seg, int seg_cap, const VadmEvLane &ev) {
   const int from = S.state;
   bool ended = false;
   switch (from) {
@@ -1813,10 +1852,12 @@ __device__ __forceinline__ void vadm_fsm(VadmState &S, const VadmConst &K, unsig
       }
       break;
     case kVmOpening:
-      if (met && index - S.speech_start >= K.min_open)
+      if (met && index - S.speech_start >= K.min_open) {
         S.state = kVmOpen;
-      else if (!met)
+        if (ev.rec) vadm_ev_put(ev, kVeSpeechOpen, S.n_segs, S.speech_start, index, 0.0f, 0.0f);
+      } else if (!met) {
         S.state = kVmClosed;
+      }
       break;
     case kVmOpen:
       if (!met) {
@@ -1837,13 +1878,16 @@ __device__ __forceinline__ void vadm_fsm(VadmState &S, const VadmConst &K, unsig
     const unsigned long long len = S.speech_end - S.speech_start;
     const float len_rt = (float)len / K.sr;
     if (len_rt >= K.min_dur) {
-      if (S.n_segs < (unsigned)seg_cap) {
+      if (S.n_segs < (unsigned)seg_cap || ev.rec) {  // (the feed carries segments past seg_cap too)
         VadmSeg g;
         g.sample_from = K.rec_pad > S.speech_start ? 0ull : S.speech_start - K.rec_pad;
         g.sample_to = S.speech_end + K.rec_pad;
         g.debug_rnn_vad = S.rnn_vad / (float)S.rnn_vad_count;
         g.debug_avg_speech_vol_ratio = S.vol_ratio / (float)S.vol_ratio_count;
-        seg[S.n_segs] = g;
+        if (S.n_segs < (unsigned)seg_cap) seg[S.n_segs] = g;
+        if (ev.rec)
+          vadm_ev_put(ev, kVeSegment, S.n_segs, g.sample_from, g.sample_to, g.debug_rnn_vad,
+                      g.debug_avg_speech_vol_ratio);
       }
       S.n_segs++;
     }
@@ -1924,6 +1968,7 @@ __device__ void vadm_stream(const StagedArgs &a, int m, int s, float *lt, size_t
   VadmState S = a.vadm.st[(size_t)m * B + s];
   float *st = a.vadm.buf + K.st_off + s, *rb = a.vadm.buf + K.r_off + s;
   VadmSeg *seg = a.vadm.seg + ((size_t)m * B + s) * a.vadm.seg_cap;
+  const VadmEvLane ev = vadm_ev_lane(a.vadm, m, s);
   const unsigned n = (unsigned)K.n_lt;
   const double f = (double)K.thr_factor, scalar = 1.0 / (double)n;
   const bool lazy = S.lt_count == n && S.lt_pre_ok && S.lt_has && n > 1 && f >= 0.0 &&
@@ -2012,7 +2057,7 @@ __device__ void vadm_stream(const StagedArgs &a, int m, int s, float *lt, size_t
           if (S.lt_neg) bscale = __builtin_inf();
         }
       }
-      vadm_fsm(S, K, index, met, vad, vr, seg, a.vadm.seg_cap);
+      vadm_fsm(S, K, index, met, vad, vr, seg, a.vadm.seg_cap, ev);
     }
   if (pending && (final || (unsigned)pending >= (a.vadm.defer_max ? a.vadm.defer_max : kLtDeferMax))) {
     fold();
@@ -2128,6 +2173,7 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
     VadmState &S = Ss[g];
     float *st = a.vadm.buf + K.st_off + (sok ? s : 0), *rb = a.vadm.buf + K.r_off + (sok ? s : 0);
     VadmSeg *seg = a.vadm.seg + ((size_t)m * B + (sok ? s : 0)) * a.vadm.seg_cap;
+    const VadmEvLane ev = vadm_ev_lane(a.vadm, m, sok ? s : 0);
     // (n > kVpMaxW: a push wraps around the buffer at most once)
     const bool forced = a.vadm.par_serial_every > 0 && s % a.vadm.par_serial_every == 0;
     const bool fast = sok && !forced && Kw <= kVpMaxW && K.n_lt > kVpMaxW && S.lt_count == (unsigned)K.n_lt &&
@@ -2152,7 +2198,7 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
           const bool met = vadm_short(S, K, st, rb, B, wmin[g][j], wvr[g][j]);
           if (!met) break;  // window j pushes: its short-term pushes are done, its long push waits for the folds
           S.windows_done++;
-          vadm_fsm(S, K, index, met, wvad[g][j], wvr[g][j], seg, a.vadm.seg_cap);
+          vadm_fsm(S, K, index, met, wvad[g][j], wvr[g][j], seg, a.vadm.seg_cap, ev);
           j++;
         }
         if (j >= Kw) rnd[g][2] = 1;
@@ -2215,7 +2261,7 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
             npush++;
           }
           S.windows_done++;
-          vadm_fsm(S, K, index, met, wvad[g][jj], wvr[g][jj], seg, a.vadm.seg_cap);
+          vadm_fsm(S, K, index, met, wvad[g][jj], wvr[g][jj], seg, a.vadm.seg_cap, ev);
           j = jj + 1;
           if (met) break;
         }
@@ -2592,6 +2638,92 @@ hipError_t launch_vadm(const StagedArgs &a, hipStream_t stream, bool fast, bool 
                     stream, a);
   else
     FVAD_KERNEL_TRY(k_vadm_par, dim3((a.n_streams + kVpS - 1) / kVpS), dim3(kVpS * kVpG), 0, stream, a);
+  return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------
+// k_vadm_events: the records a machine pass staged per lane (lane = stream *
+// n_machines + machine), packed into the engine's event ring in lane order,
+// each lane's in the order the machine produced them.  One workgroup, right
+// after the pass on the same stream: an exclusive scan of the lanes' counts
+// (a shuffle scan per wave, the waves' totals through LDS, the chunks of
+// kEvThreads lanes chained by a carried base) gives every record its place, so
+// the order needs no atomics and is the same whichever machine kernel ran.
+// Ring overflow: the pass writes the records that fit behind the cursor --
+// room = capacity - (cursor - host_read), host_read the host's read cursor when
+// the pass was enqueued, never ahead of the true one -- and counts the rest as
+// lost; unread events are never overwritten.  The cursor and the lost count
+// live in device memory (passes of an engine run in order on its side stream);
+// the header tells the host, once the event recorded behind this kernel has
+// completed, how far the ring is valid.  Every count is left at 0 for the
+// next pass.
+// ---------------------------------------------------------------------------
+constexpr int kEvThreads = 256;
+__global__ void __launch_bounds__(kEvThreads) k_vadm_events(VadmEventArgs a) {
+  __shared__ unsigned wsum[kEvThreads / 64];
+  const int tid = threadIdx.x, wl = tid & 63, wave = tid >> 6;
+  const unsigned long long wr0 = a.cursor[0];
+  const unsigned long long used = wr0 - a.host_read;
+  const unsigned long long room = used < a.ring_cap ? a.ring_cap - used : 0ull;
+  const int chunk = a.chunk > 0 && a.chunk < kEvThreads ? a.chunk : kEvThreads;
+  unsigned long long base = 0;  // records of the lanes before this chunk
+  for (int l0 = 0; l0 < a.n_lanes; l0 += chunk) {
+    const int l = l0 + tid;
+    const bool on = tid < chunk && l < a.n_lanes;
+    const unsigned c = on ? min(a.count[l], (unsigned)a.ev_cap) : 0u;
+    unsigned inc = c;  // inclusive scan over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = __shfl_up(inc, d);
+      if (wl >= d) inc += up;
+    }
+    if (wl == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kEvThreads / 64; w++) {
+      const unsigned v = wsum[w];
+      if (w < wave) before += v;
+      total += v;
+    }
+    const unsigned long long first = base + before + (inc - c);
+    for (unsigned j = 0; j < c; j++) {
+      const unsigned long long pos = first + j;
+      if (pos >= room) break;
+      const VadmEvRec r = a.stage[(size_t)l * a.ev_cap + j];
+      VadmEvent e;
+      e.kind = r.kind;
+      e.stream = l / a.n_machines;
+      e.machine = l % a.n_machines;
+      e.seq = r.seq;
+      e.push = a.push;
+      e.sample_from = r.sample_from;
+      e.sample_to = r.sample_to;
+      e.debug_rnn_vad = r.debug_rnn_vad;
+      e.debug_avg_speech_vol_ratio = r.debug_avg_speech_vol_ratio;
+      a.ring[(wr0 + pos) % a.ring_cap] = e;
+    }
+    if (c) a.count[l] = 0;
+    base += total;
+    __syncthreads();  // wsum is rewritten by the next chunk
+  }
+  if (tid == 0) {
+    const unsigned long long written = base < room ? base : room;
+    const unsigned long long lost = a.cursor[1] + (base - written);
+    a.cursor[0] = wr0 + written;
+    a.cursor[1] = lost;
+    VadmEventHeader h;
+    h.pass = a.pass;
+    h.end = wr0 + written;
+    h.lost = lost;
+    h.n = base;
+    *a.header = h;
+  }
+}
+
+hipError_t launch_vadm_events(const VadmEventArgs &a, hipStream_t stream) {
+  (void)hipGetLastError();
+  FVAD_KERNEL_TRY(k_vadm_events, dim3(1), dim3(kEvThreads), 0, stream, a);
   return hipSuccess;
 }
 

@@ -98,6 +98,8 @@ class VadmSnapshot(C.Structure):
 
 DEBUG_VADM_PAR_SERIAL_EVERY, DEBUG_VADM_ALWAYS_PAR, DEBUG_VADM_LT_FULL, DEBUG_VADM_DEFER_MAX = 1, 2, 3, 4
 DEBUG_VADM_BOUND_SCALE, DEBUG_VADM_COUNT, DEBUG_VADM_NEGATE_AT, DEBUG_RESET_TIMES = 5, 6, 7, 8
+DEBUG_EVENTS_CHUNK = 9
+EVENT_SPEECH_OPEN, EVENT_SEGMENT = 1, 2  # fvad_event.kind
 SHARE_PREP, SHARE_SIDE = 1, 2  # fvad_engine_share_streams
 
 # stream blobs (fvad_engine_save_streams): include/fvad.h documents the layout
@@ -120,6 +122,16 @@ READ_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_int, C.POINTER(F32P), C.c_size
 class Segment(C.Structure):
     _fields_ = [("sample_from", C.c_uint64), ("sample_to", C.c_uint64), ("debug_rnn_vad", C.c_float),
                 ("debug_avg_speech_vol_ratio", C.c_float)]
+
+
+class Event(C.Structure):
+    """fvad_event (include/fvad.h): one entry of the speech event feed, 48 bytes."""
+    _fields_ = [("kind", C.c_uint32), ("stream", C.c_int32), ("machine", C.c_int32), ("seq", C.c_uint32),
+                ("push", C.c_uint64), ("sample_from", C.c_uint64), ("sample_to", C.c_uint64),
+                ("debug_rnn_vad", C.c_float), ("debug_avg_speech_vol_ratio", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class StatConfig(C.Structure):
@@ -200,6 +212,11 @@ SYMBOLS = [
                                          C.POINTER(C.c_uint64)]),
     ("fvad_engine_vadm_snapshot", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("fvad_engine_vadm_rolling", C.c_long, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    ("fvad_engine_enable_events", C.c_int, [C.c_void_p, C.c_size_t]),
+    ("fvad_engine_poll_events", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_uint64)]),
+    ("fvad_engine_event_progress", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("fvad_engine_event_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("fvad_engine_set_debug", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("fvad_engine_debug_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("fvad_engine_share_streams", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
@@ -213,6 +230,7 @@ SYMBOLS = [
     ("fvad_vadm_bins", None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fvad_vadm_run", C.c_int, [C.c_void_p, C.c_uint64, F32P, C.c_float, C.c_float]),
     ("fvad_vadm_segments", C.c_size_t, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("fvad_vadm_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fvad_pipeline_create", C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.POINTER(C.c_void_p)]),
     ("fvad_pipeline_destroy", None, [C.c_void_p]),
@@ -527,6 +545,32 @@ class Engine:
         lib().fvad_engine_segments(self.h, stream, machine, buf, n)
         return [(s.sample_from, s.sample_to, s.debug_rnn_vad, s.debug_avg_speech_vol_ratio) for s in buf[:n]]
 
+    def enable_events(self, capacity=0):
+        """Start the speech event feed (fvad_engine_enable_events): after attach_vadm, with
+        no submitted push uncollected; capacity events held between polls (0: the default)."""
+        _check(lib().fvad_engine_enable_events(self.h, capacity), "fvad_engine_enable_events")
+
+    def poll_events(self, max_events=4096):
+        """(events of the machine passes the device has finished, as dicts in feed order;
+        events lost to a full ring so far).  Never waits for the device."""
+        buf = (Event * max(1, max_events))()
+        n, lost = C.c_size_t(), C.c_uint64()
+        _check(lib().fvad_engine_poll_events(self.h, buf, max_events, C.byref(n), C.byref(lost)),
+               "fvad_engine_poll_events")
+        return [buf[i].as_dict() for i in range(n.value)], lost.value
+
+    def event_progress(self):
+        """Pushes (ordinals below the result) whose events have all been polled or are ready."""
+        n = C.c_uint64()
+        _check(lib().fvad_engine_event_progress(self.h, C.byref(n)), "fvad_engine_event_progress")
+        return n.value
+
+    def event_times(self):
+        """(k_vadm_events' average ms over the timed passes, how many) -- a sync point."""
+        ms, n = C.c_double(), C.c_int()
+        _check(lib().fvad_engine_event_times(self.h, C.byref(ms), C.byref(n)), "fvad_engine_event_times")
+        return ms.value, n.value
+
     def vadm_snapshot(self, stream, machine=0):
         """The device machine's whole state (fvad_engine_vadm_snapshot) as a dict."""
         s = VadmSnapshot()
@@ -550,7 +594,7 @@ class Engine:
 
     def set_debug(self, key, value):
         """Test hooks (fvad_engine_set_debug): DEBUG_VADM_PAR_SERIAL_EVERY, DEBUG_VADM_ALWAYS_PAR,
-        DEBUG_VADM_LT_FULL, DEBUG_VADM_DEFER_MAX, DEBUG_VADM_BOUND_SCALE, DEBUG_VADM_COUNT."""
+        DEBUG_VADM_LT_FULL, DEBUG_VADM_DEFER_MAX, DEBUG_VADM_BOUND_SCALE, DEBUG_VADM_COUNT, DEBUG_EVENTS_CHUNK."""
         _check(lib().fvad_engine_set_debug(self.h, key, value), "fvad_engine_set_debug")
 
     def debug_counts(self):
@@ -599,7 +643,7 @@ class EngineGroup:
     GPU unless asked (--groups).  Engine g owns streams
     [first[g], first[g] + sizes[g])."""
 
-    def __init__(self, model, n_streams, n_channels=2, groups=2, vadm=False, **kw):
+    def __init__(self, model, n_streams, n_channels=2, groups=2, vadm=False, seg_capacity=256, **kw):
         if not 1 <= groups <= n_streams:
             raise ValueError("groups must be in [1, n_streams]")
         q, r = divmod(n_streams, groups)
@@ -611,8 +655,8 @@ class EngineGroup:
             # engine g's streams exist before engine g + 1's: the runtime hands
             # out hardware queues in creation order
             e = Engine(model, n, n_channels, **kw)
-            if vadm:
-                e.attach_vadm()
+            if vadm:  # True: the default machine; or a list of VadmConfig
+                e.attach_vadm(None if vadm is True else vadm, seg_capacity)
             if g and kw.get("mode", "staged") != "fused":  # the fused engine has no side streams
                 e.share_streams(self.engines[0], SHARE_PREP | (SHARE_SIDE if vadm else 0))
             self.engines.append(e)
@@ -649,6 +693,42 @@ class EngineGroup:
     def segments(self, stream, machine=0):
         g = max(i for i, f in enumerate(self.first) if f <= stream)
         return self.engines[g].segments(stream - self.first[g], machine)
+
+    def enable_events(self, capacity=0):
+        """Engine.enable_events on every engine of the group (capacity each)."""
+        for e in self.engines:
+            e.enable_events(capacity)
+        self._ev_q = [[] for _ in self.engines]
+
+    def poll_events(self, max_events=4096):
+        """The engines' feeds as one, stream numbers in the group's numbering:
+        ascending push, then stream (engine g's streams come before engine
+        g + 1's), then each engine's own order.  A push's events are delivered
+        once every engine's machine pass for it has finished
+        (Engine.event_progress): (events, lost summed over the engines);
+        max_events sizes each engine's polls, not the result."""
+        lost = 0
+        done = [e.event_progress() for e in self.engines]  # before the polls: all of these get drained
+        for g, e in enumerate(self.engines):
+            while True:
+                ev, l = e.poll_events(max_events)
+                for d in ev:
+                    d["stream"] += self.first[g]
+                self._ev_q[g].extend(ev)
+                if len(ev) < max_events:
+                    break
+            lost += l
+        upto = min(done)
+        out = []
+        for g in range(len(self.engines)):
+            q = self._ev_q[g]
+            k = 0
+            while k < len(q) and q[k]["push"] < upto:
+                k += 1
+            out.extend(q[:k])
+            del q[:k]
+        out.sort(key=lambda d: d["push"])  # stable: engines are already in stream order
+        return out, lost
 
     def reset_streams(self, global_ids):
         """Engine.reset_streams over the group's stream numbering."""
@@ -736,6 +816,12 @@ class VADMachine:
     def run(self, index, band_per_channel, vad, vol_ratio):
         b = np.ascontiguousarray(band_per_channel, np.float32)
         _check(lib().fvad_vadm_run(self.h, index, fptr(b), vad, vol_ratio), "fvad_vadm_run")
+
+    def state(self):
+        """(speech state 0 closed / 1 opening / 2 open / 3 closing, speech start, speech end)"""
+        st, a, b = C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(lib().fvad_vadm_state(self.h, C.byref(st), C.byref(a), C.byref(b)), "fvad_vadm_state")
+        return st.value, a.value, b.value
 
     def segments(self):
         n = lib().fvad_vadm_segments(self.h, None, 0)

@@ -369,6 +369,10 @@ void fvad_vadm_destroy(fvad_vadm *v);
 void fvad_vadm_bins(const fvad_vadm *v, int *lo, int *hi);
 int fvad_vadm_run(fvad_vadm *v, uint64_t index, const float *band_per_channel, float vad, float vol_ratio);
 size_t fvad_vadm_segments(const fvad_vadm *v, fvad_segment *out, size_t cap);
+/* speech state (0 closed, 1 opening, 2 open, 3 closing) and the current speech
+ * start / end sample indices, as fvad_engine_vadm_state reports them (each
+ * output nullable) */
+int fvad_vadm_state(const fvad_vadm *v, int *speech_state, uint64_t *speech_start, uint64_t *speech_end);
 
 /* Device VADMachines (VADMachine.zig:126-230 run on the GPU, one lane per
  * stream, after FFT B of every push).  Staged engines only.
@@ -410,6 +414,51 @@ int fvad_engine_vadm_snapshot(fvad_engine *e, int stream, int machine, fvad_vadm
  * 2 volume ratio, as doubles: copies min(len, cap) entries, returns len (< 0:
  * error code) */
 long fvad_engine_vadm_rolling(fvad_engine *e, int stream, int machine, int which, double *out, size_t cap);
+
+/* Speech event feed: what the device VADMachines decided, push by push,
+ * without a sync point.  Every reader above waits for the queued pushes and
+ * serves one (stream, machine); the feed is one list for the whole engine that
+ * a poll reads without waiting, it is lossless past seg_capacity, and it also
+ * reports speech starting. */
+#define FVAD_EVENT_SPEECH_OPEN 1 /* Opening -> Open (VADMachine.zig run) */
+#define FVAD_EVENT_SEGMENT 2     /* onSpeechEnd emitted a segment (len >= min_vad_duration_sec) */
+typedef struct {
+  uint32_t kind;
+  int32_t stream, machine;
+  uint32_t seq;  /* segments this (stream, machine) had emitted before this event; for SEGMENT its index
+                    in fvad_engine_segments' list (also past seg_capacity) */
+  uint64_t push; /* ordinal of the producing push since create / fvad_engine_reset (the first is 0) */
+  uint64_t sample_from, sample_to; /* SEGMENT: the fvad_segment's; OPEN: speech_start_index, and the start
+                                      index of the window in which the machine opened */
+  float debug_rnn_vad, debug_avg_speech_vol_ratio; /* SEGMENT: the fvad_segment's; OPEN: 0 */
+} fvad_event; /* 48 bytes, little endian, no padding */
+/* Start the feed (after fvad_engine_attach_vadm, once, with no push submitted
+ * and not yet collected: FVAD_EINVAL otherwise); events start with the next
+ * submitted push.  ring_capacity: events the engine holds between polls, 0 =
+ * the default (65536).  FVAD_ENOMEM leaves the engine unchanged.  An engine
+ * that never calls it launches and allocates nothing for the feed. */
+int fvad_engine_enable_events(fvad_engine *e, size_t ring_capacity);
+/* Up to cap events of the machine passes that have finished on the device, in
+ * order: ascending push, then stream, then machine, then as the machine
+ * produced them -- the same list for the same pushes whatever the schedule.
+ * Never waits for queued pushes or for a machine pass (a push's pass is
+ * enqueued with the next push or at a sync point, see above); after
+ * fvad_engine_sync, polls deliver every event of every push submitted so far.
+ * *n: events written; *lost (nullable): events dropped so far because the
+ * ring was full -- a pass writes what fits behind the unpolled events, in
+ * order, and counts the rest; polling makes room for later passes.
+ * fvad_engine_reset discards unpolled events and zeroes push and lost;
+ * fvad_engine_reset_streams leaves queued events in place and restarts the
+ * listed streams' seq at 0; fvad_engine_restore_streams continues seq from the
+ * blob's segment count (a stream restored Open emits no second OPEN). */
+int fvad_engine_poll_events(fvad_engine *e, fvad_event *out, size_t cap, size_t *n, uint64_t *lost);
+/* How far the feed has got, without waiting: *pushes_done = p means every event
+ * of the pushes with ordinal < p has been polled or is ready to be (what a
+ * host merging several engines' feeds per push needs). */
+int fvad_engine_event_progress(fvad_engine *e, uint64_t *pushes_done);
+/* k_vadm_events' own time: the average (ms) over the timed passes since the
+ * last fvad_engine_clear_times, and how many (synchronises the engine) */
+int fvad_engine_event_times(fvad_engine *e, double *ms_avg, int *n_runs);
 
 /* Several engines on one GPU (e.g. a GPU's streams split into sub-partitions
  * that push concurrently): e runs its k_prep3 (FVAD_SHARE_PREP) and / or its
@@ -462,6 +511,10 @@ int fvad_engine_share_streams(fvad_engine *e, fvad_engine *other, int which);
 /*   FVAD_DEBUG_RESET_TIMES  value 1: fvad_engine_reset_streams brackets each of
  *     its launches with a timing event pair (fvad_engine_reset_times) */
 #define FVAD_DEBUG_RESET_TIMES 8
+/*   FVAD_DEBUG_EVENTS_CHUNK  value k > 0: k_vadm_events packs k lanes per
+ *     iteration (k below its workgroup size: the carry across chunks at a
+ *     small engine); 0: the default.  Results are the same for every k */
+#define FVAD_DEBUG_EVENTS_CHUNK 9
 int fvad_engine_set_debug(fvad_engine *e, int key, int value);
 /* FVAD_DEBUG_RESET_TIMES' samples: average event time (ms) of a
  * fvad_engine_reset_streams call's launches on [0] the engine stream, [1] the
