@@ -379,6 +379,44 @@ __device__ __forceinline__ float band_chain(const float *lo, const float *hi, co
   if (b == 0 || b == kBands - 1) acc *= 2;
   return acc;
 }
+// band_chain as one straight line for every lane (k_fftAw): kChainBlocks block
+// steps over the band's hi terms, then kChainBlocks over its lo terms, a lane
+// keeping its sum where a step lies past its own count (a select; the adds it
+// does take are band_chain's, in its order, so the sums are the same bits).
+// band_chain's divergent loops run to the widest band anyway (22 + 22 steps)
+// and wait out the LDS latency at every step; here the loads have immediate
+// offsets from one base per phase, kChainAhead blocks are in flight across the
+// whole line (the lo phase's first loads issue before the hi phase's last
+// adds), and chain_hold keeps the compiler from sinking a load back to its
+// adds.  No lane reads past its array: a phase's base is a band edge at most
+// kChainBlocks blocks before the last edge (fvad_plan.cpp checks the table).
+constexpr int kChainAhead = 3;  // blocks in flight
+__device__ __forceinline__ void chain_hold(float &acc) { asm volatile("" : "+v"(acc) : : "memory"); }
+__device__ __forceinline__ float band_chain_ahead(const float *lo, const float *hi, const BandEdges &T, int b) {
+  const int qa = T.e4[b >= 1 ? b - 1 : 0] >> 2, qb = T.e4[b] >> 2, qc = T.e4[b <= kBands - 2 ? b + 1 : b] >> 2;
+  const int nh = qb - qa, nl = qc - qb;  // 0 for band 0's hi and the last band's lo
+  const float4 *h4 = reinterpret_cast<const float4 *>(hi) + qa;
+  const float4 *l4 = reinterpret_cast<const float4 *>(lo) + (b <= kBands - 2 ? qb : 0);
+  float4 v[kChainAhead];
+#pragma unroll
+  for (int s = 0; s < kChainAhead; s++) v[s] = h4[s];
+  float acc = 0;
+#pragma unroll
+  for (int s = 0; s < 2 * kChainBlocks; s++) {
+    const float4 c = v[s % kChainAhead];
+    const bool mine = s < kChainBlocks ? s < nh : s - kChainBlocks < nl;
+    chain_hold(acc);  // the loads issued so far stay above this point, the block's adds below it
+    float t = acc + c.x;
+    t += c.y;
+    t += c.z;
+    t += c.w;
+    acc = mine ? t : acc;
+    const int n = s + kChainAhead;
+    if (n < 2 * kChainBlocks) v[s % kChainAhead] = n < kChainBlocks ? h4[n] : l4[n - kChainBlocks];
+  }
+  if (b == 0 || b == kBands - 1) acc *= 2;
+  return acc;
+}
 
 __device__ __forceinline__ float interp_gain_t(const float *bandE, const BandEdges &T, int k) {
   if (k >= 400) return 0.0f;

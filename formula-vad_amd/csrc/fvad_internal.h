@@ -12,6 +12,7 @@ constexpr int kFrame = 480;
 constexpr int kWin = 960;
 constexpr int kFreq = 481;
 constexpr int kBands = 22;
+constexpr int kChainBlocks = 22;  // bins of the widest band / 4 (the last one, eband5ms 78..100): band_chain_ahead's steps per phase
 constexpr int kFeat = 42;
 constexpr int kCeps = 8;
 constexpr int kPitchBuf = 1728;  // PITCH_MAX_PERIOD + PITCH_FRAME_SIZE

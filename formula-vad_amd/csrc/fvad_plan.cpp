@@ -21,7 +21,16 @@
 namespace fvad {
 namespace {
 
-const int kEband5ms[kBands] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40, 48, 60, 78, 100};
+constexpr int kEband5ms[kBands] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40, 48, 60, 78, 100};
+
+// band_chain_ahead (fvad_device.h) walks kChainBlocks float4 blocks from every band
+// edge but the last: no band is wider, and none of those walks leaves the 400 bins
+constexpr bool chain_blocks_ok() {
+  for (int b = 0; b + 1 < kBands; b++)
+    if (kEband5ms[b + 1] - kEband5ms[b] > kChainBlocks || kEband5ms[b] + kChainBlocks > kEband5ms[kBands - 1]) return false;
+  return kEband5ms[0] == 0 && kEband5ms[kBands - 1] == 100;
+}
+static_assert(chain_blocks_ok(), "band table vs kChainBlocks");
 
 // celt kf_factor for 960 -> reversed stage list {5,192, 3,64, 4,16, 4,4, 4,1}.
 void celt_digit_reverse(int fout, int *f, int fstride, const int *factors) {

@@ -24,7 +24,8 @@ namespace fvad {
 // with its own LDS region, so a workgroup never waits at a barrier between
 // FFT stages; band terms go to the same region once the transform is done and
 // the 22 band chains run on lanes 0..21 (k_pspecw: Ep on 0..21 beside Exp on
-// 32..53).  Same arithmetic as the fused k_frame.  Frames are taken
+// 32..53; k_fftAw: a pair of frames, the second one's on 32..53).  Same
+// arithmetic as the fused k_frame.  Frames are taken
 // in batches of kWB consecutive frames per wave (dynamic, per-XCD queues as
 // take_group); k_fftAw runs each batch's serial Ly chains lane per frame.
 // ---------------------------------------------------------------------------
@@ -60,6 +61,50 @@ __device__ __forceinline__ int lane_val(int v, int l) { return __builtin_amdgcn_
 // the frames before)
 __device__ __forceinline__ void settle(int v) { asm volatile("" ::"v"(v)); }
 
+// k_fftAw's transform of frame f: window -> register FFT A -> X (HBM), the
+// frame's 240 new x_lp values, and the band-energy terms of bins 64 r + lane
+// (r < 7, bins < 400) left in registers (lo / hi of band_terms)
+__device__ __forceinline__ void fftA_frame(const StagedArgs &a, int f, const WaveTabs &tb, const wfft::Tw &tw, float2 *R,
+                                           int lane, float (&tl)[7], float (&th)[7]) {
+  float2 v[16];
+  const float *pb = frame_pb(a, f);
+  // the frame's new x_lp values n = 624..863 (pitch buffer samples
+  // 1247..1727, inside the window), 4 per lane (lanes 0..59): samples
+  // 1247 + 8 * lane .. 1255 + 8 * lane load before the transform
+  static_assert(kXlp - kXlpHist == 4 * 60 && kHist % 4 == 0, "x_lp lanes");
+  float xm = 0;
+  float4 qa = make_float4(0, 0, 0, 0), qb = qa;
+  if (lane < 60) {
+    const float *q = pb + kHist + 8 * lane;
+    xm = q[-1];
+    qa = *reinterpret_cast<const float4 *>(q);
+    qb = *reinterpret_cast<const float4 *>(q + 4);
+  }
+  WinRaw w;
+  win_load(w, pb + (kPitchBuf - kWin), lane);
+  win_apply(w, tb.hw, lane, v);
+  wfft::run(v, tw, tb.tw, R, lane);
+  float2 *X = a.X + (size_t)f * kFreq;
+#pragma unroll
+  for (int r = 0; r < 8; r++)
+    if (64 * r + lane < kFreq) X[64 * r + lane] = v[r];
+  if (lane < 60) {
+    // x_lp[n] = f(x[2n-1], x[2n], x[2n+1]), n = 624 + 4 * lane + t
+    float4 o;
+    o.x = xlp_value(xm, qa.x, qa.y);
+    o.y = xlp_value(qa.y, qa.z, qa.w);
+    o.z = xlp_value(qa.w, qb.x, qb.y);
+    o.w = xlp_value(qb.y, qb.z, qb.w);
+    *reinterpret_cast<float4 *>(frame_xlp(a, f) + kXlpHist + 4 * lane) = o;
+  }
+#pragma unroll
+  for (int r = 0; r < 7; r++) {
+    const int n = 64 * r + lane;
+    tl[r] = th[r] = 0;
+    if (n < 400) band_terms(v[r], v[r], tb.T, n, tl[r], th[r]);
+  }
+}
+
 __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftAw(StagedArgs a) {
   __shared__ __attribute__((aligned(16))) float2 Rg[kWNW][wfft::kSlots];
   __shared__ WaveTabs tb;
@@ -76,54 +121,61 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftAw(StagedArgs a) {
   const long long nb = ((long long)a.n_streams * a.V + kWB - 1) / kWB;
   for (long long g = wave_first(a, kWaveFftA, kWorkFftA, lane); g < nb; g = wave_next(a, kWaveFftA, kWorkFftA, lane, g)) {
     const int fl = batch_frames(a, g, lane);
-    for (int fr = 0; fr < kWB; fr++) {
-      const int f = lane_val(fl, fr);
-      if (f < 0) continue;
-      float2 v[16];
-      const float *pb = frame_pb(a, f);
-      // the frame's new x_lp values n = 624..863 (pitch buffer samples
-      // 1247..1727, inside the window), 4 per lane (lanes 0..59): samples
-      // 1247 + 8 * lane .. 1255 + 8 * lane load before the transform
-      static_assert(kXlp - kXlpHist == 4 * 60 && kHist % 4 == 0, "x_lp lanes");
-      float xm = 0;
-      float4 qa = make_float4(0, 0, 0, 0), qb = qa;
-      if (lane < 60) {
-        const float *q = pb + kHist + 8 * lane;
-        xm = q[-1];
-        qa = *reinterpret_cast<const float4 *>(q);
-        qb = *reinterpret_cast<const float4 *>(q + 4);
-      }
-      WinRaw w;
-      win_load(w, pb + (kPitchBuf - kWin), lane);
-      win_apply(w, tb.hw, lane, v);
-      wfft::run(v, tw, tb.tw, R, lane);
-      float2 *X = a.X + (size_t)f * kFreq;
+    // the batch's valid frames in pairs (a leftover one alone): both frames'
+    // transforms, then their band chains side by side in one pass, the first
+    // frame's on lanes 0..21 and the second's on lanes 32..53 (as k_pspecw's
+    // Ep / Exp).  The first frame's band terms wait in registers while the
+    // second transform uses the region.
+    unsigned todo = (unsigned)__builtin_amdgcn_ballot_w64(fl >= 0);  // bit fr: slot fr of the batch holds a frame
+    while (todo) {
+      const int fr0 = __builtin_ctz(todo);
+      todo &= todo - 1;
+      const int np = todo ? 2 : 1;
+      const int fr1 = todo ? __builtin_ctz(todo) : fr0;
+      todo &= todo - 1;  // (0 stays 0)
+      const int f0 = lane_val(fl, fr0), f1 = lane_val(fl, fr1);
+      float kl[7] = {}, kh[7] = {};
+#pragma unroll 1
+      for (int h = 0; h < np; h++) {
+        float tl[7], th[7];
+        fftA_frame(a, h ? f1 : f0, tb, tw, R, lane, tl, th);
+        if (h + 1 < np) {
 #pragma unroll
-      for (int r = 0; r < 8; r++)
-        if (64 * r + lane < kFreq) X[64 * r + lane] = v[r];
-      if (lane < 60) {
-        // x_lp[n] = f(x[2n-1], x[2n], x[2n+1]), n = 624 + 4 * lane + t
-        float4 o;
-        o.x = xlp_value(xm, qa.x, qa.y);
-        o.y = xlp_value(qa.y, qa.z, qa.w);
-        o.z = xlp_value(qa.w, qb.x, qb.y);
-        o.w = xlp_value(qb.y, qb.z, qb.w);
-        *reinterpret_cast<float4 *>(frame_xlp(a, f) + kXlpHist + 4 * lane) = o;
-      }
+          for (int r = 0; r < 7; r++) {
+            kl[r] = tl[r];
+            kh[r] = th[r];
+          }
+        } else {
+          // the pair's last transform is done: the region takes the terms
 #pragma unroll
-      for (int r = 0; r < 7; r++) {
-        const int n = 64 * r + lane;
-        if (n < 400) band_terms(v[r], v[r], T, n, tr[n], tr[400 + n]);
+          for (int r = 0; r < 7; r++) {
+            const int n = 64 * r + lane;
+            if (n < 400) {
+              if (h) {
+                tr[n] = kl[r];
+                tr[400 + n] = kh[r];
+              }
+              tr[800 * h + n] = tl[r];
+              tr[800 * h + 400 + n] = th[r];
+            }
+          }
+        }
       }
       wfft::wsync();
-      if (lane < kBands) {
-        const float ex = band_chain(tr, tr + 400, T, lane);
-        a.Ex[(size_t)f * kBands + lane] = ex;
-        exb[wv][fr][lane] = ex;
-        lyb[wv][fr][lane] = (float)log10(1e-2 + (double)ex);
+      const int h = lane >> 5, b = lane & 31;
+      if (b < kBands && h < np) {
+        const float ex = band_chain_ahead(tr + 800 * h, tr + 800 * h + 400, T, b);
+        a.Ex[(size_t)(h ? f1 : f0) * kBands + b] = ex;
+        exb[wv][h ? fr1 : fr0][b] = ex;
       }
       wfft::wsync();
     }
+    // Ly before its floor chain, lanes = (frame, band) over the whole batch
+    for (int idx = lane; idx < kWB * kBands; idx += 64) {
+      const int fr = idx / kBands, b = idx - fr * kBands;
+      if (__shfl(fl, fr) >= 0) lyb[wv][fr][b] = (float)log10(1e-2 + (double)exb[wv][fr][b]);
+    }
+    wfft::wsync();
     // the Ly floor chain and the silence gate, lane per frame
     if (lane < kWB) {
       const int f = fl;
