@@ -35,6 +35,7 @@
 #include "fvad_kernels.h"
 #include "fvad_lifecycle.h"
 #include "fvad_staged.h"
+#include "fvad_sweep.h"
 
 const fvad::HostModel *fvad_model_host(const fvad_model *m);
 
@@ -49,6 +50,7 @@ bool fp16_mode(int mode) { return mode == FVAD_MODE_FP16 || mode == FVAD_MODE_FP
 }  // namespace
 
 extern "C" const char *fvad_last_error(void) { return g_err.c_str(); }
+int fvad::set_error(int code, const std::string &msg) { return fail(code, msg); }
 extern "C" const char *fvad_version(void) { return "fvad-mi355x 0.1 (gfx950)"; }
 
 #define HIP_TRY(expr)                                                                     \
@@ -1688,6 +1690,62 @@ double initial_avg(size_t n, double init) {
 }
 }  // namespace
 
+void fvad::vadm_fill_const(const fvad_vadm_config &c, int sample_rate, int fft_size, VadmConst *Kp, VadmState *s0p,
+                           int *lo, int *hi) {
+  const float sr = (float)sample_rate;
+  const float eval_per_sec = sr / (float)fft_size;
+  auto len_of = [&](float sec) { return std::max<size_t>(1, (size_t)(eval_per_sec * sec)); };
+  auto freq_to_bin = [&](float f) { return (int)std::round(f / (sr / (float)fft_size)); };
+  VadmConst &K = *Kp;
+  K = VadmConst{};
+  *lo = freq_to_bin(c.speech_min_freq);
+  *hi = freq_to_bin(c.speech_max_freq);
+  K.n_lt = (int)len_of(c.long_term_speech_avg_sec);
+  K.n_st = (int)len_of(c.short_term_speech_avg_sec);
+  K.n_r = (int)len_of(c.channel_vol_ratio_avg_sec);
+  K.min_open = (unsigned long long)(size_t)(sr * c.min_consecutive_sec_to_open);
+  K.max_gap = (unsigned long long)(size_t)(sr * c.max_speech_gap_sec);
+  K.rec_pad = (unsigned long long)(sr * 2);
+  K.thr_factor = c.speech_threshold_factor;
+  K.ratio_thr = c.channel_vol_ratio_threshold;
+  K.min_dur = c.min_vad_duration_sec;
+  K.sr = sr;
+  K.has_init = c.has_initial_long_term_avg != 0;
+  K.init = c.initial_long_term_avg;
+  VadmState s0{};
+  if (K.has_init) {
+    // RollingAverage(initial_avg): data = init (a double, VADMachine.zig:89-94)
+    s0.lt_count = (unsigned)K.n_lt;
+    s0.lt_last = initial_avg((size_t)K.n_lt, K.init);
+    s0.lt_has = 1;
+    s0.lt_pre_ok = 1;  // next write is at 0: the next pass starts from 0.0
+    s0.lt_pre = 0.0;
+  }
+  *s0p = s0;
+}
+
+void fvad::vadm_snapshot_of(const VadmState &st, fvad_vadm_snapshot *out) {
+  std::memset(out, 0, sizeof(*out));
+  out->speech_state = st.state;
+  out->speech_start = st.speech_start;
+  out->speech_end = st.speech_end;
+  out->windows = st.windows_done;
+  out->avg[0] = st.lt_last;
+  out->avg[1] = st.st_last;
+  out->avg[2] = st.r_last;
+  out->write_idx[0] = st.lt_widx;
+  out->write_idx[1] = st.st_widx;
+  out->write_idx[2] = st.r_widx;
+  out->written[0] = st.lt_count;
+  out->written[1] = st.st_count;
+  out->written[2] = st.r_count;
+  out->speech_rnn_vad = st.rnn_vad;
+  out->speech_vol_ratio = st.vol_ratio;
+  out->speech_rnn_vad_count = st.rnn_vad_count;
+  out->speech_vol_ratio_count = st.vol_ratio_count;
+  out->n_segments = st.n_segs;
+}
+
 int vadm_reset(fvad_engine *e) {
   std::vector<fvad::VadmState> st = e->vadm_init;
   if (!e->dbg_lt_full) {
@@ -1718,10 +1776,6 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   if (e->vadm.n > 0) return fail(FVAD_EINVAL, "VADMachines already attached");
   HIP_TRY(hipSetDevice(e->cfg.device));
   const int B = e->cfg.n_streams;
-  const float sr = (float)e->cfg.sample_rate;
-  const float eval_per_sec = sr / (float)e->cfg.fft_size;
-  auto len_of = [&](float sec) { return std::max<size_t>(1, (size_t)(eval_per_sec * sec)); };
-  auto freq_to_bin = [&](float f) { return (int)std::round(f / (sr / (float)e->cfg.fft_size)); };
   fvad::VadmArgs v{};
   v.n = n;
   v.seg_cap = seg_capacity;
@@ -1730,16 +1784,14 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   long long off = 0;
   std::vector<fvad::VadmState> init((size_t)n * B);
   for (int m = 0; m < n; m++) {
-    const fvad_vadm_config &c = cfgs[m];
     fvad::VadmConst &K = v.c[m];
-    const int lo = freq_to_bin(c.speech_min_freq), hi = freq_to_bin(c.speech_max_freq);
+    fvad::VadmState s0;
+    int lo, hi;
+    fvad::vadm_fill_const(cfgs[m], e->cfg.sample_rate, e->cfg.fft_size, &K, &s0, &lo, &hi);
     K.slot = -1;
     for (int b = 0; b < e->cfg.n_bands; b++)
       if (e->cfg.band_lo[b] == lo && e->cfg.band_hi[b] == hi) K.slot = b;
     if (K.slot < 0) return fail(FVAD_EINVAL, "no engine band matches the machine's speech band");
-    K.n_lt = (int)len_of(c.long_term_speech_avg_sec);
-    K.n_st = (int)len_of(c.short_term_speech_avg_sec);
-    K.n_r = (int)len_of(c.channel_vol_ratio_avg_sec);
     K.lt_pitch = (K.n_lt + 3) & ~3;  // 16-byte rows
     off = (off + 3) & ~3LL;
     K.lt_off = off;
@@ -1748,24 +1800,6 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
     off += (long long)K.n_st * B;
     K.r_off = off;
     off += (long long)K.n_r * B;
-    K.min_open = (unsigned long long)(size_t)(sr * c.min_consecutive_sec_to_open);
-    K.max_gap = (unsigned long long)(size_t)(sr * c.max_speech_gap_sec);
-    K.rec_pad = (unsigned long long)(sr * 2);
-    K.thr_factor = c.speech_threshold_factor;
-    K.ratio_thr = c.channel_vol_ratio_threshold;
-    K.min_dur = c.min_vad_duration_sec;
-    K.sr = sr;
-    K.has_init = c.has_initial_long_term_avg != 0;
-    K.init = c.initial_long_term_avg;
-    fvad::VadmState s0{};
-    if (K.has_init) {
-      // RollingAverage(initial_avg): data = init (a double, VADMachine.zig:89-94)
-      s0.lt_count = (unsigned)K.n_lt;
-      s0.lt_last = initial_avg((size_t)K.n_lt, K.init);
-      s0.lt_has = 1;
-      s0.lt_pre_ok = 1;  // next write is at 0: the next pass starts from 0.0
-      s0.lt_pre = 0.0;
-    }
     for (int s = 0; s < B; s++) init[(size_t)m * B + s] = s0;
   }
   int rc;
@@ -1975,25 +2009,7 @@ extern "C" int fvad_engine_vadm_snapshot(fvad_engine *e, int stream, int machine
   if (!out) return fail(FVAD_EINVAL, "null argument");
   fvad::VadmState st;
   if (const int rc = vadm_read_state(e, stream, machine, &st)) return rc;
-  std::memset(out, 0, sizeof(*out));
-  out->speech_state = st.state;
-  out->speech_start = st.speech_start;
-  out->speech_end = st.speech_end;
-  out->windows = st.windows_done;
-  out->avg[0] = st.lt_last;
-  out->avg[1] = st.st_last;
-  out->avg[2] = st.r_last;
-  out->write_idx[0] = st.lt_widx;
-  out->write_idx[1] = st.st_widx;
-  out->write_idx[2] = st.r_widx;
-  out->written[0] = st.lt_count;
-  out->written[1] = st.st_count;
-  out->written[2] = st.r_count;
-  out->speech_rnn_vad = st.rnn_vad;
-  out->speech_vol_ratio = st.vol_ratio;
-  out->speech_rnn_vad_count = st.rnn_vad_count;
-  out->speech_vol_ratio_count = st.vol_ratio_count;
-  out->n_segments = st.n_segs;
+  fvad::vadm_snapshot_of(st, out);
   return FVAD_OK;
 }
 

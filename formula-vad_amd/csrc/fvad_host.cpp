@@ -19,6 +19,7 @@
 
 #include "../../include/fvad.h"
 #include "fvad_internal.h"
+#include "fvad_sweep.h"
 
 namespace {
 
@@ -209,6 +210,36 @@ extern "C" void fvad_vadm_config_default(fvad_vadm_config *c) {
   c->min_consecutive_sec_to_open = 0.2f;
   c->max_speech_gap_sec = 2;
   c->min_vad_duration_sec = 0.7f;
+}
+
+// The sweep's host path (fvad_sweep.cpp): one fresh machine over a recorded
+// window sequence, its final state in the device snapshot's terms.
+void fvad::host_vadm_lane(const fvad_vadm_config &c, int sample_rate, int fft_size, int n_channels, int n_bands,
+                          int slot, size_t n_windows, const float *band, const float *vad, const float *vol_ratio,
+                          fvad_vadm_snapshot *snap, std::vector<fvad_segment> *segs) {
+  VADMachine m(c, sample_rate, fft_size);
+  for (size_t w = 0; w < n_windows; w++)
+    m.run((uint64_t)w * (uint64_t)fft_size, band + w * (size_t)n_channels * n_bands + slot, n_channels, n_bands,
+          vad[w], vol_ratio[w]);
+  if (snap) {
+    std::memset(snap, 0, sizeof(*snap));
+    snap->speech_state = (int)m.state;
+    snap->speech_start = m.speech_start;
+    snap->speech_end = m.speech_end;
+    snap->windows = n_windows;
+    const RollingAverage *ra[3] = {&m.long_term, &m.short_term, &m.ratio};
+    for (int k = 0; k < 3; k++) {
+      snap->avg[k] = ra[k]->last_avg;
+      snap->write_idx[k] = ra[k]->write_idx;
+      snap->written[k] = ra[k]->written_count;
+    }
+    snap->speech_rnn_vad = m.rnn_vad;
+    snap->speech_vol_ratio = m.vol_ratio;
+    snap->speech_rnn_vad_count = m.rnn_vad_count;
+    snap->speech_vol_ratio_count = m.vol_ratio_count;
+    snap->n_segments = m.segments.size();
+  }
+  if (segs) *segs = std::move(m.segments);
 }
 
 // ---------------------------------------------------------------------------

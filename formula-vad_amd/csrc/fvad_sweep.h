@@ -1,0 +1,60 @@
+// Config sweep (include/fvad.h: fvad_sweep_*): many VADMachine configs over
+// recorded window sequences.  The kernel side (fvad_sweep.hip), the host
+// pieces it shares with the engine's device machines (fvad_engine.cpp) and
+// with the host VADMachine (fvad_host.cpp).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "../../include/fvad.h"
+#include "fvad_staged.h"
+
+namespace fvad {
+
+// fvad_last_error()'s message; returns code (fvad_engine.cpp)
+int set_error(int code, const std::string &msg);
+
+// A config's device constants and a freshly constructed machine's state
+// (VADMachine.zig:75-100): RollingAverage lengths, thresholds in samples, the
+// initial long-term average folded as RollingAverage.init does.  The buffer
+// offsets (lt_off, st_off, r_off, lt_pitch) and the band slot are the
+// caller's.  *lo / *hi: the speech band as FFT-B bins (FFT.freqToBin).
+// One piece of code for fvad_engine_attach_vadm and the sweep.
+void vadm_fill_const(const fvad_vadm_config &c, int sample_rate, int fft_size, VadmConst *K, VadmState *s0, int *lo,
+                     int *hi);
+// VadmState in the reference's terms (fvad_engine_vadm_snapshot, fvad_sweep_snapshot)
+void vadm_snapshot_of(const VadmState &st, fvad_vadm_snapshot *out);
+
+// The host VADMachine (fvad_host.cpp) over one window sequence from a fresh
+// machine: band [n_windows][n_channels][n_bands], the machine reads slot
+// `slot`; vad / vol_ratio [n_windows]; window w enters with index w * fft_size.
+void host_vadm_lane(const fvad_vadm_config &c, int sample_rate, int fft_size, int n_channels, int n_bands, int slot,
+                    size_t n_windows, const float *band, const float *vad, const float *vol_ratio,
+                    fvad_vadm_snapshot *snap, std::vector<fvad_segment> *segs);
+
+// k_sweep_min + k_vadm_sweep's arguments.  A lane is (stream s, config c of
+// the chunk): lane index s * n_cfgs + c.
+struct SweepArgs {
+  int n_streams, n_cfgs;         // configs of this chunk
+  int n_channels, n_bands, seg_cap;
+  const VadmConst *K;            // [n_cfgs] device; lt_off / lt_pitch: the config's rows [stream][lt_pitch] in lt
+  VadmState *st;                 // [lane]
+  float *lt;                     // long-term rows, contiguous per lane, 16-byte aligned
+  float *sbuf, *rbuf;            // short-term and ratio entries [entry][lane]
+  VadmSeg *seg;                  // [lane][seg_cap]
+  const long long *win_off;      // [n_streams] first window of stream s in the arrays below
+  const int *n_win;              // [n_streams]
+  const float *band;             // [window][channel][band]
+  float *wmin;                   // [window][band]  min over channels (k_sweep_min)
+  const float *wvad, *wvr;       // [window]
+  long long n_windows;           // all streams'
+  unsigned long long fft;
+  double bound_scale;            // test hooks, as VadmArgs'
+  unsigned defer_max;
+  unsigned long long *count;     // null, or [kVadmCounts]
+};
+constexpr int kSweepBlock = 64;  // windows per walk: a lane re-decides lazy / non-lazy and may settle an owed fold
+hipError_t launch_sweep_min(const SweepArgs &a, hipStream_t stream);
+hipError_t launch_vadm_sweep(const SweepArgs &a, hipStream_t stream);
+
+}  // namespace fvad

@@ -7,6 +7,8 @@ Mirrors the reference's API surface for this path:
   * AudioPipeline   (src/AudioPipeline.zig pushSamples + VAD + VADMachine)
   * Multi           multi-stream simulator core (simulator.zig runAll)
   * evaluate/aggregate/parse_audacity (src/Evaluator/*)
+  * Sweep           many VADMachine configs over recorded windows (fvad_sweep_*;
+                    VAD.zig:375-380's alt_vad_machine_configs as a tuning loop)
 
 All compute goes through the HIP kernels in libfvad.so; there is no CPU
 fallback — operations raise FvadError when the library or the GPU is missing.
@@ -160,6 +162,16 @@ class AggregateStats(C.Structure):
                 ("f_score", C.c_float), ("f_score_beta", C.c_float)]
 
 
+class SweepConfig(C.Structure):
+    """fvad_sweep_config (include/fvad.h)."""
+    _fields_ = [("n_streams", C.c_int), ("n_channels", C.c_int), ("sample_rate", C.c_int), ("fft_size", C.c_int),
+                ("n_bands", C.c_int), ("band_lo", C.c_int * MAX_BANDS), ("band_hi", C.c_int * MAX_BANDS),
+                ("use_denoiser", C.c_int), ("seg_capacity", C.c_int), ("device", C.c_int)]
+
+
+SWEEP_DEBUG_BOUND_SCALE, SWEEP_DEBUG_DEFER_MAX, SWEEP_DEBUG_CHUNK, SWEEP_DEBUG_COUNT = 1, 2, 3, 4
+
+
 class KissCpx(C.Structure):
     _fields_ = [("r", C.c_float), ("i", C.c_float)]
 
@@ -252,6 +264,20 @@ SYMBOLS = [
     ("fvad_eval_stats", C.c_int, [F32P, C.c_size_t, F32P, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("fvad_eval_aggregate", None, [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("fvad_parse_audacity", C.c_long, [C.c_char_p, C.c_size_t, F32P, C.c_size_t]),
+    ("fvad_sweep_create", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fvad_sweep_destroy", None, [C.c_void_p]),
+    ("fvad_sweep_set_windows", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, F32P, F32P, F32P]),
+    ("fvad_sweep_append_outputs", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, I32P]),
+    ("fvad_sweep_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("fvad_sweep_run_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("fvad_sweep_segments", C.c_size_t, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]),
+    ("fvad_sweep_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("fvad_sweep_snapshot", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    ("fvad_sweep_score", C.c_int, [C.c_void_p, C.POINTER(F32P), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    ("fvad_sweep_bytes", C.c_size_t, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("fvad_sweep_set_debug", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("fvad_sweep_debug_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("fvad_synth_stream", C.c_long, [C.c_uint32, C.c_size_t, C.c_int, F32P, F32P, C.c_size_t]),
     ("fvad_synth_ticks", C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F32P]),
     ("fvad_synth_cache_clear", None, []),
@@ -964,6 +990,119 @@ def aggregate(stats_list):
     out = AggregateStats()
     lib().fvad_eval_aggregate(arr, len(stats_list), C.byref(out))
     return out
+
+
+class Sweep:
+    """Many VADMachine configs over recorded window sequences (fvad_sweep_*):
+    one GPU lane per (stream, config), or the host VADMachine with device=-1."""
+
+    def __init__(self, n_streams, n_channels=2, device=0, fft_size=2048, bands=((4, 64),), use_denoiser=True,
+                 seg_capacity=256, sample_rate=48000):
+        cfg = SweepConfig()
+        cfg.n_streams, cfg.n_channels, cfg.sample_rate, cfg.fft_size = n_streams, n_channels, sample_rate, fft_size
+        cfg.n_bands = len(bands)
+        for i, (lo, hi) in enumerate(bands[:MAX_BANDS]):
+            cfg.band_lo[i] = lo
+            cfg.band_hi[i] = hi
+        cfg.use_denoiser, cfg.seg_capacity, cfg.device = int(use_denoiser), seg_capacity, device
+        self.cfg = cfg
+        self.h = None
+        h = C.c_void_p()
+        _check(lib().fvad_sweep_create(C.byref(cfg), C.byref(h)), "fvad_sweep_create")
+        self.h = h
+        self.B, self.C, self.nb, self.n_cfgs = n_streams, n_channels, len(bands), 0
+
+    @staticmethod
+    def _cfgs(cfgs):
+        cfgs = list(cfgs)
+        return (VadmConfig * max(1, len(cfgs)))(*cfgs), len(cfgs)
+
+    def set_windows(self, stream, band, vol_ratio, vad=None):
+        """band [windows][channels][bands], vol_ratio [windows], vad [windows] or None (0)."""
+        r = np.ascontiguousarray(vol_ratio, np.float32).reshape(-1)
+        b = np.ascontiguousarray(band, np.float32).reshape(len(r), self.C, self.nb)
+        v = np.ascontiguousarray(vad, np.float32).reshape(len(r)) if vad is not None else None
+        _check(lib().fvad_sweep_set_windows(self.h, stream, len(r), fptr(b), fptr(v) if v is not None else None,
+                                            fptr(r)), "fvad_sweep_set_windows")
+
+    def append_outputs(self, out, ticks_valid=None):
+        """The completed windows of one push (Engine.push's dict) appended to every stream."""
+        T = out["win_flag"].shape[0]
+        a = {k: np.ascontiguousarray(out[k], np.int32 if k == "win_flag" else np.float32)
+             for k in ("win_flag", "win_ratio", "win_vad", "band")}
+        s = Outputs(None, None, a["win_flag"].ctypes.data_as(I32P), fptr(a["win_ratio"]), fptr(a["win_vad"]),
+                    fptr(a["band"]), None)
+        tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
+        _check(lib().fvad_sweep_append_outputs(self.h, C.byref(s), T, tv.ctypes.data_as(I32P) if tv is not None
+                                               else None), "fvad_sweep_append_outputs")
+
+    def run(self, cfgs):
+        arr, n = self._cfgs(cfgs)
+        _check(lib().fvad_sweep_run(self.h, arr, n), "fvad_sweep_run")
+        self.n_cfgs = n
+
+    def run_host(self, cfgs):
+        arr, n = self._cfgs(cfgs)
+        _check(lib().fvad_sweep_run_host(self.h, arr, n), "fvad_sweep_run_host")
+        self.n_cfgs = n
+
+    def segments(self, stream, cfg):
+        """(total, the first min(total, seg_capacity) segments as tuples)."""
+        n = lib().fvad_sweep_segments(self.h, stream, cfg, None, 0)
+        k = min(n, self.cfg.seg_capacity)
+        buf = (Segment * max(1, k))()
+        lib().fvad_sweep_segments(self.h, stream, cfg, buf, k)
+        return n, [(s.sample_from, s.sample_to, s.debug_rnn_vad, s.debug_avg_speech_vol_ratio) for s in buf[:k]]
+
+    def counts(self):
+        """Segment totals [stream][cfg]."""
+        out = np.zeros((self.B, self.n_cfgs), np.uint64)
+        _check(lib().fvad_sweep_counts(self.h, out.ctypes.data_as(C.c_void_p), out.size), "fvad_sweep_counts")
+        return out
+
+    def snapshot(self, stream, cfg):
+        s = VadmSnapshot()
+        _check(lib().fvad_sweep_snapshot(self.h, stream, cfg, C.byref(s)), "fvad_sweep_snapshot")
+        return s.as_dict()
+
+    def score(self, refs, ignore_shorter_than_sec=0.0, extrude_start=0.0, extrude_end=0.0, fill_gaps=0.0,
+              single=False):
+        """refs: per stream a list of (from_sec, to_sec).  Returns the AggregateStats
+        per config (and with single=True the per-stream stats dicts [cfg][stream])."""
+        arrs = [np.ascontiguousarray(np.asarray(r, np.float32).reshape(-1, 2)) for r in refs]
+        assert len(arrs) == self.B, "one reference list per stream"
+        ptrs = (F32P * self.B)(*[fptr(a) for a in arrs])
+        lens = (C.c_size_t * self.B)(*[len(a) for a in arrs])
+        sc = StatConfig(ignore_shorter_than_sec, extrude_start, extrude_end, fill_gaps)
+        agg = (AggregateStats * max(1, self.n_cfgs))()
+        one = (SingleStats * max(1, self.n_cfgs * self.B))() if single else None
+        _check(lib().fvad_sweep_score(self.h, ptrs, lens, C.byref(sc), agg, one), "fvad_sweep_score")
+        if not single:
+            return list(agg[:self.n_cfgs])
+        return list(agg[:self.n_cfgs]), [[{n: getattr(one[m * self.B + s], n) for n in _STAT_FIELDS}
+                                          for s in range(self.B)] for m in range(self.n_cfgs)]
+
+    def bytes(self, cfgs):
+        """Device bytes the machines of these configs need in one chunk (fvad_sweep_bytes)."""
+        arr, n = self._cfgs(cfgs)
+        return lib().fvad_sweep_bytes(C.byref(self.cfg), arr, n)
+
+    def set_debug(self, key, value):
+        """Test hooks: SWEEP_DEBUG_BOUND_SCALE, SWEEP_DEBUG_DEFER_MAX, SWEEP_DEBUG_CHUNK, SWEEP_DEBUG_COUNT."""
+        _check(lib().fvad_sweep_set_debug(self.h, key, value), "fvad_sweep_set_debug")
+
+    def debug_counts(self):
+        out = np.zeros(4, np.uint64)
+        n = lib().fvad_sweep_debug_counts(self.h, out.ctypes.data_as(C.c_void_p), 4)
+        _check(n if n < 0 else 0, "fvad_sweep_debug_counts")
+        return dict(zip(("exact", "settled", "open", "end_fold"), (int(v) for v in out[:n])))
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().fvad_sweep_destroy(self.h)
+        except Exception:
+            pass
 
 
 def parse_audacity(txt):

@@ -618,6 +618,85 @@ void fvad_eval_aggregate(const fvad_single_stats *stats, size_t n, fvad_aggregat
 /* formats.parseAudacitySegments (formats.zig:7-36): returns count or <0 */
 long fvad_parse_audacity(const char *txt, size_t len, float *from_to, size_t cap);
 
+/* Config sweep: many VADMachine configs over recorded window sequences (the
+ * tuning loop of VAD.zig:375-380's alt_vad_machine_configs).  A VADMachine
+ * sees nothing of the audio but a completed window's band sums, vad and volume
+ * ratio, so a sweep records each stream's windows once -- from any engine's
+ * pushes, or set directly -- and runs any number of configs over them: one
+ * GPU lane per (stream, config) (k_vadm_sweep, the engine's device machine
+ * over the whole sequence), each from a freshly constructed machine, bit for
+ * bit the host VADMachine's segments and state.  Independent of any engine. */
+typedef struct {
+  int n_streams;
+  int n_channels;              /* 1..FVAD_MAX_CHANNELS */
+  int sample_rate;             /* 48000 (FVAD_ERATE otherwise) */
+  int fft_size;                /* even, 2..4194304: a window is fft_size samples */
+  int n_bands;                 /* 1..FVAD_MAX_BANDS bands per recorded window, as the engine's */
+  int band_lo[FVAD_MAX_BANDS];
+  int band_hi[FVAD_MAX_BANDS];
+  int use_denoiser;            /* 0: every window's vad enters the machines as 0 (VADMachine.zig:240-246) */
+  int seg_capacity;            /* >= 1: segments kept per (stream, config) */
+  int device;                  /* HIP device, or -1: a host-only sweep (needs no GPU; run = run_host) */
+} fvad_sweep_config;
+typedef struct fvad_sweep fvad_sweep;
+int fvad_sweep_create(const fvad_sweep_config *cfg, fvad_sweep **out);
+void fvad_sweep_destroy(fvad_sweep *sw);
+/* A stream's whole window sequence, in order: band [n_windows][n_channels]
+ * [n_bands] (one window slot of fvad_outputs.band each), vad [n_windows]
+ * (nullable: 0), vol_ratio [n_windows].  Replaces what the stream held; a
+ * stream never set has 0 windows.  Window w enters every machine with sample
+ * index w * fft_size. */
+int fvad_sweep_set_windows(fvad_sweep *sw, int stream, size_t n_windows, const float *band, const float *vad,
+                           const float *vol_ratio);
+/* Appends the completed windows of one push's outputs (win_flag, win_ratio,
+ * win_vad, band: all required; the layout of an engine with the sweep's
+ * streams, channels, bands and fft_size) to every stream: ticks in order, then
+ * a tick's slots w < win_flag; stream s only its first ticks_valid[s] ticks
+ * (nullable: all).  Host code: any engine mode's pushes can fill a sweep. */
+int fvad_sweep_append_outputs(fvad_sweep *sw, const fvad_outputs *out, int n_ticks, const int32_t *ticks_valid);
+/* Runs every config over every stream, each from a freshly constructed machine
+ * (fvad_engine_attach_vadm's initial state), replacing the previous run's
+ * results.  Each config's speech band (FFT.freqToBin of speech_min/max_freq at
+ * fft_size) must be one of the sweep's bands: FVAD_EINVAL naming the config
+ * otherwise, with nothing run.  On a device sweep the configs run on the GPU,
+ * in chunks when their buffers exceed the budget (results do not depend on the
+ * chunking); fvad_sweep_run_host runs the host VADMachine instead (always, on
+ * a host-only sweep). */
+int fvad_sweep_run(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs);
+int fvad_sweep_run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs);
+/* total segments of (stream, config) in the last run; copies min(total, seg_capacity, cap) */
+size_t fvad_sweep_segments(const fvad_sweep *sw, int stream, size_t cfg, fvad_segment *out, size_t cap);
+/* every total, out[stream * n_cfgs + cfg] */
+int fvad_sweep_counts(const fvad_sweep *sw, uint64_t *out, size_t cap);
+/* the machine's final state (every owed long-term fold resolved: avg[0] is the reference's bits) */
+int fvad_sweep_snapshot(const fvad_sweep *sw, int stream, size_t cfg, fvad_vadm_snapshot *out);
+/* Scores of the last run: per config, fvad_eval_stats per stream on its
+ * segments as (float)sample / 48000.0f seconds against ref_from_to[stream]
+ * (n_ref[stream] (from, to) pairs), then fvad_eval_aggregate over the streams
+ * into agg_out[cfg]; single_out (nullable) [cfg][stream].  A lane that
+ * overflowed seg_capacity would be scored from a truncated list:
+ * FVAD_EINVAL naming it. */
+int fvad_sweep_score(const fvad_sweep *sw, const float *const *ref_from_to, const size_t *n_ref,
+                     const fvad_stat_config *stat_cfg, fvad_aggregate_stats *agg_out, fvad_single_stats *single_out);
+/* Device memory the machines of a run need when all configs run in one chunk
+ * (buffers, states, segments, constants; the recorded windows come on top:
+ * (n_channels * n_bands + n_bands + 2) floats each); 0 on invalid arguments. */
+size_t fvad_sweep_bytes(const fvad_sweep_config *cfg, const fvad_vadm_config *cfgs, size_t n_cfgs);
+/* Test hooks (results are identical for every setting), for the next runs:
+ *   FVAD_SWEEP_DEBUG_BOUND_SCALE  the lazy long-term test's bound times value (-1: infinite, 0: default)
+ *   FVAD_SWEEP_DEBUG_DEFER_MAX    settle an owed fold once value long pushes are owed (0: default)
+ *   FVAD_SWEEP_DEBUG_CHUNK        configs per chunk (0: by the memory budget)
+ *   FVAD_SWEEP_DEBUG_COUNT        value != 0: count how long-term tests were decided (device sweeps)
+ * fvad_sweep_debug_counts: the last run's counters -- decided from an exact
+ * average, settled from the estimate, left open by the bound (folded), folds at
+ * a block's or the stream's end; returns how many were written (< 0: error). */
+#define FVAD_SWEEP_DEBUG_BOUND_SCALE 1
+#define FVAD_SWEEP_DEBUG_DEFER_MAX 2
+#define FVAD_SWEEP_DEBUG_CHUNK 3
+#define FVAD_SWEEP_DEBUG_COUNT 4
+int fvad_sweep_set_debug(fvad_sweep *sw, int key, int value);
+int fvad_sweep_debug_counts(const fvad_sweep *sw, unsigned long long *out, int n);
+
 /* Synthetic 48 kHz onboard audio; returns label count */
 long fvad_synth_stream(uint32_t stream_id, size_t n, int n_channels, float *out, float *labels,
                        size_t label_cap);
