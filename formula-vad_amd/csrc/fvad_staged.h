@@ -13,6 +13,26 @@ constexpr int kStagedKernels = 11;
 constexpr int kWorkCounters = 64;  // persistent-kernel queues (fvad_staged.hip: take_group)
 constexpr int kPitchRecord = 80;  // floats per frame of the pitch record (k_pcorr -> k_select)
 
+// The wave-per-frame kernels take frames in batches of kWB consecutive frame
+// indices per wave (fvad_wave.hip).  k_synthw overlap-adds inside a batch, so
+// the batch size also fixes the layout of a ys row [f][960]:
+//   [0, 480)    head, always written: first half of frame f's windowed
+//               synthesis, plus the second half of frame f - 1 when f is not
+//               a seam
+//   [480, 960)  tail (second half), written only where no wave adds it to
+//               the next frame: ys_tail_kept
+// Frame f = s * V + v is a seam when its predecessor is not the frame its
+// wave ran just before it: the stream's first frame of the push (its previous
+// half is the state's synthesis memory) or the first slot of a batch (the
+// tail of row f - 1).  A stream's valid frames are a prefix of its V, so
+// f - 1 is valid whenever f is and v > 0.
+constexpr int kWB = 8;
+__host__ __device__ constexpr bool ys_seam(long long f, int v) { return v == 0 || f % kWB == 0; }
+// n_valid: the stream's valid frames of the push (ticks * channels)
+__host__ __device__ constexpr bool ys_tail_kept(long long f, int v, int n_valid) {
+  return f % kWB == kWB - 1 || v + 1 == n_valid;
+}
+
 // Pitch tile buffer (k_plpc -> k_pcorr): a tile is 64 streams at one frame
 // position; each quarter (16 streams) is one contiguous block of kRows rows of
 // 16 floats (the yy_lookup region is laid out frame-major instead).  xf (x_lp

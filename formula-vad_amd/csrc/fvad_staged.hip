@@ -1398,7 +1398,8 @@ __global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) { rnn3_body<false>
 __global__ void __launch_bounds__(kR3NT) k_rnn3f(StagedArgs a) { rnn3_body<true>(a); }
 
 // ---------------------------------------------------------------------------
-// k_ola: out = x[0..479] + synthesis_mem; denoised * 1/32767; re-block ring;
+// k_ola: out = x[0..479] + synthesis_mem (at the seams k_synthw leaves, done
+// in its registers elsewhere); denoised * 1/32767; re-block ring;
 // per-tick vad_low (min over channels in channel order).  Two frames per
 // 256-thread workgroup, a float4 of samples per thread (32-bit frame
 // arithmetic; the ring position of a frame is reduced once per thread).
@@ -1415,10 +1416,14 @@ __global__ void __launch_bounds__(256) k_ola(StagedArgs a) {
   const int t = v / C, c = v - t * C, i = 4 * q;
   const float *stp = a.state + (size_t)s * st::kWords;
   const size_t f = (size_t)s * V + v;
-  const float4 prev = (v == 0) ? *reinterpret_cast<const float4 *>(stp + st::kSyn + i)
-                               : *reinterpret_cast<const float4 *>(a.ys + (f - 1) * kWin + kFrame + i);
-  const float4 cur = *reinterpret_cast<const float4 *>(a.ys + f * kWin + i);
-  float4 o = make_float4(cur.x + prev.x, cur.y + prev.y, cur.z + prev.z, cur.w + prev.w);
+  // k_synthw has added the previous half already except at a seam (ys rows,
+  // fvad_staged.h); adding a zero elsewhere would turn a -0 into +0
+  float4 o = *reinterpret_cast<const float4 *>(a.ys + f * kWin + i);
+  if (ys_seam((long long)f, v)) {
+    const float4 prev = (v == 0) ? *reinterpret_cast<const float4 *>(stp + st::kSyn + i)
+                                 : *reinterpret_cast<const float4 *>(a.ys + (f - 1) * kWin + kFrame + i);
+    o = make_float4(o.x + prev.x, o.y + prev.y, o.z + prev.z, o.w + prev.w);
+  }
   if (!a.raw_s16) {
     const float k = 1.0f / (float)32767;
     o = make_float4(o.x * k, o.y * k, o.z * k, o.w * k);
@@ -1515,7 +1520,8 @@ __global__ void __launch_bounds__(64) k_winmeta(StagedArgs a) {
     for (; j < a.wmax; j++) wt[j] = -1;
   }
   // synthesis_mem for the next launch = second half of the last frame's
-  // window; each lane's float4 loads go out before its stores (a store
+  // window (a tail ys_tail_kept keeps in the ys row); each lane's float4
+  // loads go out before its stores (a store
   // between them would make every load wait for the one before)
   // (4 streams per pass: lane = float4 q and q + 64 of each stream's 120)
   constexpr int kSynQ = kFrame / 4, kSynS = 4;

@@ -29,7 +29,7 @@ namespace fvad {
 // in batches of kWB consecutive frames per wave (dynamic, per-XCD queues as
 // take_group); k_fftAw runs each batch's serial Ly chains lane per frame.
 // ---------------------------------------------------------------------------
-constexpr int kWB = 8;   // frames per wave batch
+// (kWB frames per wave batch: fvad_staged.h, with the ys row layout it fixes)
 constexpr int kWNW = 4;  // waves per workgroup
 constexpr int kWOcc = 3;  // waves per SIMD (<= 168 VGPRs; 3 workgroups per CU at <= 53 KB LDS)
 
@@ -249,7 +249,16 @@ __global__ void __launch_bounds__(64 * kPNW, 4) k_pspecw(StagedArgs a) {
 // k_synthw: kSNW waves per workgroup sharing one copy of the tables (band
 // edges without the DCT, twiddles, window): 2 workgroups = 16 waves per CU,
 // 4 per SIMD, within 160 KB of LDS and 128 VGPRs (the other wave kernels hold
-// 3 per SIMD: their VGPRs exceed 128)
+// 3 per SIMD: their VGPRs exceed 128).
+// Overlap-add inside a batch (ys rows: fvad_staged.h): a frame's windowed
+// second half stays in registers (cq) and is added to the next frame's first
+// half before that is stored, so it reaches HBM only where the next frame is
+// another wave's or another push's.  Output sample n' = 64 r' + lane' of the
+// first half (n' = 0, 481..959; row index 960 - n') pairs with n = n' - 480 of
+// the frame before (n' = 0 with n = 480), which that frame holds on lane
+// lane' ^ 32, in register r' - 8 (lane' < 32) or r' - 7: the carry moves
+// across the wave halves once, when it is made, to the lanes that add it:
+// cq[j] of lane' pairs with register 7 + j, and lane 0's cq[0] with n' = 0.
 constexpr int kSNW = 8;
 constexpr int kSOcc = 4;  // waves per SIMD
 struct SynthTabs {
@@ -273,16 +282,33 @@ __global__ void __launch_bounds__(64 * kSNW, kSOcc) k_synthw(StagedArgs a) {
   float *tr = reinterpret_cast<float *>(R);
   float *rr = bp[wv][0], *nrm = bp[wv][1], *gsm = bp[wv][2];
   const long long nb = ((long long)a.n_streams * a.V + kWB - 1) / kWB;
-  for (long long g = wave_first<kSNW>(a, kWaveSynth, kWorkSynth, lane); g < nb;
-       g = wave_next<kSNW>(a, kWaveSynth, kWorkSynth, lane, g)) {
-    // the batch's frames and silence flags, lane per frame
-    const int fl = batch_frames(a, g, lane);
-    const int sl = fl >= 0 ? a.silence[fl] : 0;
+  // (frame indices are ints, so batch indices are: one register across the
+  // transform instead of two)
+  for (int g = (int)min(wave_first<kSNW>(a, kWaveSynth, kWorkSynth, lane), nb); g < nb;
+       g = (int)min(wave_next<kSNW>(a, kWaveSynth, kWorkSynth, lane, g), nb)) {
+    // the batch's frames (as frame_of) and their flags, lane per frame:
+    // silence (1), the frame before is the slot before (2), the tail goes to
+    // HBM (4)
+    int fl = -1, sl = 0;
+    if (lane < kWB) {
+      const long long fq = (long long)g * kWB + lane;
+      if (fq < (long long)a.n_streams * a.V) {
+        const int s = (int)(fq / a.V), vq = (int)(fq - (long long)s * a.V), nv = ticks_of(a, s) * a.n_channels;
+        if (vq < nv) {
+          fl = (int)fq;
+          sl = (a.silence[fq] ? 1 : 0) | (ys_seam(fq, vq) ? 0 : 2) | (ys_tail_kept(fq, vq, nv) ? 4 : 0);
+        }
+      }
+    }
     settle(sl);
+    float cq[8];  // the windowed second half of the frame before, on the lanes that add it
+#pragma unroll
+    for (int j = 0; j < 8; j++) cq[j] = 0;
     for (int fr = 0; fr < kWB; fr++) {
       const int f = lane_val(fl, fr);
       if (f < 0) continue;
-      const bool fil = !lane_val(sl, fr);  // silent frames: X passes through
+      const int fg = lane_val(sl, fr);
+      const bool fil = !(fg & 1);  // silent frames: X passes through
       // every input of the frame in one batch of loads (each later load
       // would also wait for the stores still in flight)
       const float2 *X = a.X + (size_t)f * kFreq;
@@ -366,12 +392,38 @@ __global__ void __launch_bounds__(64 * kSNW, kSOcc) k_synthw(StagedArgs a) {
       wfft::wsync();
       wfft::run(v, tw, tb.tw, R, lane);
       float *y = a.ys + (size_t)f * kWin;
+      // output sample n = 64 r + lane is row index 960 - n (n = 0: 0): the
+      // first half is lane 0 of register 0, lanes 33.. of register 7 and
+      // registers 8..14
+      float w[15];
 #pragma unroll
       for (int r = 0; r < 15; r++) {
         const int n = 64 * r + lane;
         const int i = (n == 0) ? 0 : kWin - n;
         const float yv = kWin * v[r].x;
-        y[i] = yv * win960(tb.hw, i);
+        w[r] = yv * win960(tb.hw, i);
+      }
+      if (fg & 2) {  // overlap-add (nowhere else: adding a zero would turn a -0 into +0)
+        if (lane == 0) w[0] += cq[0];
+        if (lane > 32) w[7] += cq[0];
+#pragma unroll
+        for (int j = 1; j < 8; j++) w[7 + j] += cq[j];
+      }
+      if (lane == 0) y[0] = w[0];
+      if (lane > 32) y[kWin - 64 * 7 - lane] = w[7];
+#pragma unroll
+      for (int r = 8; r < 15; r++) y[kWin - 64 * r - lane] = w[r];
+      if (fg & 4) {
+        if (lane > 0) y[kWin - lane] = w[0];
+#pragma unroll
+        for (int r = 1; r < 7; r++) y[kWin - 64 * r - lane] = w[r];
+        if (lane <= 32) y[kWin - 64 * 7 - lane] = w[7];
+      } else {
+        // the next slot's carry: sample n goes to the lane that holds n + 480
+        const bool hi = lane >= 32;
+        cq[0] = __shfl_xor(hi ? w[7] : w[0], 32);
+#pragma unroll
+        for (int j = 1; j < 8; j++) cq[j] = __shfl_xor(hi ? w[j - 1] : w[j], 32);
       }
       wfft::wsync();
     }
@@ -598,8 +650,9 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftbw(StagedArgs a) {
 // (BASELINE configs[4]'s fusion of the synthesis tail: overlap-add ->
 // 480 -> 2048 re-block -> FFT B -> band sums, VAD.zig:298-348,
 // PipelineFFT.zig:88-112).  A workgroup takes 4 / C streams, wave = (stream,
-// channel).  The wave walks its channel's ticks: overlap-add of the ys rows
-// (the next tick's rows load during this tick), the denoised samples go
+// channel).  The wave walks its channel's ticks: the head of the tick's ys
+// row, overlap-added here only at a seam (k_synthw has done it elsewhere; the
+// next tick's loads run during this tick), the denoised samples go
 // straight into the wave's LDS window (the current FFT-B window, VAD.zig's
 // fft_input_buffer), and when a tick completes the window the wave runs FFT B
 // on it in place (fftb_bands) -- the re-block ring in HBM only carries the
@@ -661,13 +714,20 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
       // lane l < 60 owns samples 8 l .. 8 l + 7 of each tick
       const bool sl = lane < 60;
       const int q = 8 * lane;
+      // a row's head already holds the overlap-add except at a seam (ys rows,
+      // fvad_staged.h); there the previous half is the state's synthesis
+      // memory (v == 0) or the tail of the row before
+      const long long f0 = (long long)s * V;
+      auto seam_of = [&](int t) { return ys_seam(f0 + t * C + c, t * C + c); };
       auto load = [&](int t, float4 (&cur)[2], float4 (&prv)[2]) {
         const int v = t * C + c;
         const float *cp = ysr + (size_t)v * kWin + q;
-        const float *pp = v == 0 ? stp + st::kSyn + q : ysr + (size_t)(v - 1) * kWin + kFrame + q;
         if (sl) {
           cur[0] = *reinterpret_cast<const float4 *>(cp);
           cur[1] = *reinterpret_cast<const float4 *>(cp + 4);
+        }
+        if (sl && seam_of(t)) {
+          const float *pp = v == 0 ? stp + st::kSyn + q : ysr + (size_t)(v - 1) * kWin + kFrame + q;
           prv[0] = *reinterpret_cast<const float4 *>(pp);
           prv[1] = *reinterpret_cast<const float4 *>(pp + 4);
         }
@@ -698,15 +758,19 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
         // the next tick's rows load now, or after this tick's FFT B (the
         // transform needs the registers)
         if (!complete && t + 1 < nt) load(t + 1, cn, pn);
-        float o[8];
-        o[0] = (cur[0].x + prv[0].x) * kInv;
-        o[1] = (cur[0].y + prv[0].y) * kInv;
-        o[2] = (cur[0].z + prv[0].z) * kInv;
-        o[3] = (cur[0].w + prv[0].w) * kInv;
-        o[4] = (cur[1].x + prv[1].x) * kInv;
-        o[5] = (cur[1].y + prv[1].y) * kInv;
-        o[6] = (cur[1].z + prv[1].z) * kInv;
-        o[7] = (cur[1].w + prv[1].w) * kInv;
+        float o[8] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w};
+        if (seam_of(t)) {  // (nowhere else: adding a zero would turn a -0 into +0)
+          o[0] += prv[0].x;
+          o[1] += prv[0].y;
+          o[2] += prv[0].z;
+          o[3] += prv[0].w;
+          o[4] += prv[1].x;
+          o[5] += prv[1].y;
+          o[6] += prv[1].z;
+          o[7] += prv[1].w;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) o[e] *= kInv;
         const size_t ot = (size_t)t * B + s;
         if (a.out_den && sl) {
           float4 *dp = reinterpret_cast<float4 *>(a.out_den + (ot * C + c) * kFrame + q);
@@ -782,7 +846,7 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
         reinterpret_cast<int *>(stp)[st::kFramesDone] = fd0 + nt;
         stp[st::kVolAcc] = vol;
       }
-      if (c == C - 1) {  // synthesis memory = second half of the stream's last frame
+      if (c == C - 1) {  // synthesis memory = second half of the stream's last frame (a tail ys_tail_kept keeps)
         const float4 *yl =
             reinterpret_cast<const float4 *>(a.ys + ((size_t)s * V + (size_t)nt * C - 1) * kWin + kFrame);
         float4 *dst = reinterpret_cast<float4 *>(stp + st::kSyn);

@@ -143,6 +143,10 @@ def staged_kernels(n_channels=2, fft_size=2048):
     xlp = 864 * 4
     plpc = (p["pitch downsample + autocorr + LPC + FIR5"] - xlp + 240 * 2 + 147 * 4 + 480 * 2 + 294 * 4 +
             480 * 2)
+    # a ys row: the head always, the tail only where no
+    # k_synthw wave adds it to the next frame -- every 8th frame (batches of
+    # kWB = 8), plus a stream's last frame of the push (1 in V, not counted)
+    ys_row = 480 * 4 + 480 * 4 / 8.0
     k = {
         "k_prep3": (p["prep: s16 scale + HP biquad + rms"], 480 * 4 * 2 + 4.0 / C),
         "k_fftAw": (p["analysis window + FFT A + scale"] + p["band energy Ex"] + 22 * 3 + dct_ly + xlp,
@@ -161,10 +165,12 @@ def staged_kernels(n_channels=2, fft_size=2048):
         "k_rnn3": (feat - 22 * 3 - dct_ly - dct_exp + p["GRU stack"],
                   (22 + 8 + 1) * 4 + (22 + 22 + 1) * 4),
         # k_synthw: pitch filter (X + r P, band energies, norm), gains, synthesis;
-        # reads X, P, Exp, g, Ex, Ep, smoothed g, silence; writes the windowed frame
+        # reads X, P, Exp, g, Ex, Ep, smoothed g, silence; writes the ys row (7 of
+        # 8 overlap-adds happen in its registers; the 480 adds stay charged to
+        # k_ola / k_olafb, the sum is unchanged)
         "k_synthw": (p["pitch filter + gains"] + p["synthesis (scale, FFT A, window, OLA, 1/32767)"] - 960,
-                    2 * spec + 5 * 22 * 4 + 4 + 960 * 4),
-        "k_ola": (960, 960 * 4 + 480 * 4 + 4.0 / C),
+                    2 * spec + 5 * 22 * 4 + 4 + ys_row),
+        "k_ola": (960, ys_row + 480 * 4 + 4.0 / C),
         "k_winmeta": (0.0, 4 * 4.0 / C),
         "k_fftbw": (p["re-block + FFT B share"], 480 * 4 + 4),
         # fft_size 512: the workgroup-per-window kernel, same work
@@ -175,7 +181,7 @@ def staged_kernels(n_channels=2, fft_size=2048):
     # kernel; the ys rows in, per-tick outputs out, the re-block window stays
     # in LDS (only the partial window crosses pushes through the ring:
     # <= 2047 samples each way per channel and push, ~2 x 8 KB / 50 ticks)
-    k["k_olafb"] = (960 + p["re-block + FFT B share"], 960 * 4 + 4 * 4.0 / C + 2 * 8192.0 / 50)
+    k["k_olafb"] = (960 + p["re-block + FFT B share"], ys_row + 4 * 4.0 / C + 2 * 8192.0 / 50)
     k["k_vadm_par"] = k["k_vadm_hbm"]  # the same machine, window-parallel (the push flushed at a sync point)
     k["k_gru16"] = k["k_rnn3"]  # FVAD_MODE_FP16: the same recurrence, gate sums on MFMA
     # FVAD_MODE_FP16_FUSED: k_pspecw's work and k_gru16's in one kernel; features
