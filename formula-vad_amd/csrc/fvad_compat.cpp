@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "../../include/fvad.h"
+#include "fvad_hip_own.h"
 #include "fvad_internal.h"
 #include "fvad_kernels.h"
 
@@ -128,12 +129,15 @@ void leaf_perm(int *perm, int out_base, int in_base, int fstride, const int *fac
   }
 }
 
+// kiss_fftr's device scratch.  It lives as long as the process: allocated on
+// first use and never destroyed, so no HIP call runs at static destruction
 struct DevScratch {
   int dev = -1;
   size_t cap = 0;
-  float *buf = nullptr;
-  hipStream_t stream = nullptr;
-} g_fft;
+  fvad::stream_ptr stream;
+  fvad::dev_ptr<float> buf;
+};
+DevScratch &g_fft = *new DevScratch;
 
 }  // namespace
 
@@ -197,21 +201,21 @@ extern "C" void kiss_fftr(kiss_fftr_cfg cfg, const float *timedata, kiss_fft_cpx
     std::abort();
   }
   if (g_fft.dev != dev || g_fft.cap < need) {
-    if (g_fft.buf) (void)hipFree(g_fft.buf);
-    if (!g_fft.stream && hipStreamCreate(&g_fft.stream) != hipSuccess) std::abort();
-    if (hipMalloc(&g_fft.buf, need * sizeof(float)) != hipSuccess) {
+    g_fft.buf.reset();
+    if (!g_fft.stream && fvad::make_stream(g_fft.stream, hipStreamDefault)) std::abort();
+    if (fvad::make_dev(g_fft.buf, need)) {
       std::fprintf(stderr, "kiss_fftr: device allocation failed\n");
       std::abort();
     }
     g_fft.cap = need;
     g_fft.dev = dev;
   }
-  float *d_tab = g_fft.buf;
+  float *d_tab = g_fft.buf.get();
   int *d_fac = reinterpret_cast<int *>(d_tab + tf);
   float *d_in = d_tab + tf + fac_floats;
   float *d_out = d_in + 2 * (size_t)nc;
   float *d_work = d_out + 2 * (size_t)(nc + 1);
-  hipStream_t s = g_fft.stream;
+  hipStream_t s = g_fft.stream.get();
   bool ok = hipMemcpyAsync(d_tab, tw, tf * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
             hipMemcpyAsync(d_fac, cfg->fac, sizeof(cfg->fac), hipMemcpyHostToDevice, s) == hipSuccess &&
             hipMemcpyAsync(d_in, timedata, 2 * (size_t)nc * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&

@@ -1,0 +1,321 @@
+// The batched engine's private parts: struct fvad_engine and the functions its
+// translation units share (fvad_engine.cpp, fvad_engine_ingest.cpp,
+// fvad_engine_vadm.cpp, fvad_engine_lifecycle.cpp).  Host code only: not
+// installed, and no .hip file includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <deque>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/fvad.h"
+#include "fvad_hip_own.h"
+#include "fvad_internal.h"
+#include "fvad_kernels.h"
+#include "fvad_lifecycle.h"
+#include "fvad_staged.h"
+#include "fvad_sweep.h"
+
+#define HIP_TRY(expr)                                                                                             \
+  do {                                                                                                            \
+    hipError_t e_ = (expr);                                                                                       \
+    if (e_ != hipSuccess) return fvad::eng::fail(FVAD_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+namespace fvad {
+namespace eng {
+
+inline int fail(int code, const std::string &msg) { return set_error(code, msg); }
+// the GRU stack on the matrix cores (configs[4]): split (k_pspecw + k_gru16) or fused (k_fused16)
+inline bool fp16_mode(int mode) { return mode == FVAD_MODE_FP16 || mode == FVAD_MODE_FP16_FUSED; }
+// a cross-stream wait (skipping the ones already complete measured no gain:
+// DESIGN §8 r4)
+inline hipError_t wait_event(hipStream_t stream, hipEvent_t ev) { return hipStreamWaitEvent(stream, ev, 0); }
+
+// A begin / end event pair round work on one stream, read without waiting:
+// collect adds the sample once its end event has completed and leaves it
+// pending otherwise.  A begin over an unread sample drops that sample.
+struct EventTimer {
+  event_ptr ev[2];
+  bool pending = false;
+  int create() {
+    for (event_ptr &x : ev)
+      if (!x)
+        if (const int rc = make_event(x, true)) return rc;
+    return FVAD_OK;
+  }
+  int begin(hipStream_t s) {
+    pending = false;
+    HIP_TRY(hipEventRecord(ev[0].get(), s));
+    return FVAD_OK;
+  }
+  int end(hipStream_t s) {
+    HIP_TRY(hipEventRecord(ev[1].get(), s));
+    pending = true;
+    return FVAD_OK;
+  }
+  int collect(double &ms_sum, int &n) {
+    if (!pending || hipEventQuery(ev[1].get()) != hipSuccess) return FVAD_OK;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()));
+    ms_sum += ms;
+    n++;
+    pending = false;
+    return FVAD_OK;
+  }
+};
+
+// FNV-1a (64 bit), the hash of a stream blob's compatibility fields
+constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull;
+inline uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 0x100000001b3ull;
+  return h;
+}
+
+}  // namespace eng
+}  // namespace fvad
+
+struct fvad_engine {
+  // Ownership: every allocation, event and stream has exactly one owning
+  // member (fvad_hip_own.h); raw pointers beside them are views.  Members are
+  // destroyed in reverse order of declaration, so the streams come first
+  // here: every buffer and event is released before any stream, and the
+  // engine stream goes last (fvad_engine_destroy synchronises them before).
+  fvad::stream_ptr stream;
+  // H2D copies of the streaming ingest, created on first use (ensure_slots)
+  fvad::stream_ptr cstream;
+  // staged mode: k_prep3 runs on pstream, so push k's prep overlaps push k-1's
+  // kernels.  k_vadm_hbm runs on the side stream over one push's window
+  // outputs, overlapped with the next push (it only depends on its own state).
+  // Engines of one GPU may share either (fvad_engine_share_streams): the last
+  // owner destroys the stream; pstream / side are the streams in use.
+  std::shared_ptr<ihipStream_t> pstream_ref, side_ref;
+  hipStream_t pstream = nullptr, side = nullptr;
+
+  fvad_engine_config cfg{};
+  int ring_len = 0;
+  fvad::dev_ptr<fvad::Plan> d_plan;
+  fvad::dev_ptr<float> d_weights;
+  fvad::DevModel dmodel{};
+  fvad::dev_ptr<fvad::DevModel> d_model;
+  fvad::dev_ptr<float> d_state, d_ring, d_xbuf, d_vad, d_den;
+  // staged-mode intermediates
+  fvad::dev_ptr<float> d_X, d_P, d_Ex, d_Ep, d_Exp, d_Lyf, d_f34, d_rec, d_ptile, d_vadf, d_ys, d_gr, d_gs;
+  fvad::dev_ptr<int> d_sil, d_pitch, d_wtick;
+  fvad::dev_ptr<long long> d_wstart;
+  fvad::dev_ptr<int8_t> d_rnn_img;
+  fvad::dev_ptr<uint16_t> d_gru16;  // FVAD_MODE_FP16: MFMA weight fragments (f16 bits)
+  fvad::dev_ptr<float> d_gru16_bias;
+  // xs / xlp / ratio / ticks are double-buffered: push k uses buffer k & 1,
+  // reused once the push that used it last has finished (ev_buf_free[b]).
+  // d_xs, d_ratio, d_ticks: the buffer of the latest push (views)
+  fvad::dev_ptr<float> d_xs_b[2], d_ratio_b[2], d_xlp_b[2];
+  fvad::dev_ptr<int> d_ticks_b[2];
+  float *d_xs = nullptr, *d_ratio = nullptr;
+  int *d_ticks = nullptr;
+  fvad::event_ptr ev_prep_done[2], ev_buf_free[2];
+  bool buf_busy[2] = {false, false};
+  int next_buf = 0;
+  // the last push's k_fftAw done: push k's k_prep3 starts once push k-1's
+  // k_fftAw has finished, so it runs beside k_plpc / k_pcorr instead (measured:
+  // k_fftAw 0.64 -> 0.57, k_plpc 0.48 -> 0.40, k_pcorr 1.18 -> 1.24 ms, push
+  // 5.00 -> 4.90 ms; started after k_plpc it overruns into k_rnn3: 5.93 ms)
+  fvad::event_ptr ev_fft_a;
+  bool fft_a_rec = false;
+  // push k's k_fftAw runs on pstream (after its k_prep3) once push k-1's
+  // k_synthw, the last reader of what it writes, is done (ev_synth): beside
+  // push k-1's k_olafb instead of after it (push 4.87 -> 4.78 ms)
+  fvad::event_ptr ev_synth;
+  bool synth_rec = false;
+  hipEvent_t synth_wait = nullptr;  // the last push's k_synthw-end event: ev_synth, or ev[10] in a timed push (a view)
+  // Window outputs of push k in set k & 1; set 1 exists once VADMachines are
+  // attached (without them every push writes set 0): k_vadm_hbm of push k
+  // reads set k & 1 in place, push k + 2 rewrites it after that pass
+  // (ev_vadm_b).  vticks (with machines): the pass's copy of the push's ticks.
+  // d_wflag / d_wratio / d_wvad / d_band: the latest push's set (views).
+  struct WinOut {
+    fvad::dev_ptr<int> flag;
+    fvad::dev_ptr<float> ratio, vad, band;
+    fvad::dev_ptr<int32_t> vticks;
+  } wout[2];
+  int *d_wflag = nullptr;
+  float *d_wratio = nullptr, *d_wvad = nullptr, *d_band = nullptr;
+  // device VADMachines (fvad_engine_attach_vadm); vadm's pointers are views of
+  // the owners below
+  fvad::VadmArgs vadm{};
+  fvad::dev_ptr<fvad::VadmState> vadm_st;
+  fvad::dev_ptr<float> vadm_buf;
+  fvad::dev_ptr<fvad::VadmSeg> vadm_seg;
+  fvad::dev_ptr<unsigned long long> vadm_count;  // FVAD_DEBUG_VADM_COUNT
+  fvad::event_ptr ev_vadm, ev_vadm_b[2];
+  // The VADMachine of push k is enqueued when the next push is launched, as
+  // k_vadm_hbm (32 waves, overlapping that push quietly: the 512-wave burst of
+  // k_vadm_par beside the next push's k_fftAw cost more than it saved,
+  // measured), or at a sync point with nothing else queued as k_vadm_par
+  // (0.25 ms instead of 1.45: the drain of a job's last push).
+  bool vpend = false, vpend_timed = false;
+  int vpend_b = 0;
+  fvad::StagedArgs vpend_args{};
+  // a non-final k_vadm_hbm was queued last (its machines may owe their
+  // long-term fold): a sync point with no push pending resolves it with a
+  // resolve-only pass (vowed_args: that launch's argument block)
+  bool vowed = false;
+  fvad::StagedArgs vowed_args{};
+  // VADMachine timing never blocks the host (it would serialise the overlap):
+  // two timers alternate (vadm_slot) and are read once complete.  By kernel:
+  // [0] k_vadm_hbm (steady state), [1] k_vadm_par (a push flushed at a sync
+  // point); vadm_kind[slot]: the kernel a pending sample brackets
+  fvad::eng::EventTimer vt[2];
+  double vadm_ms_sum[2] = {};
+  int vadm_timed[2] = {};
+  int vadm_kind[2] = {};
+  int vadm_slot = 0;
+  bool dbg_always_par = false;  // test hook FVAD_DEBUG_VADM_ALWAYS_PAR
+  bool dbg_lt_full = false;     // test hook FVAD_DEBUG_VADM_LT_FULL
+  // Speech event feed (fvad_engine_enable_events).  The
+  // machine kernels stage events per lane in HBM (ev_stage), k_vadm_events
+  // packs them behind each pass into a ring in pinned host memory and writes
+  // the pass's header slot there; ev_flight holds, oldest first, the passes
+  // whose `done` event (recorded behind k_vadm_events) has not been seen
+  // complete yet.  poll_events reads the ring only up to the end cursor of the
+  // last retired pass: the host never looks at ring or header bytes of a pass
+  // before its event has completed (an event's completion releases the
+  // kernel's stores to the system, whichever coherence the allocation has).
+  struct EvPass {
+    uint64_t pass, push;
+    fvad::event_ptr done;
+  };
+  static constexpr int kEvHeaders = 64;  // header slots: passes in flight at most (an older one is waited for)
+  bool events_on = false;
+  fvad::dev_ptr<fvad::VadmEvRec> ev_stage;       // vadm.ev_stage
+  fvad::dev_ptr<unsigned> ev_count;              // vadm.ev_count
+  fvad::dev_ptr<unsigned long long> d_ev_cursor;  // device: [0] write cursor, [1] lost
+  fvad::pinned_ptr<fvad_event> h_ev_ring;         // written by the device through dv_ev_ring
+  fvad::VadmEvent *dv_ev_ring = nullptr;
+  fvad::pinned_ptr<fvad::VadmEventHeader> h_ev_hdr;  // [kEvHeaders], slot pass % kEvHeaders
+  fvad::VadmEventHeader *dv_ev_hdr = nullptr;
+  size_t ev_ring_cap = 0;
+  uint64_t ev_read = 0, ev_end = 0, ev_lost = 0;  // host read cursor; ring valid up to ev_end; lost so far
+  uint64_t ev_pass_next = 0;
+  uint64_t ev_pushes_done = 0;  // pushes up to here have every event in the ring's valid part
+  std::deque<EvPass> ev_flight;
+  std::vector<fvad::event_ptr> ev_pool;  // retired passes' events, re-used
+  uint64_t push_count = 0, vpend_push = 0;  // pushes launched since create / reset; the pending pass's
+  int dbg_events_chunk = 0;  // test hook FVAD_DEBUG_EVENTS_CHUNK
+  fvad::eng::EventTimer et[2];  // k_vadm_events' samples, by vadm_slot
+  double et_ms_sum = 0;
+  int et_timed = 0;
+  // test hook (fvad_engine_output_log): the per-tick outputs of the next
+  // log_cap pushes, copied on the engine stream as each push ends
+  fvad::dev_ptr<float> d_log;
+  int log_cap = 0, log_n = 0;
+  size_t log_stride = 0;
+  std::vector<int> log_ticks;
+  std::vector<fvad::VadmState> vadm_init;  // [m][stream] initial states
+  size_t vadm_buf_len = 0;
+  int rnn_act[fvad::rnnimg::kMats] = {};
+  int V = 0, L = 0, LX = 0, wmax = 0, grid_frames = 0;
+  int wpt = 1;  // window slots per (tick, stream): windows_per_tick(fft_size)
+  // FFT B above kMaxFftB: tables [tw | sup | hann | perm] and k_fftb's scratch
+  fvad::dev_ptr<float> d_fbtab;
+  fvad::dev_ptr<float2> d_fbwork;
+  int fb_work_blocks = 0;
+  long long fb_work_stride = 0;
+  int resident_ticks = 0;
+  int n_kernels = 0;
+  bool olafb = false;  // staged: k_olafb in place of k_ola, k_winmeta, k_fftbw (kernel 8)
+  // per-kernel timing events, two sets used alternately so the host reads
+  // push k's events while push k+1 is already queued (no launch gap).  The
+  // launchers take hipEvent_t *: evs holds the handles evs_own owns
+  fvad::event_ptr evs_own[2][FVAD_MAX_TIMES];
+  hipEvent_t evs[2][FVAD_MAX_TIMES] = {};
+  hipEvent_t *ev = evs[0];
+  int n_events = 0;    // timing events per launch
+  int last_event = 0;  // the one recorded last (the launch's end)
+  int ev_slot = 0;
+  bool slot_pending[2] = {false, false};
+  double ms_sum[FVAD_MAX_TIMES] = {};
+  int n_timed = 0;
+  int res_count = 0;  // run_resident calls since the last clear_times (event sampling)
+  int raw_s16 = 0;    // rnnoise compat mode (s16-scaled I/O)
+  fvad::dev_ptr<unsigned long long> d_stamps;  // diagnostic stamp buffer (FVAD_STAMPS builds)
+  fvad::dev_ptr<unsigned> d_work;              // staged: persistent-kernel group counters
+  // Device inputs alternate by push (d_pcm: the current one, a view): the
+  // input of push k+1 may be copied in while push k's k_prep3 still reads
+  // its own.  ev_in_free[i]: buffer i's last reader (k_prep3 / k_prep) done.
+  // run_resident reads d_pcm_b[0] (fvad_engine_load_synthetic).
+  fvad::dev_ptr<float> d_pcm_b[2];
+  float *d_pcm = nullptr;
+  // fvad_engine_load_synthetic_ex with n_pushes > 1: [push][tick][stream][ch][480]
+  fvad::dev_ptr<float> d_res;
+  int res_pushes = 0, res_next = 0;
+  fvad::event_ptr ev_in_free[2];
+  bool in_busy[2] = {false, false};
+  int in_next = 0;
+  // Streaming ingest (fvad_engine_submit / collect): pinned host input slots
+  // and output slots per in-flight push (kSlots = FVAD_MAX_IN_FLIGHT), H2D
+  // copies on cstream.  Allocated on first use.  With three pushes in
+  // flight the H2D of push k + 2 waits only for its device input buffer, free
+  // once push k's k_prep3 has read it -- not for push k's outputs.
+  struct Slot {
+    fvad::pinned_ptr<float> in;       // [max_ticks][B][C][480]
+    fvad::pinned_ptr<int16_t> in16;   // 16-bit input slot (fvad_engine_input_slot_i16; on first use)
+    fvad::pinned_ptr<int32_t> ticks;  // [B]
+    // outputs of the push that used this slot
+    fvad::pinned_ptr<float> vad, ratio, wratio, wvad, band, den;
+    fvad::pinned_ptr<int32_t> wflag;
+    fvad::event_ptr h2d, done;
+    bool h2d_busy = false, pending = false;
+    int n_ticks = 0;
+  } slots[FVAD_MAX_IN_FLIGHT];
+  int sub_next = 0, col_next = 0;
+  // device staging of a 16-bit submit that k_pcm16 converts into d_pcm: fused
+  // and no-denoiser engines, and the rnnoise compat mode (raw_s16)
+  fvad::dev_ptr<int16_t> d_pcm16;
+  // this push's input is 16-bit samples in d_pcm's buffer, read by k_prep3
+  // itself (staged engines with the denoiser: no d_pcm16, no k_pcm16)
+  bool pcm16_push = false;
+  // per-stream lifecycle (fvad_engine_reset_streams / save_streams / restore_streams)
+  uint64_t model_hash = 0;                  // of the model's int8 arrays (a blob's compatibility check)
+  std::vector<fvad_vadm_config> vadm_cfgs;  // the attached machines' configs (hashed into a blob's header)
+  fvad::dev_ptr<float> d_blob;              // device staging of a save / restore, grown on demand
+  size_t blob_cap = 0;                      //   (bytes)
+  // test hook FVAD_DEBUG_RESET_TIMES: timers round the launches of
+  // fvad_engine_reset_streams ([0] engine stream, [1] prep stream, [2] side
+  // stream), kRtSlots calls deep, read at fvad_engine_reset_times
+  static constexpr int kRtSlots = 64;
+  bool dbg_reset_times = false;
+  fvad::eng::EventTimer rt[kRtSlots][3];
+  int rt_next = 0;
+  double rt_ms[3] = {};
+  int rt_n[3] = {};
+};
+
+namespace fvad {
+namespace eng {
+
+// fvad_engine.cpp
+int launch(fvad_engine *e, int n_ticks, bool use_ticks, bool timed, bool use_tail = false);
+int fetch(fvad_engine *e, int n_ticks, fvad_outputs *o);
+int make_win_out(const fvad_engine *e, fvad_engine::WinOut &w);
+void use_win_out(fvad_engine *e, int b);
+// fvad_engine_ingest.cpp: the device input buffers
+hipStream_t input_reader(const fvad_engine *e);
+int input_buffer(fvad_engine *e, hipStream_t cs);
+int release_input(fvad_engine *e);
+int check_ticks(const fvad_engine *e, const int32_t *ticks_valid, int n_ticks);
+int tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, const int32_t *last, int n_ticks,
+               std::vector<int32_t> &tt);
+// fvad_engine_vadm.cpp
+int vadm_reset(fvad_engine *e);
+int vadm_flush(fvad_engine *e, bool fast = true);
+int events_reset(fvad_engine *e);
+int collect_vadm_timing(fvad_engine *e);
+
+}  // namespace eng
+}  // namespace fvad

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/fvad.h"
+#include "fvad_hip_own.h"
 #include "fvad_internal.h"
 #include "fvad_sweep.h"
 
@@ -34,8 +35,8 @@ struct Lane {  // results of (stream, config)
   fvad_vadm_snapshot snap{};
   std::vector<fvad_segment> segs;  // the first min(total, seg_capacity)
 };
-struct DevBuf {
-  void *p = nullptr;
+struct DevBuf {  // device bytes, grown on demand (ensure)
+  fvad::dev_ptr<char> p;
   size_t cap = 0;
 };
 }  // namespace
@@ -53,8 +54,8 @@ struct fvad_sweep {
   unsigned defer_max = 0;
   size_t chunk = 0;
   bool count_on = false;
-  // device
-  hipStream_t stream = nullptr;
+  // device (the stream first: it is destroyed after the buffers)
+  fvad::stream_ptr stream;
   DevBuf d_band, d_wmin, d_wvad, d_wvr, d_off, d_nwin, d_K, d_st, d_lt, d_sbuf, d_rbuf, d_seg, d_count;
   long long n_windows = 0;
 };
@@ -62,15 +63,9 @@ struct fvad_sweep {
 namespace {
 int ensure(DevBuf &b, size_t bytes) {
   if (bytes <= b.cap) return FVAD_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
+  b.p.reset();
   b.cap = 0;
-  const hipError_t e = hipMalloc(&b.p, std::max<size_t>(bytes, 256));
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    (void)hipGetLastError();
-    return set_error(FVAD_ENOMEM, std::string("hipMalloc (sweep): ") + hipGetErrorString(e));
-  }
+  if (const int rc = fvad::make_dev(b.p, std::max<size_t>(bytes, 256))) return rc;
   b.cap = std::max<size_t>(bytes, 256);
   return FVAD_OK;
 }
@@ -154,21 +149,21 @@ int upload_windows(fvad_sweep *sw) {
       (rc = ensure(sw->d_nwin, B * sizeof(int))))
     return rc;
   if (total) {
-    HIP_TRY(hipMemcpy(sw->d_band.p, band.data(), band.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sw->d_wvad.p, vad.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sw->d_wvr.p, vr.data(), total * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sw->d_band.p.get(), band.data(), band.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sw->d_wvad.p.get(), vad.data(), total * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sw->d_wvr.p.get(), vr.data(), total * sizeof(float), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipMemcpy(sw->d_off.p, off.data(), B * sizeof(long long), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(sw->d_nwin.p, nwin.data(), B * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(sw->d_off.p.get(), off.data(), B * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(sw->d_nwin.p.get(), nwin.data(), B * sizeof(int), hipMemcpyHostToDevice));
   sw->n_windows = (long long)total;
   fvad::SweepArgs a{};
   a.n_channels = c.n_channels;
   a.n_bands = c.n_bands;
   a.n_windows = sw->n_windows;
-  a.band = static_cast<const float *>(sw->d_band.p);
-  a.wmin = static_cast<float *>(sw->d_wmin.p);
-  HIP_TRY(fvad::launch_sweep_min(a, sw->stream));
-  HIP_TRY(hipStreamSynchronize(sw->stream));
+  a.band = reinterpret_cast<const float *>(sw->d_band.p.get());
+  a.wmin = reinterpret_cast<float *>(sw->d_wmin.p.get());
+  HIP_TRY(fvad::launch_sweep_min(a, sw->stream.get()));
+  HIP_TRY(hipStreamSynchronize(sw->stream.get()));
   sw->dirty = false;
   return FVAD_OK;
 }
@@ -194,7 +189,7 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
   int rc;
   if (sw->count_on) {
     if ((rc = ensure(sw->d_count, fvad::kVadmCounts * sizeof(unsigned long long)))) return rc;
-    HIP_TRY(hipMemsetAsync(sw->d_count.p, 0, fvad::kVadmCounts * sizeof(unsigned long long), sw->stream));
+    HIP_TRY(hipMemsetAsync(sw->d_count.p.get(), 0, fvad::kVadmCounts * sizeof(unsigned long long), sw->stream.get()));
   }
   std::vector<Lane> lanes(B * n);
   std::vector<fvad::VadmState> st;
@@ -222,40 +217,40 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     st.resize(nl);
     for (size_t s = 0; s < B; s++)
       for (size_t m = 0; m < nc; m++) st[s * nc + m] = s0[c0 + m];
-    HIP_TRY(hipMemcpyAsync(sw->d_K.p, K.data() + c0, nc * sizeof(fvad::VadmConst), hipMemcpyHostToDevice, sw->stream));
-    HIP_TRY(hipMemcpyAsync(sw->d_st.p, st.data(), nl * sizeof(fvad::VadmState), hipMemcpyHostToDevice, sw->stream));
+    HIP_TRY(hipMemcpyAsync(sw->d_K.p.get(), K.data() + c0, nc * sizeof(fvad::VadmConst), hipMemcpyHostToDevice, sw->stream.get()));
+    HIP_TRY(hipMemcpyAsync(sw->d_st.p.get(), st.data(), nl * sizeof(fvad::VadmState), hipMemcpyHostToDevice, sw->stream.get()));
     // entries never pushed are never read (lt_nw, the counts); zeroed all the same
-    HIP_TRY(hipMemsetAsync(sw->d_lt.p, 0, lt * sizeof(float), sw->stream));
-    HIP_TRY(hipMemsetAsync(sw->d_sbuf.p, 0, max_st * nl * sizeof(float), sw->stream));
-    HIP_TRY(hipMemsetAsync(sw->d_rbuf.p, 0, max_r * nl * sizeof(float), sw->stream));
+    HIP_TRY(hipMemsetAsync(sw->d_lt.p.get(), 0, lt * sizeof(float), sw->stream.get()));
+    HIP_TRY(hipMemsetAsync(sw->d_sbuf.p.get(), 0, max_st * nl * sizeof(float), sw->stream.get()));
+    HIP_TRY(hipMemsetAsync(sw->d_rbuf.p.get(), 0, max_r * nl * sizeof(float), sw->stream.get()));
     fvad::SweepArgs a{};
     a.n_streams = c.n_streams;
     a.n_cfgs = (int)nc;
     a.n_channels = c.n_channels;
     a.n_bands = c.n_bands;
     a.seg_cap = c.seg_capacity;
-    a.K = static_cast<const fvad::VadmConst *>(sw->d_K.p);
-    a.st = static_cast<fvad::VadmState *>(sw->d_st.p);
-    a.lt = static_cast<float *>(sw->d_lt.p);
-    a.sbuf = static_cast<float *>(sw->d_sbuf.p);
-    a.rbuf = static_cast<float *>(sw->d_rbuf.p);
-    a.seg = static_cast<fvad::VadmSeg *>(sw->d_seg.p);
-    a.win_off = static_cast<const long long *>(sw->d_off.p);
-    a.n_win = static_cast<const int *>(sw->d_nwin.p);
-    a.band = static_cast<const float *>(sw->d_band.p);
-    a.wmin = static_cast<float *>(sw->d_wmin.p);
-    a.wvad = static_cast<const float *>(sw->d_wvad.p);
-    a.wvr = static_cast<const float *>(sw->d_wvr.p);
+    a.K = reinterpret_cast<const fvad::VadmConst *>(sw->d_K.p.get());
+    a.st = reinterpret_cast<fvad::VadmState *>(sw->d_st.p.get());
+    a.lt = reinterpret_cast<float *>(sw->d_lt.p.get());
+    a.sbuf = reinterpret_cast<float *>(sw->d_sbuf.p.get());
+    a.rbuf = reinterpret_cast<float *>(sw->d_rbuf.p.get());
+    a.seg = reinterpret_cast<fvad::VadmSeg *>(sw->d_seg.p.get());
+    a.win_off = reinterpret_cast<const long long *>(sw->d_off.p.get());
+    a.n_win = reinterpret_cast<const int *>(sw->d_nwin.p.get());
+    a.band = reinterpret_cast<const float *>(sw->d_band.p.get());
+    a.wmin = reinterpret_cast<float *>(sw->d_wmin.p.get());
+    a.wvad = reinterpret_cast<const float *>(sw->d_wvad.p.get());
+    a.wvr = reinterpret_cast<const float *>(sw->d_wvr.p.get());
     a.n_windows = sw->n_windows;
     a.fft = (unsigned long long)c.fft_size;
     a.bound_scale = sw->bound_scale;
     a.defer_max = sw->defer_max;
-    a.count = sw->count_on ? static_cast<unsigned long long *>(sw->d_count.p) : nullptr;
-    HIP_TRY(fvad::launch_vadm_sweep(a, sw->stream));
-    HIP_TRY(hipStreamSynchronize(sw->stream));
+    a.count = sw->count_on ? reinterpret_cast<unsigned long long *>(sw->d_count.p.get()) : nullptr;
+    HIP_TRY(fvad::launch_vadm_sweep(a, sw->stream.get()));
+    HIP_TRY(hipStreamSynchronize(sw->stream.get()));
     seg.resize(nl * (size_t)c.seg_capacity);
-    HIP_TRY(hipMemcpy(st.data(), sw->d_st.p, nl * sizeof(fvad::VadmState), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(seg.data(), sw->d_seg.p, seg.size() * sizeof(fvad::VadmSeg), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st.data(), sw->d_st.p.get(), nl * sizeof(fvad::VadmState), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(seg.data(), sw->d_seg.p.get(), seg.size() * sizeof(fvad::VadmSeg), hipMemcpyDeviceToHost));
     for (size_t s = 0; s < B; s++)
       for (size_t m = 0; m < nc; m++)
         lane_from_device(st[s * nc + m], seg.data() + (s * nc + m) * (size_t)c.seg_capacity, c.seg_capacity,
@@ -263,7 +258,7 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     c0 = c1;
   }
   if (sw->count_on)
-    HIP_TRY(hipMemcpy(sw->counts, sw->d_count.p, sizeof(sw->counts), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sw->counts, sw->d_count.p.get(), sizeof(sw->counts), hipMemcpyDeviceToHost));
   sw->have_counts = sw->count_on;
   sw->lanes = std::move(lanes);
   sw->n_cfgs = n;
@@ -303,7 +298,7 @@ const Lane *lane_of(const fvad_sweep *sw, int stream, size_t cfg) {
 extern "C" int fvad_sweep_create(const fvad_sweep_config *cfg, fvad_sweep **out) {
   if (!cfg || !out) return set_error(FVAD_EINVAL, "null argument");
   if (const int rc = check_config(*cfg)) return rc;
-  hipStream_t stream = nullptr;
+  fvad::stream_ptr stream;
   if (cfg->device != -1) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -312,26 +307,19 @@ extern "C" int fvad_sweep_create(const fvad_sweep_config *cfg, fvad_sweep **out)
     }
     if (cfg->device < 0 || cfg->device >= ndev) return set_error(FVAD_EDEVICE, "device ordinal out of range");
     HIP_TRY(hipSetDevice(cfg->device));
-    HIP_TRY(hipStreamCreate(&stream));
+    if (const int rc = fvad::make_stream(stream, hipStreamDefault)) return rc;
   }
   fvad_sweep *sw = new fvad_sweep;
   sw->cfg = *cfg;
   sw->win.resize((size_t)cfg->n_streams);
-  sw->stream = stream;
+  sw->stream = std::move(stream);
   *out = sw;
   return FVAD_OK;
 }
 
 extern "C" void fvad_sweep_destroy(fvad_sweep *sw) {
   if (!sw) return;
-  if (sw->cfg.device != -1) {
-    (void)hipSetDevice(sw->cfg.device);
-    DevBuf *bufs[] = {&sw->d_band, &sw->d_wmin, &sw->d_wvad, &sw->d_wvr, &sw->d_off,  &sw->d_nwin, &sw->d_K,
-                      &sw->d_st,   &sw->d_lt,   &sw->d_sbuf, &sw->d_rbuf, &sw->d_seg, &sw->d_count};
-    for (DevBuf *b : bufs)
-      if (b->p) (void)hipFree(b->p);
-    if (sw->stream) (void)hipStreamDestroy(sw->stream);
-  }
+  if (sw->cfg.device != -1) (void)hipSetDevice(sw->cfg.device);
   delete sw;
 }
 

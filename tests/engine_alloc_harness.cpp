@@ -1,0 +1,306 @@
+// Ownership of the batched engine's GPU resources under allocation failure.
+//
+// The engine's real host translation units (fvad_engine*.cpp with
+// fvad_model.cpp, fvad_plan.cpp, fvad_synth.cpp) linked against two stubs
+// defined here, so the program needs no GPU:
+//   - a HIP runtime on the heap: device and pinned memory from calloc, copies
+//     are memcpy, events and streams are small heap objects, every query
+//     succeeds, elapsed times are 0, one device.  It counts live device
+//     allocations, pinned allocations, events and streams, refuses to release
+//     what is not live, and can fail the k-th creating call;
+//   - kernel launches: every fvad::launch_* and the host helpers the .hip
+//     files define return at once, doing only what the host code reads back.
+//
+// One scenario walks every allocation site of an engine kind.  Run without a
+// failure it must leave nothing live and gives the number N of creating
+// calls; then for every k < N the k-th creating call fails: the API call it
+// fails in must report it, destroy must still release everything, and
+// attach_vadm / enable_events must succeed when simply called again.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../include/fvad.h"
+#include "fvad_lifecycle.h"
+#include "fvad_kernels.h"
+#include "fvad_staged.h"
+
+// ---------------------------------------------------------------------------
+// stub HIP runtime
+// ---------------------------------------------------------------------------
+namespace {
+std::set<void *> g_dev, g_pinned, g_events, g_streams;
+long g_creates = 0;   // creating calls so far in this run
+long g_fail_at = -1;  // the creating call to fail (-1: none)
+int g_bad = 0;        // releases of something not live
+
+bool refuse() { return g_creates++ == g_fail_at; }
+hipError_t create(std::set<void *> &live, void **out, size_t bytes) {
+  if (refuse()) return hipErrorOutOfMemory;
+  *out = calloc(bytes ? bytes : 1, 1);
+  live.insert(*out);
+  return hipSuccess;
+}
+hipError_t release(std::set<void *> &live, void *p, const char *what) {
+  if (!live.erase(p)) {
+    std::printf("FAIL: %s of %p, which is not live\n", what, p);
+    g_bad++;
+    return hipErrorInvalidValue;
+  }
+  free(p);
+  return hipSuccess;
+}
+}  // namespace
+
+extern "C" {
+hipError_t hipMalloc(void **p, size_t n) { return create(g_dev, p, n); }
+hipError_t hipFree(void *p) { return p ? release(g_dev, p, "hipFree") : hipSuccess; }
+hipError_t hipHostMalloc(void **p, size_t n, unsigned) { return create(g_pinned, p, n); }
+hipError_t hipHostFree(void *p) { return p ? release(g_pinned, p, "hipHostFree") : hipSuccess; }
+hipError_t hipHostGetDevicePointer(void **dev, void *host, unsigned) {
+  *dev = host;
+  return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t *e) { return create(g_events, reinterpret_cast<void **>(e), 1); }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
+hipError_t hipEventDestroy(hipEvent_t e) { return release(g_events, e, "hipEventDestroy"); }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { return g_events.count(e) ? hipSuccess : hipErrorInvalidHandle; }
+hipError_t hipEventQuery(hipEvent_t e) { return g_events.count(e) ? hipSuccess : hipErrorInvalidHandle; }
+hipError_t hipEventSynchronize(hipEvent_t e) { return hipEventQuery(e); }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) {
+  *ms = 0;
+  return g_events.count(a) && g_events.count(b) ? hipSuccess : hipErrorInvalidHandle;
+}
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return create(g_streams, reinterpret_cast<void **>(s), 1); }
+hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned f, int) { return hipStreamCreateWithFlags(s, f); }
+hipError_t hipStreamDestroy(hipStream_t s) { return release(g_streams, s, "hipStreamDestroy"); }
+hipError_t hipStreamSynchronize(hipStream_t s) { return g_streams.count(s) ? hipSuccess : hipErrorInvalidHandle; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+  return g_streams.count(s) && g_events.count(e) ? hipSuccess : hipErrorInvalidHandle;
+}
+hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) {
+  *lo = 0;
+  *hi = -1;
+  return hipSuccess;
+}
+hipError_t hipGetDeviceCount(int *n) {
+  *n = 1;
+  return hipSuccess;
+}
+hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDevice; }
+hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
+  std::memset(p, 0, sizeof(*p));
+  p->multiProcessorCount = 4;
+  return hipSuccess;
+}
+hipError_t hipGetLastError(void) { return hipSuccess; }
+const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory (injected)" : "stub error"; }
+hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) {
+  std::memcpy(d, s, n);
+  return hipSuccess;
+}
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t) { return hipMemcpy(d, s, n, k); }
+hipError_t hipMemcpy2D(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind) {
+  for (size_t r = 0; r < h; r++) std::memcpy(static_cast<char *>(d) + r * dp, static_cast<const char *>(s) + r * sp, w);
+  return hipSuccess;
+}
+hipError_t hipMemset(void *d, int v, size_t n) {
+  std::memset(d, v, n);
+  return hipSuccess;
+}
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { return hipMemset(d, v, n); }
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// stub kernel launches and the host helpers of the .hip files
+// ---------------------------------------------------------------------------
+namespace fvad {
+hipError_t launch_prep(const PrepArgs &, hipStream_t) { return hipSuccess; }
+hipError_t launch_frame(const FrameArgs &, hipStream_t) { return hipSuccess; }
+hipError_t launch_prep(const StagedArgs &, hipStream_t, hipEvent_t *) { return hipSuccess; }
+hipError_t launch_staged(const StagedArgs &, int, hipStream_t, hipEvent_t *, hipEvent_t, hipStream_t, hipEvent_t,
+                         hipEvent_t) {
+  return hipSuccess;
+}
+hipError_t launch_nodenoise(const StagedArgs &, int, hipStream_t) { return hipSuccess; }
+hipError_t launch_pcm16(const int16_t *, float *, size_t, hipStream_t) { return hipSuccess; }
+hipError_t launch_vadm(const StagedArgs &, hipStream_t, bool fast, bool *ran_par) {
+  if (ran_par) *ran_par = fast;
+  return hipSuccess;
+}
+// the host reads the pass's header once the pass's event has completed
+hipError_t launch_vadm_events(const VadmEventArgs &a, hipStream_t) {
+  *a.header = VadmEventHeader{a.pass, 0, 0, 0};
+  return hipSuccess;
+}
+hipError_t launch_stream_clear(const ClearArgs &, hipStream_t) { return hipSuccess; }
+hipError_t launch_stream_vclear(const VClearArgs &, hipStream_t) { return hipSuccess; }
+hipError_t launch_stream_gather(const XferArgs &, hipStream_t) { return hipSuccess; }  // (the staging is zeroed: a valid record)
+hipError_t launch_stream_scatter(const XferArgs &, hipStream_t) { return hipSuccess; }
+const char *staged_kernel_name(int) { return "k_stub"; }
+bool olafb_fused(const StagedArgs &a) { return a.nfft_b == 2048 && a.n_channels <= 4; }
+bool fftb_generic(int) { return false; }
+// scratch only above kMaxFftB, so that kind reaches the d_fbwork allocation
+long long fftb_work_stride(int nfft_b, int, int, int) { return nfft_b > kMaxFftB ? nfft_b : 0; }
+int gru16_frag_count() { return 1; }
+int gru16_bias_rows() { return 1; }
+void gru16_build(const int8_t *, uint16_t *, float *) {}
+}  // namespace fvad
+
+// ---------------------------------------------------------------------------
+// the scenario
+// ---------------------------------------------------------------------------
+namespace {
+
+struct Kind {
+  const char *name;
+  int mode, fft_size, use_denoiser;
+  bool machines;  // fused engines refuse device VADMachines (and with them the event feed)
+};
+const Kind kKinds[] = {{"staged", FVAD_MODE_STAGED, 2048, 1, true},
+                       {"staged, fft_size above kMaxFftB", FVAD_MODE_STAGED, 2 * fvad::kMaxFftB, 1, true},
+                       {"fused", FVAD_MODE_FUSED, 2048, 1, false},
+                       {"fp16", FVAD_MODE_FP16, 2048, 1, true},
+                       {"use_denoiser = 0", FVAD_MODE_STAGED, 2048, 0, true}};
+
+constexpr int kStreams = 2, kChannels = 1, kTicks = 2;
+int g_fail = 0;
+fvad_model *g_model = nullptr;
+
+#define CHECK(cond, ...)            \
+  do {                              \
+    if (!(cond)) {                  \
+      std::printf("FAIL: ");        \
+      std::printf(__VA_ARGS__);     \
+      std::printf("\n");            \
+      g_fail++;                     \
+    }                               \
+  } while (0)
+
+bool all_released(const char *when, const Kind &k, long fail_at) {
+  const bool ok = g_dev.empty() && g_pinned.empty() && g_events.empty() && g_streams.empty();
+  CHECK(ok, "%s, failing call %ld, %s: live device %zu, pinned %zu, events %zu, streams %zu", k.name, fail_at, when,
+        g_dev.size(), g_pinned.size(), g_events.size(), g_streams.size());
+  return ok;
+}
+
+// One run of the scenario with creating call fail_at refused (-1: none).
+// Returns the creating calls made, -1 after a failed check.
+long run(const Kind &k, long fail_at) {
+  g_creates = 0;
+  g_fail_at = fail_at;
+  const int fails_before = g_fail;
+  fvad_engine *e = nullptr;
+  bool over = false;  // the scenario ended at the injected failure
+  // a step's status: negative only where the injected failure struck, and
+  // then with a message; `again` (attach_vadm, enable_events) repeats the call
+  auto step = [&](const char *what, auto call, bool again = false) {
+    if (over || g_fail != fails_before) return;
+    const long before = g_creates;
+    const bool bad = call();
+    const bool struck = fail_at >= before && fail_at < g_creates;
+    if (!struck) {
+      CHECK(!bad, "%s, failing call %ld: %s failed: %s", k.name, fail_at, what, fvad_last_error());
+      return;
+    }
+    CHECK(bad, "%s: %s succeeded although its creating call %ld failed", k.name, what, fail_at);
+    CHECK(fvad_last_error()[0] != 0, "%s: %s failed at creating call %ld without a message", k.name, what, fail_at);
+    if (again)
+      CHECK(!call(), "%s: %s repeated after its failed creating call %ld: %s", k.name, what, fail_at, fvad_last_error());
+    else
+      over = true;
+  };
+
+  fvad_engine_config cfg;
+  fvad_engine_config_default(&cfg, kStreams, kChannels);
+  cfg.mode = k.mode;
+  cfg.fft_size = k.fft_size;
+  cfg.use_denoiser = k.use_denoiser;
+  cfg.max_ticks = kTicks;
+  fvad_vadm_config vc{};  // (fvad_vadm_config_default lives in fvad_host.cpp, not linked here)
+  vc.speech_min_freq = 100;
+  vc.speech_max_freq = 1500;
+  vc.long_term_speech_avg_sec = 180;
+  vc.short_term_speech_avg_sec = 0.2f;
+  vc.speech_threshold_factor = 18;
+  vc.channel_vol_ratio_avg_sec = 0.5f;
+  vc.channel_vol_ratio_threshold = 0.5f;
+  vc.min_consecutive_sec_to_open = 0.2f;
+  vc.max_speech_gap_sec = 2;
+  vc.min_vad_duration_sec = 0.7f;
+  // the machine's speech band as an engine band (FFT.freqToBin, as vadm_fill_const)
+  const float bin_hz = (float)cfg.sample_rate / (float)cfg.fft_size;
+  cfg.band_lo[0] = (int)std::round(vc.speech_min_freq / bin_hz);
+  cfg.band_hi[0] = (int)std::round(vc.speech_max_freq / bin_hz);
+
+  step("create", [&] { return fvad_engine_create(&cfg, g_model, &e) < 0; });
+  if (!e) {  // create itself failed: nothing to destroy
+    all_released("after the failed create", k, fail_at);
+    return g_fail == fails_before ? g_creates : -1;
+  }
+  const size_t n_in = (size_t)kTicks * kStreams * kChannels * 480;
+  const int32_t stream0 = 0;
+  if (k.machines) {
+    step("attach_vadm", [&] { return fvad_engine_attach_vadm(e, &vc, 1, 4) < 0; }, true);
+    step("enable_events", [&] { return fvad_engine_enable_events(e, 16) < 0; }, true);
+  }
+  float *slot = nullptr;
+  step("input_slot", [&] { return (slot = fvad_engine_input_slot(e)) == nullptr; });
+  step("submit", [&] {
+    std::memset(slot, 0, n_in * sizeof(float));
+    return fvad_engine_submit(e, slot, kTicks, nullptr) < 0;
+  });
+  step("submit_i16", [&] {
+    const std::vector<int16_t> pcm(n_in, 0);
+    return fvad_engine_submit_i16(e, pcm.data(), kTicks, nullptr, nullptr) < 0;
+  });
+  for (int i = 0; i < 2; i++) step("collect", [&] { return fvad_engine_collect(e, nullptr, nullptr) < 0; });
+  step("load_synthetic_ex", [&] { return fvad_engine_load_synthetic_ex(e, kTicks, 2, 0) < 0; });
+  for (int i = 0; i < 2; i++) step("run_resident", [&] { return fvad_engine_run_resident(e, kTicks) < 0; });
+  step("set_debug", [&] { return fvad_engine_set_debug(e, FVAD_DEBUG_RESET_TIMES, 1) < 0; });
+  step("reset_streams", [&] { return fvad_engine_reset_streams(e, &stream0, 1) < 0; });
+  std::vector<char> blob;
+  step("save_streams", [&] {
+    blob.resize(fvad_engine_save_size(e, 1));
+    return fvad_engine_save_streams(e, &stream0, 1, blob.data(), blob.size()) < 0;
+  });
+  step("restore_streams", [&] { return fvad_engine_restore_streams(e, &stream0, 1, blob.data(), blob.size(), nullptr) < 0; });
+  step("kernel_times", [&] {
+    double ms[FVAD_MAX_TIMES];
+    int n = 0;
+    return fvad_engine_kernel_times(e, ms, &n) < 0;
+  });
+  fvad_engine_destroy(e);
+  all_released("after destroy", k, fail_at);
+  CHECK(fail_at < 0 || fail_at < g_creates, "%s: creating call %ld was never reached (%ld made)", k.name, fail_at,
+        g_creates);
+  return g_fail == fails_before ? g_creates : -1;
+}
+
+}  // namespace
+
+int main() {
+  if (fvad_model_synthetic(1, &g_model) != FVAD_OK) {
+    std::printf("FAIL: no synthetic model: %s\n", fvad_last_error());
+    return 1;
+  }
+  for (const Kind &k : kKinds) {
+    const long n = run(k, -1);
+    if (n < 0) continue;
+    long done = 0;
+    for (long f = 0; f < n; f++)
+      if (run(k, f) >= 0) done++;
+    std::printf("%s: %ld creating calls, %ld of them failed in turn and survived\n", k.name, n, done);
+    CHECK(done == n, "%s: %ld of %ld failure runs passed", k.name, done, n);
+  }
+  fvad_model_free(g_model);
+  CHECK(g_bad == 0, "%d releases of something not live", g_bad);
+  std::printf(g_fail ? "FAILED: %d checks\n" : "ok\n", g_fail);
+  return g_fail ? 1 : 0;
+}

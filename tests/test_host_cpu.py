@@ -245,3 +245,50 @@ def test_lazy_longterm_bound(tmp_path):
     assert worst < 0.5, out.stdout
     sharp = subprocess.run([str(exe), "200000", "1e-3"], capture_output=True, text=True, timeout=120)
     assert sharp.returncode == 1 and "MISMATCH" in sharp.stdout, sharp.stdout
+
+
+def test_engine_objects_export_only_the_api(fvad_mod):
+    """The engine's translation units define no global function outside the C
+    API: every global text symbol of build/fvad_engine*.cpp.o is a function
+    include/fvad.h declares, fvad_engine_set_raw_s16 (fvad_compat.cpp calls it)
+    or a name inside fvad:: -- a library dropped into another program must not
+    export helpers such as wait_event."""
+    import glob
+    import subprocess
+    hdr = open(os.path.join(ROOT, "include", "fvad.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    api = set(re.findall(r"\b(fvad_[A-Za-z0-9_]*)\s*\(", hdr)) | {"fvad_engine_set_raw_s16"}
+    units = ["fvad_engine", "fvad_engine_ingest", "fvad_engine_vadm", "fvad_engine_lifecycle"]
+    subprocess.check_call(["make", "-s", "-j", "4", "-C", PKG] + ["build/%s.cpp.o" % u for u in units])
+    objs = sorted(glob.glob(os.path.join(PKG, "build", "fvad_engine*.cpp.o")))
+    assert len(objs) == len(units), objs
+    seen = 0
+    for obj in objs:
+        out = subprocess.run(["nm", "-C", "--defined-only", obj], capture_output=True, text=True, check=True).stdout
+        for line in out.splitlines():
+            parts = line.split(None, 2)
+            if len(parts) < 3 or parts[1] != "T":
+                continue
+            seen += 1
+            name = parts[2]
+            assert name.startswith("fvad::") or name.split("(")[0] in api, (os.path.basename(obj), name)
+    assert seen >= 40
+
+
+def test_engine_releases_everything_when_an_allocation_fails():
+    """tests/engine_alloc_harness.cpp: the engine's host objects over a stub HIP
+    runtime that fails each creating call in turn, for staged (fft_size 2048
+    and above kMaxFftB), fused, fp16 and use_denoiser = 0 engines.  The failing
+    API call reports it, fvad_engine_destroy leaves no device memory, pinned
+    memory, event or stream live, and a failed attach_vadm / enable_events
+    succeeds when called again."""
+    import subprocess
+    subprocess.check_call(["make", "-s", "-j", "8", "-C", PKG, "build/engine_alloc_harness"])
+    out = subprocess.run([os.path.join(PKG, "build", "engine_alloc_harness")], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.strip().splitlines()
+    assert lines[-1] == "ok" and len(lines) == 6, out.stdout
+    for line in lines[:-1]:
+        m = re.search(r": (\d+) creating calls, (\d+) of them failed in turn and survived", line)
+        assert m and int(m[1]) == int(m[2]) >= 40, line
