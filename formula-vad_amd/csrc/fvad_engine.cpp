@@ -272,13 +272,17 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   // the re-block ring holds a window plus a push; a multiple of 4 so a
   // frame's float4 writes never straddle its end (k_ola, k_ndring)
   e->ring_len = (c.fft_size + c.max_ticks * fvad::kFrame + 3) & ~3;
-  e->n_kernels = c.mode != FVAD_MODE_FUSED ? fvad::kStagedKernels : 2;
-  if (c.mode != FVAD_MODE_FUSED && c.use_denoiser) {
+  e->n_kernels = 2;  // fused: k_prep, k_frame
+  if (c.mode != FVAD_MODE_FUSED) {
+    // the kernels of this engine's pushes (launch_staged's variant: run_staged
+    // sets a.fma, a.gru16_frags and a.fuse16 from the mode)
     fvad::StagedArgs probe{};
     probe.nfft_b = c.fft_size;
     probe.n_channels = c.n_channels;
-    e->olafb = fvad::olafb_fused(probe);
-    if (e->olafb) e->n_kernels = fvad::kStagedKernels - 2;  // k_olafb's events span k_ola's pair
+    const bool olafb = c.use_denoiser && fvad::olafb_fused(probe);
+    e->kernels = fvad::staged_kernels({c.mode == FVAD_MODE_F32_FAST && c.use_denoiser, fp16_mode(c.mode),
+                                       c.mode == FVAD_MODE_FP16_FUSED, olafb});
+    e->n_kernels = e->kernels.n;
   }
   e->n_events = c.mode != FVAD_MODE_FUSED ? fvad::kStagedEvents : 3;
   e->last_event = c.mode != FVAD_MODE_FUSED ? fvad::kStagedLast : 2;
@@ -579,7 +583,8 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
     HIP_TRY(fvad::launch_staged(a, e->grid_frames, e->stream.get(), timed ? e->ev : nullptr, e->ev_fft_a.get(),
                                 own_prep ? e->pstream : nullptr, e->synth_rec ? e->synth_wait : nullptr,
                                 e->ev_synth.get()));
-    e->synth_wait = timed ? e->ev[10] : e->ev_synth.get();  // (launch_staged records ev[10] in its place when timed)
+    // (launch_staged records the timing event in ev_synth's place when timed)
+    e->synth_wait = timed ? e->ev[fvad::kEvSynthEnd] : e->ev_synth.get();
     e->synth_rec = true;
     e->fft_a_rec = true;
   } else {
@@ -642,7 +647,7 @@ int collect_slot(fvad_engine *e, int slot) {
   HIP_TRY(hipEventSynchronize(ev[e->last_event]));
   for (int i = 0; i < e->n_kernels; i++) {
     float ms = 0;
-    const int b = staged ? fvad::kStagedTime[i][0] : i, en = staged ? fvad::kStagedTime[i][1] : i + 1;
+    const int b = staged ? e->kernels.k[i].begin : i, en = staged ? e->kernels.k[i].end : i + 1;
     HIP_TRY(hipEventElapsedTime(&ms, ev[b], ev[en]));
     e->ms_sum[1 + i] += ms;
   }
@@ -882,10 +887,7 @@ extern "C" const char *fvad_engine_kernel_name(const fvad_engine *e, int i) {
   if (e && i == e->n_kernels + 1 && e->vadm.n > 0) return "k_vadm_par";
   if (!e || i < 0 || i >= e->n_kernels) return nullptr;
   if (e->cfg.mode == FVAD_MODE_FUSED) return i == 0 ? "k_prep" : "k_frame";
-  if (fp16_mode(e->cfg.mode) && i == 6) return e->cfg.mode == FVAD_MODE_FP16_FUSED ? "k_fused16" : "k_gru16";
-  if (e->cfg.mode == FVAD_MODE_F32_FAST && e->cfg.use_denoiser && i == 6) return "k_rnn3f";
-  if (e->olafb && i == 8) return "k_olafb";
-  return fvad::staged_kernel_name(i);
+  return e->kernels.k[i].name;
 }
 
 extern "C" int fvad_engine_output_log(fvad_engine *e, int n_pushes) {

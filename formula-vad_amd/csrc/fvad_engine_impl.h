@@ -132,7 +132,7 @@ struct fvad_engine {
   // push k-1's k_olafb instead of after it (push 4.87 -> 4.78 ms)
   fvad::event_ptr ev_synth;
   bool synth_rec = false;
-  hipEvent_t synth_wait = nullptr;  // the last push's k_synthw-end event: ev_synth, or ev[10] in a timed push (a view)
+  hipEvent_t synth_wait = nullptr;  // the last push's k_synthw-end event: ev_synth, or ev[kEvSynthEnd] in a timed push (a view)
   // Window outputs of push k in set k & 1; set 1 exists once VADMachines are
   // attached (without them every push writes set 0): k_vadm_hbm of push k
   // reads set k & 1 in place, push k + 2 rewrites it after that pass
@@ -228,7 +228,7 @@ struct fvad_engine {
   long long fb_work_stride = 0;
   int resident_ticks = 0;
   int n_kernels = 0;
-  bool olafb = false;  // staged: k_olafb in place of k_ola, k_winmeta, k_fftbw (kernel 8)
+  fvad::StagedKernels kernels{};  // not fused: the kernels of a push and their timing events (n_kernels of them)
   // per-kernel timing events, two sets used alternately so the host reads
   // push k's events while push k+1 is already queued (no launch gap).  The
   // launchers take hipEvent_t *: evs holds the handles evs_own owns

@@ -65,7 +65,7 @@ FVAD_HD inline double add_const_n(double acc, double c, unsigned n) {
   return acc;
 }
 
-// The lazy long-term test of the device VADMachine (fvad_staged.hip
+// The lazy long-term test of the device VADMachine (fvad_vadm.hip
 // vadm_stream).  VADMachine.zig:150-167 tests st_avg > RN(lt_avg * f), lt_avg
 // the long-term RollingAverage's fold of its n terms t_i = RN(e_i / n)
 // (RollingAverage.zig:45-56, C order).  Between exact folds the walk carries

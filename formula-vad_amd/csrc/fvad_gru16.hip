@@ -1,6 +1,6 @@
 // k_gru16: the staged pipeline's recurrence with the GRU stack on the matrix
 // cores -- BASELINE.json configs[4]'s "fp16 GRU weights" variant (engine mode
-// FVAD_MODE_FP16), replacing k_rnn3 (fvad_staged.hip) and nothing else.
+// FVAD_MODE_FP16), replacing k_rnn3 (fvad_rnn3.hip) and nothing else.
 //
 // What it computes is rnnoise's compute_rnn (rnn.c, called from
 // rnnoise_process_frame at Denoiser.zig:60) plus the recurrent feature work

@@ -1,12 +1,13 @@
 // k_pcorr in a translation unit of its own: built without SLP vectorisation
 // (Makefile), which keeps its f32 sums in single VALU instructions -- measured
-// faster for this kernel (1.60 -> 1.46 ms), while k_plpc and the GRU kernel
-// in fvad_staged.hip prefer the packed form.
+// faster for this kernel (1.60 -> 1.46 ms), while k_plpc (fvad_plpc.hip) and
+// the GRU kernel (fvad_rnn3.hip) prefer the packed form.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
 #include "fvad_device.h"
 #include "fvad_internal.h"
+#include "fvad_launch.h"
 #include "fvad_staged.h"
 #include "fvad_staged_dev.h"
 
@@ -652,11 +653,7 @@ __global__ void __launch_bounds__(kPcNT) k_pcorr(StagedArgs a) {
 }
 
 hipError_t launch_pcorr(const StagedArgs &a, long long tiles, int n_cu, hipStream_t stream) {
-  static const int per_cu = [] {
-    int p = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, k_pcorr, kPcNT, 0) != hipSuccess || p < 1) p = 1;
-    return p;
-  }();
+  static const int per_cu = resident_per_cu(k_pcorr, kPcNT);
   const int resident = per_cu * n_cu;
   const long long groups = tiles * 4 * (ptile::kQuarter / kPcF);
   hipLaunchKernelGGL(k_pcorr, dim3((unsigned)std::min<long long>(groups, resident)), dim3(kPcNT), 0, stream, a);

@@ -1,7 +1,8 @@
-// Argument block and launcher of the staged (time-parallel) pipeline
-// (fvad_staged.hip).  Frame f = s * V + v, v = tick * C + channel: the
-// channels of a stream are one interleaved virtual rnnoise stream
-// (VAD.zig:274-296), so frame order within a stream is tick-major.
+// Argument block, stage table and launchers of the staged (time-parallel)
+// pipeline (fvad_staged.hip maps it; one stage family per translation unit).
+// Frame f = s * V + v, v = tick * C + channel: the channels of a stream are
+// one interleaved virtual rnnoise stream (VAD.zig:274-296), so frame order
+// within a stream is tick-major.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,8 +10,7 @@
 
 namespace fvad {
 
-constexpr int kStagedKernels = 11;
-constexpr int kWorkCounters = 64;  // persistent-kernel queues (fvad_staged.hip: take_group)
+constexpr int kWorkCounters = 64;  // persistent-kernel queues (fvad_staged_dev.h: take_group)
 constexpr int kPitchRecord = 80;  // floats per frame of the pitch record (k_pcorr -> k_select)
 
 // The wave-per-frame kernels take frames in batches of kWB consecutive frame
@@ -200,16 +200,88 @@ struct StagedArgs {
   unsigned long long *stamps;  // diagnostic build only (FVAD_STAMPS): per-phase cycles of k_rnn3
 };
 
-// Timing events: kernel i runs between ev[kStagedTime[i][0]] and
-// ev[kStagedTime[i][1]]; ev[0] and ev[kStagedLast] bracket the launch.
-constexpr int kStagedEvents = 15, kStagedLast = 13;
-constexpr int kStagedTime[kStagedKernels][2] = {{0, 1}, {2, 3},   {14, 4},  {4, 5},   {5, 6},  {7, 8},
-                                                {8, 9}, {9, 10}, {10, 11}, {11, 12}, {12, 13}};
-// k_prep3 on `stream` (ev[0], ev[1] around it); the engine runs it one push
-// ahead on its own stream (double-buffered xs / ratio / ticks).
+// true when launch_staged runs k_olafb in place of k_ola, k_winmeta, k_fftbw
+bool olafb_fused(const StagedArgs &a);
+
+// ---------------------------------------------------------------------------
+// The kernels of a push, described once: launch_prep / launch_staged record
+// the timing events by these names, the engine times and names its kernels
+// from staged_kernels().
+// ---------------------------------------------------------------------------
+// Timing events of a timed push, as indices into its event array (the values
+// are places in the engine's arrays, not the order of recording).  Every push
+// records all of them, whatever the variant.
+enum StagedEvent {
+  kEvPrepBegin = 0,  // the push's first
+  kEvPrepEnd = 1,
+  kEvFftABegin = 2,  // on the stream k_fftAw runs on
+  kEvFftAEnd = 3,
+  kEvPlpcEnd = 4,
+  kEvPcorrEnd = 5,
+  kEvSelectEnd = 6,
+  kEvPspecBegin = 7,
+  kEvPspecEnd = 8,
+  kEvRnnEnd = 9,
+  kEvSynthEnd = 10,  // in a timed push also the synthesis-done event the next push's k_fftAw waits for
+  kEvOlaEnd = 11,
+  kEvWinmetaEnd = 12,
+  kEvFftBEnd = 13,   // the push's last
+  kEvPlpcBegin = 14,  // on the main stream, once it has waited for k_fftAw
+  kStagedEvents = 15
+};
+constexpr StagedEvent kStagedFirst = kEvPrepBegin, kStagedLast = kEvFftBEnd;
+
+enum StagedStage {
+  kStagePrep, kStageFftA, kStagePlpc, kStagePcorr, kStageSelect, kStagePspec, kStageRnn, kStageSynth,
+  kStageOla, kStageWinmeta, kStageFftB, kStagedStages
+};
+// What launch_staged branches on.  fma: k_rnn3f is the recurrence
+// (FVAD_MODE_F32_FAST); fp16: k_gru16 is; fuse16: k_fused16 is and also does
+// k_pspecw's work; olafb: k_olafb is the whole tail.
+struct StagedVariant {
+  bool fma, fp16, fuse16, olafb;
+};
+inline StagedVariant staged_variant(const StagedArgs &a) {
+  const bool fp16 = a.gru16_frags != nullptr;
+  return {!fp16 && a.fma != 0, fp16, fp16 && a.fuse16 != 0, olafb_fused(a)};
+}
+struct StagedKernel {
+  StagedStage stage;
+  const char *name;
+  StagedEvent begin, end;  // the kernel runs between these two
+};
+struct StagedKernels {
+  int n;
+  StagedKernel k[kStagedStages];
+};
+// The kernels that run in a push of the variant, in pipeline order.  A stage
+// the variant does not run is not listed (its events then bracket nothing).
+constexpr StagedKernels staged_kernels(const StagedVariant &v) {
+  StagedKernels l{};
+  l.k[l.n++] = {kStagePrep, "k_prep3", kEvPrepBegin, kEvPrepEnd};
+  l.k[l.n++] = {kStageFftA, "k_fftAw", kEvFftABegin, kEvFftAEnd};
+  l.k[l.n++] = {kStagePlpc, "k_plpc", kEvPlpcBegin, kEvPlpcEnd};
+  l.k[l.n++] = {kStagePcorr, "k_pcorr", kEvPlpcEnd, kEvPcorrEnd};
+  l.k[l.n++] = {kStageSelect, "k_select", kEvPcorrEnd, kEvSelectEnd};
+  if (!v.fuse16) l.k[l.n++] = {kStagePspec, "k_pspecw", kEvPspecBegin, kEvPspecEnd};
+  l.k[l.n++] = {kStageRnn, v.fuse16 ? "k_fused16" : v.fp16 ? "k_gru16" : v.fma ? "k_rnn3f" : "k_rnn3", kEvPspecEnd,
+                kEvRnnEnd};
+  l.k[l.n++] = {kStageSynth, "k_synthw", kEvRnnEnd, kEvSynthEnd};
+  if (v.olafb) {
+    l.k[l.n++] = {kStageOla, "k_olafb", kEvSynthEnd, kEvFftBEnd};
+  } else {
+    l.k[l.n++] = {kStageOla, "k_ola", kEvSynthEnd, kEvOlaEnd};
+    l.k[l.n++] = {kStageWinmeta, "k_winmeta", kEvOlaEnd, kEvWinmetaEnd};
+    l.k[l.n++] = {kStageFftB, "k_fftbw", kEvWinmetaEnd, kEvFftBEnd};
+  }
+  return l;
+}
+
+// k_prep3 on `stream` (kEvPrepBegin, kEvPrepEnd around it); the engine runs
+// it one push ahead on its own stream (double-buffered xs / ratio / ticks).
 hipError_t launch_prep(const StagedArgs &a, hipStream_t stream, hipEvent_t *ev);
-// Launch the other 10 kernels; when ev != nullptr their timing events are
-// recorded.
+// Launch the other kernels of a push; when ev != nullptr their timing events
+// are recorded.
 // fft_a_done (optional): recorded right after k_fftAw (the next push's
 // k_prep3 waits for it).  fa_stream (optional, with fft_a_done): k_fftAw runs
 // there instead, after fa_after (the previous push's synth_done: the last
@@ -219,11 +291,18 @@ hipError_t launch_prep(const StagedArgs &a, hipStream_t stream, hipEvent_t *ev);
 hipError_t launch_staged(const StagedArgs &a, int n_cu, hipStream_t stream, hipEvent_t *ev,
                          hipEvent_t fft_a_done = nullptr, hipStream_t fa_stream = nullptr,
                          hipEvent_t fa_after = nullptr, hipEvent_t synth_done = nullptr);
-// k_pcorr over `tiles` pitch tiles (fvad_pitch.hip)
+// The stages' own launchers (each in its kernels' translation unit; n_cu: the
+// CUs the engine's stream may use).  k_plpc and k_pcorr over `tiles` pitch
+// tiles (fvad_plpc.hip, fvad_pitch.hip), k_select (fvad_vadm.hip)
+hipError_t launch_plpc(const StagedArgs &a, long long tiles, int n_cu, hipStream_t stream);
 hipError_t launch_pcorr(const StagedArgs &a, long long tiles, int n_cu, hipStream_t stream);
-const char *staged_kernel_name(int i);
-// true when launch_staged runs k_olafb in place of k_ola, k_winmeta, k_fftbw
-bool olafb_fused(const StagedArgs &a);
+hipError_t launch_select(const StagedArgs &a, hipStream_t stream);
+// k_rnn3, or k_rnn3f when a.fma (fvad_rnn3.hip)
+hipError_t launch_rnn3(const StagedArgs &a, hipStream_t stream);
+// the three-kernel tail (fvad_tail.hip); launch_fftb: k_fftbw for fft_size 2048, else k_fftb
+hipError_t launch_ola(const StagedArgs &a, hipStream_t stream);
+hipError_t launch_winmeta(const StagedArgs &a, hipStream_t stream);
+hipError_t launch_fftb(const StagedArgs &a, int n_cu, hipStream_t stream);
 // The wave-per-frame FFT kernels (fvad_wave.hip), persistent grids; kWaveFftB
 // needs fft_size 2048 (a 1024-point complex transform); kWaveOlaFb (k_ola +
 // k_winmeta + k_fftbw fused) needs fft_size 2048 and n_channels <= 4.

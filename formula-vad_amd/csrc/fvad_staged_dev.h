@@ -1,5 +1,6 @@
 // Device helpers shared by the staged kernels' translation units
-// (fvad_staged.hip, fvad_wave.hip, fvad_pitch.hip).
+// (fvad_prep.hip, fvad_wave.hip, fvad_plpc.hip, fvad_pitch.hip, fvad_rnn3.hip,
+// fvad_gru16.hip, fvad_tail.hip, fvad_vadm.hip).
 #pragma once
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
@@ -21,9 +22,12 @@ __device__ __forceinline__ int ticks_of(const StagedArgs &a, int s) {
 // under round-robin dispatch, which keeps each counter's atomics local and
 // few).  A workgroup that starts late -- beside another kernel's waves --
 // just takes fewer groups instead of stretching the launch with a tail.
-// The counters a.work[slot][8] are zeroed on the stream before every launch.
+// The counters a.work[slot][8] are zero when the engine is created, then
+// reset by every push's k_select for the next push (the kernels before it)
+// and this push (after it).
 constexpr int kQueues = 8;
 enum WorkSlot { kWorkFftA = 0, kWorkPlpc, kWorkPcorr, kWorkPspec, kWorkSynth, kWorkFftB, kWorkSlots };
+static_assert(kWorkSlots * kQueues <= kWorkCounters, "work counters");
 __device__ __forceinline__ long long take_group(const StagedArgs &a, int slot) {
   const int x = blockIdx.x % kQueues;
   return x + (long long)kQueues * atomicAdd(&a.work[slot * kQueues + x], 1u);
@@ -76,6 +80,14 @@ __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\
 #else
 __device__ __forceinline__ void lds_sync() { __syncthreads(); }
 #endif
+
+// LDS written and read back by lanes of the same wave only: LDS operations of
+// a wave execute in order, so a compiler-level fence is all that is needed.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // Diagnostic build only (-DFVAD_STAMPS): per-phase s_memtime totals of
 // thread 0 (it joins every barrier, so a phase's stamp is its critical path),

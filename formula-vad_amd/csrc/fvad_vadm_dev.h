@@ -1,5 +1,5 @@
 // The device VADMachine's per-window code, shared by the engine's machine
-// kernels (fvad_staged.hip: k_vadm_hbm, k_vadm_par) and the config sweep
+// kernels (fvad_vadm.hip: k_vadm_hbm, k_vadm_par) and the config sweep
 // (fvad_sweep.hip: k_vadm_sweep), so every kernel runs the same expressions in
 // the same order: the rolling averages, the long-term folds, the speech-state
 // machine, and the serial walk over a run of windows (vadm_walk), which takes

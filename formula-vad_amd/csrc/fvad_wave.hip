@@ -2,7 +2,7 @@
 // k_synthw).  A translation unit of their own: they are built without SLP
 // vectorisation (Makefile), which keeps their f32 arithmetic in single
 // (non-packed) VALU instructions -- measured faster for these kernels, while
-// the GRU kernel in fvad_staged.hip prefers the packed form.
+// the GRU kernel in fvad_rnn3.hip prefers the packed form.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
@@ -11,6 +11,7 @@
 
 #include "fvad_device.h"
 #include "fvad_internal.h"
+#include "fvad_launch.h"
 #include "fvad_staged.h"
 #include "fvad_staged_dev.h"
 #include "fvad_wavedev.h"
@@ -856,21 +857,11 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
   }
 }
 
-namespace {
-// workgroups of a kernel one CU holds (occupancy calculator, once per kernel)
-template <typename K>
-int wave_per_cu(K kernel, int nw = kWNW) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64 * nw, 0) != hipSuccess || per_cu < 1)
-    per_cu = 1;
-  return per_cu;
-}
-}  // namespace
-
 // n_cu: the CUs the engine's stream may use (all, or its CU mask's)
 hipError_t launch_wave(WaveKernel which, const StagedArgs &a, int n_cu, hipStream_t stream) {
-  static const int p_fftA = wave_per_cu(k_fftAw), p_pspec = wave_per_cu(k_pspecw, kPNW), p_synth = wave_per_cu(k_synthw, kSNW),
-                   p_fftb = wave_per_cu(k_fftbw), p_olafb = wave_per_cu(k_olafb);
+  static const int p_fftA = resident_per_cu(k_fftAw, 64 * kWNW), p_pspec = resident_per_cu(k_pspecw, 64 * kPNW),
+                   p_synth = resident_per_cu(k_synthw, 64 * kSNW), p_fftb = resident_per_cu(k_fftbw, 64 * kWNW),
+                   p_olafb = resident_per_cu(k_olafb, 64 * kWNW);
   // k_olafb: at most 2 of its 3 resident workgroups per CU.  Beside the next
   // push's k_fftAw (which starts ~10 us after it) it then leaves that kernel
   // a workgroup slot per CU from the start, and its 1 024 items (2 048 stereo

@@ -120,7 +120,7 @@ def prep_kernel_bytes(n_streams, n_channels, n_ticks):
 
 def staged_kernels(n_channels=2, fft_size=2048):
     """Per channel-frame algorithmic flops and HBM bytes of each staged kernel
-    (fvad_staged.hip).  Flops re-partition phases() (the sum is unchanged);
+    (fvad_staged.hip lists them and their translation units).  Flops re-partition phases() (the sum is unchanged);
     bytes are the kernel's compulsory reads + writes of its inputs/outputs in
     the staged layout.  k_pcorr's speculative work (the
     final 3-lag xcorr for every candidate instead of the selected one) is

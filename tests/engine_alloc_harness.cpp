@@ -143,7 +143,6 @@ hipError_t launch_stream_clear(const ClearArgs &, hipStream_t) { return hipSucce
 hipError_t launch_stream_vclear(const VClearArgs &, hipStream_t) { return hipSuccess; }
 hipError_t launch_stream_gather(const XferArgs &, hipStream_t) { return hipSuccess; }  // (the staging is zeroed: a valid record)
 hipError_t launch_stream_scatter(const XferArgs &, hipStream_t) { return hipSuccess; }
-const char *staged_kernel_name(int) { return "k_stub"; }
 bool olafb_fused(const StagedArgs &a) { return a.nfft_b == 2048 && a.n_channels <= 4; }
 bool fftb_generic(int) { return false; }
 // scratch only above kMaxFftB, so that kind reaches the d_fbwork allocation
@@ -283,6 +282,66 @@ long run(const Kind &k, long fail_at) {
   return g_fail == fails_before ? g_creates : -1;
 }
 
+// The stage table (fvad_staged.h staged_kernels, the real function): the
+// kernels of a push per pipeline variant, and that every list is a chain of
+// timing events from the push's first to its last.
+void check_stage_table() {
+  using fvad::StagedVariant;
+  struct Case {
+    const char *what;
+    StagedVariant v;  // fma, fp16, fuse16, olafb
+    std::vector<std::string> names;
+  };
+  const std::vector<std::string> front = {"k_prep3", "k_fftAw", "k_plpc", "k_pcorr", "k_select"};
+  auto with = [&](std::vector<std::string> rest) {
+    std::vector<std::string> l = front;
+    l.insert(l.end(), rest.begin(), rest.end());
+    return l;
+  };
+  const Case cases[] = {
+      {"staged, fused tail", {false, false, false, true}, with({"k_pspecw", "k_rnn3", "k_synthw", "k_olafb"})},
+      {"f32_fast", {true, false, false, true}, with({"k_pspecw", "k_rnn3f", "k_synthw", "k_olafb"})},
+      {"fp16", {false, true, false, true}, with({"k_pspecw", "k_gru16", "k_synthw", "k_olafb"})},
+      {"fp16_fused", {false, true, true, true}, with({"k_fused16", "k_synthw", "k_olafb"})},
+      {"three-kernel tail", {false, false, false, false},
+       with({"k_pspecw", "k_rnn3", "k_synthw", "k_ola", "k_winmeta", "k_fftbw"})},
+  };
+  for (const Case &c : cases) {
+    const fvad::StagedKernels l = fvad::staged_kernels(c.v);
+    std::vector<std::string> got;
+    for (int i = 0; i < l.n; i++) got.push_back(l.k[i].name);
+    std::string joined;
+    for (const std::string &s : got) joined += s + " ";
+    CHECK(got == c.names, "stage table, %s: kernels %s", c.what, joined.c_str());
+    CHECK(l.n >= 1 && l.n <= fvad::kStagedStages && l.n + 2 < FVAD_MAX_TIMES, "stage table, %s: %d kernels", c.what, l.n);
+    for (int i = 0; i < l.n; i++) {
+      CHECK(l.k[i].begin >= 0 && l.k[i].begin < fvad::kStagedEvents && l.k[i].end >= 0 &&
+                l.k[i].end < fvad::kStagedEvents && l.k[i].begin != l.k[i].end,
+            "stage table, %s: %s runs between events %d and %d", c.what, l.k[i].name, l.k[i].begin, l.k[i].end);
+      CHECK(i == 0 || l.k[i].stage > l.k[i - 1].stage, "stage table, %s: %s out of pipeline order", c.what, l.k[i].name);
+    }
+    CHECK(l.k[0].begin == fvad::kStagedFirst, "stage table, %s: starts at event %d", c.what, l.k[0].begin);
+    CHECK(l.k[l.n - 1].end == fvad::kStagedLast, "stage table, %s: ends at event %d", c.what, l.k[l.n - 1].end);
+  }
+  // the variant as launch_staged derives it from a push's arguments
+  fvad::StagedArgs a{};
+  a.nfft_b = 2048;
+  a.n_channels = 2;
+  a.fma = 1;
+  StagedVariant v = fvad::staged_variant(a);
+  CHECK(v.fma && !v.fp16 && !v.fuse16 && v.olafb, "staged_variant: f32_fast");
+  a.gru16_frags = &a;  // the fp16 recurrence runs whatever a.fma says
+  a.fuse16 = 1;
+  a.nfft_b = 1000;
+  v = fvad::staged_variant(a);
+  CHECK(!v.fma && v.fp16 && v.fuse16 && !v.olafb, "staged_variant: fp16_fused, fft_size 1000");
+  a.gru16_frags = nullptr;  // (fuse16 means nothing without the fp16 recurrence)
+  a.fma = 0;
+  v = fvad::staged_variant(a);
+  CHECK(!v.fma && !v.fp16 && !v.fuse16 && !v.olafb, "staged_variant: staged, fft_size 1000");
+  static_assert(fvad::kStagedEvents <= FVAD_MAX_TIMES && fvad::kStagedLast < fvad::kStagedEvents, "timing events");
+}
+
 }  // namespace
 
 int main() {
@@ -290,6 +349,7 @@ int main() {
     std::printf("FAIL: no synthetic model: %s\n", fvad_last_error());
     return 1;
   }
+  check_stage_table();
   for (const Kind &k : kKinds) {
     const long n = run(k, -1);
     if (n < 0) continue;

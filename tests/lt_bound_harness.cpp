@@ -1,5 +1,5 @@
 // tests/test_host_cpu.py::test_lazy_longterm_bound: the device VADMachine's
-// lazy long-term test (fvad_staged.hip vadm_stream, through fvad_exact.h's
+// lazy long-term test (fvad_vadm.hip vadm_stream, through fvad_exact.h's
 // lt_bound / lt_decide / lt_estimate -- the same header the kernel includes)
 // against the reference's exact decision, st_avg > RN(avg * f) with avg the
 // RollingAverage fold (RollingAverage.zig:45-56: avg += data[i] * scalar in

@@ -20,7 +20,7 @@ PKG = os.path.join(ROOT, "formula-vad_amd")
 # did not beat their exact kernels: they and their rows are not in the tree,
 # DESIGN.md section 3)
 TWINS = {
-    "k_rnn3f": ("k_rnn3", "fvad_staged.hip", 4),
+    "k_rnn3f": ("k_rnn3", "fvad_rnn3.hip", 4),
 }
 SOURCES = sorted({v[1] for v in TWINS.values()})
 # (v_fmac_f32 is v_fma_f32 with the addend in the destination register: the form

@@ -75,3 +75,35 @@ def test_fused16_kernel_names(fvad_mod, model):
     pu.engine_run(fvad_mod, eng, streams, 50, denoised=False)
     kt = eng.kernel_times()["kernels"]
     assert "k_fused16" in kt and "k_gru16" not in kt and "k_rnn3" not in kt, kt
+    assert list(kt) == FRONT + ["k_fused16", "k_synthw", "k_olafb"], kt
+    assert "k_pspecw" not in kt
+
+
+FRONT = ["k_prep3", "k_fftAw", "k_plpc", "k_pcorr", "k_select"]
+ENGINES = {  # engine -> (constructor arguments, the kernels of its pushes)
+    "staged": ({}, FRONT + ["k_pspecw", "k_rnn3", "k_synthw", "k_olafb"]),
+    "f32_fast": ({"mode": "f32_fast"}, FRONT + ["k_pspecw", "k_rnn3f", "k_synthw", "k_olafb"]),
+    "fp16": ({"mode": "fp16"}, FRONT + ["k_pspecw", "k_gru16", "k_synthw", "k_olafb"]),
+    "fp16_fused": ({"mode": "fp16_fused"}, FRONT + ["k_fused16", "k_synthw", "k_olafb"]),
+    "three-kernel tail": ({"fft_size": 1000, "bands": ((2, 31),)},
+                          FRONT + ["k_pspecw", "k_rnn3", "k_synthw", "k_ola", "k_winmeta", "k_fftbw"]),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(ENGINES))
+def test_kernel_times_list_what_ran(fvad_mod, model, kind):
+    """kernel_times() names exactly the kernels of the engine's pushes (the
+    stage table, fvad_staged.h), and each of them took time in the timed
+    pushes: an entry between two events with no kernel in between reads 0."""
+    kw, names = ENGINES[kind]
+    eng = fvad_mod.Engine(model, 2, 2, max_ticks=10, **kw)
+    eng.load_synthetic(10, 3)
+    for _ in range(8):  # every fourth resident push is timed
+        eng.run_resident(10)
+    kt = eng.kernel_times()
+    print(kind, kt)
+    assert list(kt["kernels"]) == names
+    assert kt["runs"] >= 1
+    for k, ms in kt["kernels"].items():
+        assert ms > 0, (k, kt)
+    assert kt["total_ms"] >= max(kt["kernels"].values()), kt

@@ -40,7 +40,7 @@ def host_segments(fvad_mod, outs, cfg, C, slot, stream):
 def test_device_vadm_matches_host(fvad_mod, alt_init, alt_lt_sec, sync_each, defer_max, bound):
     """bound -1: FVAD_DEBUG_VADM_BOUND_SCALE infinite -- every long-term test
     the lazy walk's estimate would settle takes the exact fold instead (the
-    branch the bound leaves open, fvad_staged.hip vadm_stream), counted with
+    branch the bound leaves open, fvad_vadm.hip vadm_stream), counted with
     FVAD_DEBUG_VADM_COUNT."""
     m = fvad_mod.Model(seed=1)
     alt = fvad_mod.VadmConfig.default()

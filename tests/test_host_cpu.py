@@ -220,7 +220,7 @@ def test_add_const_n_exact(tmp_path):
 
 
 def test_lazy_longterm_bound(tmp_path):
-    """The device VADMachine's lazy long-term test (fvad_staged.hip vadm_stream
+    """The device VADMachine's lazy long-term test (fvad_vadm.hip vadm_stream
     via fvad_exact.h lt_bound / lt_decide / lt_estimate, the code the kernel
     compiles) decides exactly as the reference's st_avg > RN(avg * f)
     (VADMachine.zig:150-167, RollingAverage.zig:45-56) on 2 * 10^6 adversarial

@@ -45,7 +45,8 @@ def resources(src):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_kernel_register_budgets():
     got = {}
-    for src in ("fvad_staged.hip", "fvad_pitch.hip", "fvad_wave.hip", "fvad_gru16.hip"):
+    for src in ("fvad_prep.hip", "fvad_plpc.hip", "fvad_rnn3.hip", "fvad_vadm.hip", "fvad_pitch.hip", "fvad_wave.hip",
+                "fvad_gru16.hip"):
         got.update(resources(src))
     for k, (occ, spill) in EXPECT.items():
         assert k in got, (k, sorted(got))

@@ -1,5 +1,5 @@
 // Microbenchmark (diagnostic, not part of the product): the floor of k_prep3's
-// serial HP biquad (fvad_staged.hip prep_chain `step`, rnnoise denoise.c
+// serial HP biquad (fvad_prep.hip prep_chain `step`, rnnoise denoise.c
 // biquad with f64 intermediates), register-only: a lane walks its own chain
 // over samples held in registers, so no memory latency is involved.
 //   mode 0  the exact step, 1 chain per lane               (the chain floor)
