@@ -1,7 +1,10 @@
 // Config sweep (include/fvad.h: fvad_sweep_*): the recorded windows, the
-// validation, the device run in chunks (k_vadm_sweep, fvad_sweep.hip), the
-// host run (the host VADMachine, fvad_host.cpp) and the scores (the host
-// evaluator).  Everything but fvad_sweep_run on a device sweep is host code.
+// validation, the device run in chunks (k_vadm_sweep, fvad_sweep.hip; with
+// fvad_sweep_run_score each chunk's k_sweep_score behind it,
+// fvad_sweep_score.hip), the host run (the host VADMachine, fvad_host.cpp) and
+// the scores (fvad_sweep_score: the host evaluator; fvad_sweep_run_score: the
+// shared core, fvad_eval_core.h).  Everything but fvad_sweep_run and
+// fvad_sweep_run_score on a device sweep is host code.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,9 +12,11 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/fvad.h"
+#include "fvad_eval_core.h"
 #include "fvad_hip_own.h"
 #include "fvad_internal.h"
 #include "fvad_sweep.h"
@@ -39,6 +44,14 @@ struct DevBuf {  // device bytes, grown on demand (ensure)
   fvad::dev_ptr<char> p;
   size_t cap = 0;
 };
+struct Score {  // one fvad_sweep_run_score call: what the lanes are scored against, and their scores
+  std::vector<float> lab;      // every stream's (from, to), each stream's stably sorted by start
+  std::vector<long long> off;  // [n_streams + 1] first label of a stream
+  const fvad_stat_config *stat = nullptr;
+  size_t n_stat = 0;  // 1 or n_cfgs
+  std::vector<fvad_single_stats> single;  // [stream][cfg]
+  std::vector<unsigned> status;           // [stream][cfg] fvad::kEval*
+};
 }  // namespace
 
 struct fvad_sweep {
@@ -47,6 +60,8 @@ struct fvad_sweep {
   bool dirty = true;  // the device copy of the windows is stale
   size_t n_cfgs = 0;
   std::vector<Lane> lanes;  // [stream][cfg]
+  bool kept = true;         // the last run kept its segments (fvad_sweep_run_score does not)
+  size_t bytes_back = 0;    // device-to-host bytes of the last run
   bool have_counts = false;
   unsigned long long counts[fvad::kVadmCounts] = {};
   // test hooks
@@ -57,6 +72,7 @@ struct fvad_sweep {
   // device (the stream first: it is destroyed after the buffers)
   fvad::stream_ptr stream;
   DevBuf d_band, d_wmin, d_wvad, d_wvr, d_off, d_nwin, d_K, d_st, d_lt, d_sbuf, d_rbuf, d_seg, d_count;
+  DevBuf d_lab, d_lab_off, d_stat, d_single, d_status;  // fvad_sweep_run_score
   long long n_windows = 0;
 };
 
@@ -180,7 +196,9 @@ void lane_from_device(const fvad::VadmState &st, const fvad::VadmSeg *seg, int s
   }
 }
 
-int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vector<fvad::VadmState> &s0) {
+// sc: null (the segments come back), or the lanes are scored on the device and
+// their statistics and status words come back instead
+int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vector<fvad::VadmState> &s0, Score *sc) {
   const fvad_sweep_config &c = sw->cfg;
   const size_t B = (size_t)c.n_streams, n = K.size();
   HIP_TRY(hipSetDevice(c.device));
@@ -191,9 +209,24 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     if ((rc = ensure(sw->d_count, fvad::kVadmCounts * sizeof(unsigned long long)))) return rc;
     HIP_TRY(hipMemsetAsync(sw->d_count.p.get(), 0, fvad::kVadmCounts * sizeof(unsigned long long), sw->stream.get()));
   }
+  if (sc) {  // the labels and the stat configs, once per call
+    if ((rc = ensure(sw->d_lab, sc->lab.size() * sizeof(float))) ||
+        (rc = ensure(sw->d_lab_off, sc->off.size() * sizeof(long long))) ||
+        (rc = ensure(sw->d_stat, sc->n_stat * sizeof(fvad_stat_config))))
+      return rc;
+    const auto up = [&](DevBuf &d, const void *src, size_t bytes) {
+      return bytes ? hipMemcpyAsync(d.p.get(), src, bytes, hipMemcpyHostToDevice, sw->stream.get()) : hipSuccess;
+    };
+    HIP_TRY(up(sw->d_lab, sc->lab.data(), sc->lab.size() * sizeof(float)));
+    HIP_TRY(up(sw->d_lab_off, sc->off.data(), sc->off.size() * sizeof(long long)));
+    HIP_TRY(up(sw->d_stat, sc->stat, sc->n_stat * sizeof(fvad_stat_config)));
+  }
   std::vector<Lane> lanes(B * n);
   std::vector<fvad::VadmState> st;
   std::vector<fvad::VadmSeg> seg;
+  std::vector<fvad_single_stats> single;
+  std::vector<unsigned> status;
+  size_t bytes_back = 0;
   for (size_t c0 = 0; c0 < n;) {
     // the chunk: configs [c0, c1), by the test hook or as many as the budget holds (one at least)
     size_t c1 = c0 + 1;
@@ -213,6 +246,9 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
         (rc = ensure(sw->d_lt, lt * sizeof(float))) || (rc = ensure(sw->d_sbuf, max_st * nl * sizeof(float))) ||
         (rc = ensure(sw->d_rbuf, max_r * nl * sizeof(float))) ||
         (rc = ensure(sw->d_seg, nl * (size_t)c.seg_capacity * sizeof(fvad::VadmSeg))))
+      return rc;
+    if (sc && ((rc = ensure(sw->d_single, nl * sizeof(fvad_single_stats))) ||
+               (rc = ensure(sw->d_status, nl * sizeof(unsigned)))))
       return rc;
     st.resize(nl);
     for (size_t s = 0; s < B; s++)
@@ -247,14 +283,45 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     a.defer_max = sw->defer_max;
     a.count = sw->count_on ? reinterpret_cast<unsigned long long *>(sw->d_count.p.get()) : nullptr;
     HIP_TRY(fvad::launch_vadm_sweep(a, sw->stream.get()));
+    if (sc) {
+      fvad::ScoreArgs b{};
+      b.n_streams = c.n_streams;
+      b.n_cfgs = (int)nc;
+      b.seg_cap = c.seg_capacity;
+      b.st = a.st;
+      b.seg = a.seg;
+      b.lab = reinterpret_cast<const float *>(sw->d_lab.p.get());
+      b.lab_off = reinterpret_cast<const long long *>(sw->d_lab_off.p.get());
+      b.stat_stride = sc->n_stat == 1 ? 0 : 1;
+      b.stat = reinterpret_cast<const fvad_stat_config *>(sw->d_stat.p.get()) + c0 * (size_t)b.stat_stride;
+      b.single = reinterpret_cast<fvad_single_stats *>(sw->d_single.p.get());
+      b.status = reinterpret_cast<unsigned *>(sw->d_status.p.get());
+      HIP_TRY(fvad::launch_sweep_score(b, sw->stream.get()));
+    }
     HIP_TRY(hipStreamSynchronize(sw->stream.get()));
-    seg.resize(nl * (size_t)c.seg_capacity);
     HIP_TRY(hipMemcpy(st.data(), sw->d_st.p.get(), nl * sizeof(fvad::VadmState), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(seg.data(), sw->d_seg.p.get(), seg.size() * sizeof(fvad::VadmSeg), hipMemcpyDeviceToHost));
-    for (size_t s = 0; s < B; s++)
-      for (size_t m = 0; m < nc; m++)
-        lane_from_device(st[s * nc + m], seg.data() + (s * nc + m) * (size_t)c.seg_capacity, c.seg_capacity,
-                         &lanes[s * n + c0 + m]);
+    bytes_back += nl * sizeof(fvad::VadmState);
+    if (sc) {
+      single.resize(nl);
+      status.resize(nl);
+      HIP_TRY(hipMemcpy(single.data(), sw->d_single.p.get(), nl * sizeof(fvad_single_stats), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(status.data(), sw->d_status.p.get(), nl * sizeof(unsigned), hipMemcpyDeviceToHost));
+      bytes_back += nl * (sizeof(fvad_single_stats) + sizeof(unsigned));
+      for (size_t s = 0; s < B; s++)
+        for (size_t m = 0; m < nc; m++) {
+          fvad::vadm_snapshot_of(st[s * nc + m], &lanes[s * n + c0 + m].snap);
+          sc->status[s * n + c0 + m] = status[s * nc + m];
+          sc->single[s * n + c0 + m] = single[s * nc + m];
+        }
+    } else {
+      seg.resize(nl * (size_t)c.seg_capacity);
+      HIP_TRY(hipMemcpy(seg.data(), sw->d_seg.p.get(), seg.size() * sizeof(fvad::VadmSeg), hipMemcpyDeviceToHost));
+      bytes_back += seg.size() * sizeof(fvad::VadmSeg);
+      for (size_t s = 0; s < B; s++)
+        for (size_t m = 0; m < nc; m++)
+          lane_from_device(st[s * nc + m], seg.data() + (s * nc + m) * (size_t)c.seg_capacity, c.seg_capacity,
+                           &lanes[s * n + c0 + m]);
+    }
     c0 = c1;
   }
   if (sw->count_on)
@@ -262,10 +329,14 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
   sw->have_counts = sw->count_on;
   sw->lanes = std::move(lanes);
   sw->n_cfgs = n;
+  sw->kept = !sc;
+  sw->bytes_back = bytes_back;
   return FVAD_OK;
 }
 
-int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fvad::VadmConst> &K) {
+// sc: null (the segments are kept), or each lane is scored by the shared core
+// as k_sweep_score does it and keeps no segments
+int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fvad::VadmConst> &K, Score *sc) {
   const fvad_sweep_config &c = sw->cfg;
   const size_t B = (size_t)c.n_streams, n = K.size(), nl = B * n;
   std::vector<Lane> lanes(nl);
@@ -275,7 +346,22 @@ int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fva
       const Windows &w = sw->win[s];
       fvad::host_vadm_lane(cfgs[m], c.sample_rate, c.fft_size, c.n_channels, c.n_bands, K[m].slot, w.n(),
                            w.band.data(), w.vad.data(), w.vr.data(), &lanes[l].snap, &lanes[l].segs);
-      if (lanes[l].segs.size() > (size_t)c.seg_capacity) lanes[l].segs.resize((size_t)c.seg_capacity);
+      if (sc) {
+        const std::vector<fvad_segment> &g = lanes[l].segs;
+        if (g.size() > (size_t)c.seg_capacity)
+          sc->status[l] = fvad::kEvalOverCapacity;
+        else
+          sc->status[l] = fvad::eval_lane(
+              [&](size_t i, float *from, float *to) {
+                *from = (float)g[i].sample_from / 48000.0f;
+                *to = (float)g[i].sample_to / 48000.0f;
+              },
+              g.size(), sc->lab.data() + 2 * sc->off[s], (size_t)(sc->off[s + 1] - sc->off[s]),
+              sc->stat[sc->n_stat == 1 ? 0 : m], &sc->single[l]);
+        lanes[l].segs = {};
+      } else if (lanes[l].segs.size() > (size_t)c.seg_capacity) {
+        lanes[l].segs.resize((size_t)c.seg_capacity);
+      }
     }
   };
   const size_t nt = std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)std::thread::hardware_concurrency(), nl}));
@@ -286,6 +372,8 @@ int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fva
   sw->lanes = std::move(lanes);
   sw->n_cfgs = n;
   sw->have_counts = false;
+  sw->kept = !sc;
+  sw->bytes_back = 0;
   return FVAD_OK;
 }
 
@@ -383,7 +471,7 @@ extern "C" int fvad_sweep_run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs,
   std::vector<fvad::VadmConst> K;
   std::vector<fvad::VadmState> s0;
   if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
-  return run_host(sw, cfgs, K);
+  return run_host(sw, cfgs, K, nullptr);
 }
 
 extern "C" int fvad_sweep_run(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs) {
@@ -391,8 +479,73 @@ extern "C" int fvad_sweep_run(fvad_sweep *sw, const fvad_vadm_config *cfgs, size
   std::vector<fvad::VadmConst> K;
   std::vector<fvad::VadmState> s0;
   if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
-  if (sw->cfg.device == -1) return run_host(sw, cfgs, K);
-  return run_device(sw, K, s0);
+  if (sw->cfg.device == -1) return run_host(sw, cfgs, K, nullptr);
+  return run_device(sw, K, s0, nullptr);
+}
+
+extern "C" int fvad_sweep_run_score(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs,
+                                    const float *const *ref_from_to, const size_t *n_ref,
+                                    const fvad_stat_config *stat_cfgs, size_t n_stat_cfgs,
+                                    fvad_aggregate_stats *agg_out, fvad_single_stats *single_out) {
+  // everything that can be refused is refused before anything runs
+  if (const int rc = check_run(sw, cfgs, n_cfgs)) return rc;
+  if (!ref_from_to || !n_ref || !stat_cfgs || !agg_out) return set_error(FVAD_EINVAL, "null argument");
+  if (n_stat_cfgs != 1 && n_stat_cfgs != n_cfgs)
+    return set_error(FVAD_EINVAL, "n_stat_cfgs must be 1 or n_cfgs (" + std::to_string(n_cfgs) + "), not " +
+                                      std::to_string(n_stat_cfgs));
+  const size_t B = (size_t)sw->cfg.n_streams, n = n_cfgs;
+  for (size_t s = 0; s < B; s++)
+    if (n_ref[s] > 0 && !ref_from_to[s]) return set_error(FVAD_EINVAL, "null reference list");
+  std::vector<fvad::VadmConst> K;
+  std::vector<fvad::VadmState> s0;
+  if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
+  Score sc;
+  sc.stat = stat_cfgs;
+  sc.n_stat = n_stat_cfgs;
+  sc.off.resize(B + 1);
+  using Label = std::pair<float, float>;
+  std::vector<Label> one;
+  for (size_t s = 0; s < B; s++) {  // fvad_eval_stats' sort_by_start, once per stream
+    sc.off[s] = (long long)(sc.lab.size() / 2);
+    one.clear();
+    for (size_t j = 0; j < n_ref[s]; j++) one.emplace_back(ref_from_to[s][2 * j], ref_from_to[s][2 * j + 1]);
+    std::stable_sort(one.begin(), one.end(), [](const Label &a, const Label &b) { return a.first < b.first; });
+    for (const auto &r : one) {
+      sc.lab.push_back(r.first);
+      sc.lab.push_back(r.second);
+    }
+  }
+  sc.off[B] = (long long)(sc.lab.size() / 2);
+  sc.single.resize(B * n);
+  sc.status.assign(B * n, fvad::kEvalScored);
+  if (const int rc = sw->cfg.device == -1 ? run_host(sw, cfgs, K, &sc) : run_device(sw, K, s0, &sc)) return rc;
+  // the run stands (counts, snapshots); a lane that could not be scored fails the call
+  for (size_t s = 0; s < B; s++)
+    for (size_t m = 0; m < n; m++) {
+      const std::string where = "stream " + std::to_string(s) + ", config " + std::to_string(m) + ": ";
+      if (sc.status[s * n + m] == fvad::kEvalOverCapacity)
+        return set_error(FVAD_EINVAL, where + std::to_string(sw->lanes[s * n + m].snap.n_segments) +
+                                          " segments exceed seg_capacity, the score would be of a truncated list");
+      if (sc.status[s * n + m] != fvad::kEvalScored)
+        return set_error(FVAD_EINVAL, where + "segment starts are not in non-decreasing order, the lane was not scored");
+    }
+  std::vector<fvad_single_stats> st(B);
+  for (size_t m = 0; m < n; m++) {
+    for (size_t s = 0; s < B; s++) {
+      st[s] = sc.single[s * n + m];
+      if (single_out) single_out[m * B + s] = st[s];
+    }
+    fvad_eval_aggregate(st.data(), B, &agg_out[m]);
+  }
+  return FVAD_OK;
+}
+
+extern "C" int fvad_sweep_last_run(const fvad_sweep *sw, size_t *n_cfgs, int *kept_segments, size_t *bytes_back) {
+  if (!sw) return set_error(FVAD_EINVAL, "null sweep");
+  if (n_cfgs) *n_cfgs = sw->n_cfgs;
+  if (kept_segments) *kept_segments = sw->kept ? 1 : 0;
+  if (bytes_back) *bytes_back = sw->bytes_back;
+  return FVAD_OK;
 }
 
 extern "C" size_t fvad_sweep_segments(const fvad_sweep *sw, int stream, size_t cfg, fvad_segment *out, size_t cap) {
@@ -423,6 +576,8 @@ extern "C" int fvad_sweep_score(const fvad_sweep *sw, const float *const *ref_fr
                                 fvad_single_stats *single_out) {
   if (!sw || !ref_from_to || !n_ref || !stat_cfg || !agg_out) return set_error(FVAD_EINVAL, "null argument");
   if (sw->n_cfgs == 0) return set_error(FVAD_EINVAL, "no run to score");
+  if (!sw->kept)
+    return set_error(FVAD_EINVAL, "the last run (fvad_sweep_run_score) kept no segments: nothing to score");
   const size_t B = (size_t)sw->cfg.n_streams, n = sw->n_cfgs;
   for (size_t s = 0; s < B; s++) {
     if (n_ref[s] > 0 && !ref_from_to[s]) return set_error(FVAD_EINVAL, "null reference list");

@@ -1,5 +1,5 @@
 // Config sweep (include/fvad.h: fvad_sweep_*): many VADMachine configs over
-// recorded window sequences.  The kernel side (fvad_sweep.hip), the host
+// recorded window sequences.  The kernel side (fvad_sweep.hip, fvad_sweep_score.hip), the host
 // pieces it shares with the engine's device machines (fvad_engine.cpp) and
 // with the host VADMachine (fvad_host.cpp).
 #pragma once
@@ -56,5 +56,20 @@ struct SweepArgs {
 constexpr int kSweepBlock = 64;  // windows per walk: a lane re-decides lazy / non-lazy and may settle an owed fold
 hipError_t launch_sweep_min(const SweepArgs &a, hipStream_t stream);
 hipError_t launch_vadm_sweep(const SweepArgs &a, hipStream_t stream);
+
+// k_sweep_score's arguments (fvad_sweep_score.hip): a chunk's lanes as
+// SweepArgs', scored where k_vadm_sweep left them.
+struct ScoreArgs {
+  int n_streams, n_cfgs, seg_cap;  // configs of this chunk
+  const VadmState *st;             // [lane]  n_segs
+  const VadmSeg *seg;              // [lane][seg_cap]
+  const float *lab;                // every stream's labels as (from, to) seconds, each stream's stably sorted by start
+  const long long *lab_off;        // [n_streams + 1] first label of stream s in lab
+  const fvad_stat_config *stat;    // the chunk's first config's; config c reads stat[c * stat_stride]
+  int stat_stride;                 // 0: one for all, 1: one per config
+  fvad_single_stats *single;       // [lane], written where status is kEvalScored (fvad_eval_core.h)
+  unsigned *status;                // [lane] kEvalScored / kEvalOverCapacity / kEvalUnsorted
+};
+hipError_t launch_sweep_score(const ScoreArgs &a, hipStream_t stream);
 
 }  // namespace fvad

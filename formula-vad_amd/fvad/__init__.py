@@ -275,6 +275,10 @@ SYMBOLS = [
     ("fvad_sweep_snapshot", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     ("fvad_sweep_score", C.c_int, [C.c_void_p, C.POINTER(F32P), C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    ("fvad_sweep_run_score", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(F32P), C.POINTER(C.c_size_t),
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("fvad_sweep_last_run", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_size_t)]),
     ("fvad_sweep_bytes", C.c_size_t, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("fvad_sweep_set_debug", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("fvad_sweep_debug_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
@@ -1011,6 +1015,7 @@ class Sweep:
         _check(lib().fvad_sweep_create(C.byref(cfg), C.byref(h)), "fvad_sweep_create")
         self.h = h
         self.B, self.C, self.nb, self.n_cfgs = n_streams, n_channels, len(bands), 0
+        self.kept_segments = True  # the last run kept its segments (run_score does not)
 
     @staticmethod
     def _cfgs(cfgs):
@@ -1039,17 +1044,18 @@ class Sweep:
     def run(self, cfgs):
         arr, n = self._cfgs(cfgs)
         _check(lib().fvad_sweep_run(self.h, arr, n), "fvad_sweep_run")
-        self.n_cfgs = n
+        self.n_cfgs, self.kept_segments = n, True
 
     def run_host(self, cfgs):
         arr, n = self._cfgs(cfgs)
         _check(lib().fvad_sweep_run_host(self.h, arr, n), "fvad_sweep_run_host")
-        self.n_cfgs = n
+        self.n_cfgs, self.kept_segments = n, True
 
     def segments(self, stream, cfg):
-        """(total, the first min(total, seg_capacity) segments as tuples)."""
+        """(total, the first min(total, seg_capacity) segments as tuples); after a
+        run_score, which keeps no segments, (total, [])."""
         n = lib().fvad_sweep_segments(self.h, stream, cfg, None, 0)
-        k = min(n, self.cfg.seg_capacity)
+        k = min(n, self.cfg.seg_capacity) if self.kept_segments else 0
         buf = (Segment * max(1, k))()
         lib().fvad_sweep_segments(self.h, stream, cfg, buf, k)
         return n, [(s.sample_from, s.sample_to, s.debug_rnn_vad, s.debug_avg_speech_vol_ratio) for s in buf[:k]]
@@ -1077,10 +1083,42 @@ class Sweep:
         agg = (AggregateStats * max(1, self.n_cfgs))()
         one = (SingleStats * max(1, self.n_cfgs * self.B))() if single else None
         _check(lib().fvad_sweep_score(self.h, ptrs, lens, C.byref(sc), agg, one), "fvad_sweep_score")
-        if not single:
+        return self._scores(agg, one)
+
+    def _scores(self, agg, one):
+        if one is None:
             return list(agg[:self.n_cfgs])
         return list(agg[:self.n_cfgs]), [[{n: getattr(one[m * self.B + s], n) for n in _STAT_FIELDS}
                                           for s in range(self.B)] for m in range(self.n_cfgs)]
+
+    def run_score(self, cfgs, refs, stat=None, single=False):
+        """run(cfgs) and score(refs) in one call (fvad_sweep_run_score): the lanes are
+        scored where they ran and the segments are not kept.  stat: a dict of
+        StatConfig's four fields for every config, or a list of len(cfgs) such
+        dicts (config m is scored with stat[m]); None: all zeros.  Returns what
+        score returns."""
+        arr, n = self._cfgs(cfgs)
+        arrs = [np.ascontiguousarray(np.asarray(r, np.float32).reshape(-1, 2)) for r in refs]
+        assert len(arrs) == self.B, "one reference list per stream"
+        ptrs = (F32P * self.B)(*[fptr(a) for a in arrs])
+        lens = (C.c_size_t * self.B)(*[len(a) for a in arrs])
+        stats = [stat or {}] if stat is None or isinstance(stat, dict) else list(stat)
+        sc = (StatConfig * max(1, len(stats)))(*[StatConfig(**d) for d in stats])
+        agg = (AggregateStats * max(1, n))()
+        one = (SingleStats * max(1, n * self.B))() if single else None
+        try:
+            _check(lib().fvad_sweep_run_score(self.h, arr, n, ptrs, lens, sc, len(stats), agg, one),
+                   "fvad_sweep_run_score")
+        finally:  # a call refused before it ran leaves the previous run; a lane over capacity leaves this one
+            last = self.last_run()
+            self.n_cfgs, self.kept_segments = last["n_cfgs"], last["kept_segments"]
+        return self._scores(agg, one)
+
+    def last_run(self):
+        """The last run: its configs, whether its segments were kept, the bytes copied back from the device."""
+        n, kept, back = C.c_size_t(), C.c_int(), C.c_size_t()
+        _check(lib().fvad_sweep_last_run(self.h, C.byref(n), C.byref(kept), C.byref(back)), "fvad_sweep_last_run")
+        return {"n_cfgs": n.value, "kept_segments": bool(kept.value), "bytes_back": back.value}
 
     def bytes(self, cfgs):
         """Device bytes the machines of these configs need in one chunk (fvad_sweep_bytes)."""

@@ -678,6 +678,38 @@ int fvad_sweep_snapshot(const fvad_sweep *sw, int stream, size_t cfg, fvad_vadm_
  * FVAD_EINVAL naming it. */
 int fvad_sweep_score(const fvad_sweep *sw, const float *const *ref_from_to, const size_t *n_ref,
                      const fvad_stat_config *stat_cfg, fvad_aggregate_stats *agg_out, fvad_single_stats *single_out);
+/* fvad_sweep_run followed by fvad_sweep_score, for a tuning loop that wants a
+ * score per config and not the segments: on a device sweep each lane is scored
+ * on the GPU where k_vadm_sweep left its segments (k_sweep_score, the
+ * evaluator's order of operations: fvad_eval_stats' bits, NaN for NaN), and
+ * the statistics come back instead of the segments; a host-only sweep scores
+ * with the same code on the host.  agg_out [cfg], single_out (nullable)
+ * [cfg][stream], as fvad_sweep_score's.  What differs:
+ *  - n_stat_cfgs is 1 (stat_cfgs[0] for every config) or n_cfgs (config m is
+ *    scored with stat_cfgs[m], e.g. ignore_shorter_than_sec =
+ *    min_vad_duration_sec of that machine, as the simulator scores).
+ *  - The segments are not kept: afterwards fvad_sweep_counts, _snapshot and
+ *    _debug_counts describe this run, fvad_sweep_segments returns the lane's
+ *    total and copies nothing, and fvad_sweep_score returns FVAD_EINVAL until
+ *    the next fvad_sweep_run / _run_host.
+ *  - Null arguments, a null label list with n_ref[s] > 0, n_stat_cfgs not in
+ *    {1, n_cfgs} and a config whose speech band is none of the sweep's give
+ *    FVAD_EINVAL before anything runs: the previous run's results stay.  A
+ *    lane whose total exceeds seg_capacity shows only after the run:
+ *    FVAD_EINVAL naming the first such (stream, config) in fvad_sweep_score's
+ *    order, agg_out / single_out unspecified, counts and snapshots valid.
+ * Measured (MI355X, 64 streams x 20 000 windows x 1 024 configs at
+ * seg_capacity 136, tools/sweep_score_times.py, profiles/sweep_score_times.json,
+ * wall clock around the calls, interleaved in one process): 94.8 ms against
+ * 1 203.9 ms for fvad_sweep_run + fvad_sweep_score, 13.6 MB copied back
+ * against 224.4 MB, the same aggregates by their bits. */
+int fvad_sweep_run_score(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs,
+                         const float *const *ref_from_to, const size_t *n_ref, const fvad_stat_config *stat_cfgs,
+                         size_t n_stat_cfgs, fvad_aggregate_stats *agg_out, fvad_single_stats *single_out);
+/* The last run (each pointer nullable): its configs (0 before any), whether
+ * its segments were kept (fvad_sweep_run_score: 0), and the bytes it copied
+ * back from the device (0 for a host run). */
+int fvad_sweep_last_run(const fvad_sweep *sw, size_t *n_cfgs, int *kept_segments, size_t *bytes_back);
 /* Device memory the machines of a run need when all configs run in one chunk
  * (buffers, states, segments, constants; the recorded windows come on top:
  * (n_channels * n_bands + n_bands + 2) floats each); 0 on invalid arguments. */
