@@ -17,8 +17,8 @@
 #include "fvad_internal.h"
 #include "fvad_kernels.h"
 #include "fvad_lifecycle.h"
+#include "fvad_machine.h"
 #include "fvad_staged.h"
-#include "fvad_sweep.h"
 
 #define HIP_TRY(expr)                                                                                             \
   do {                                                                                                            \

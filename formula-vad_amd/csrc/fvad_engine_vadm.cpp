@@ -168,72 +168,6 @@ int fvad::eng::collect_vadm_timing(fvad_engine *e) {
 // Device VADMachines (VADMachine.zig:126-230 on the GPU)
 // ---------------------------------------------------------------------------
 namespace {
-// RollingAverage(count, init) initial state (RollingAverage.zig:16-32)
-double initial_avg(size_t n, double init) {
-  double a = 0.0;
-  const double scalar = 1.0 / (double)n;
-  for (size_t i = 0; i < n; i++) a += init * scalar;
-  return a;
-}
-}  // namespace
-
-void fvad::vadm_fill_const(const fvad_vadm_config &c, int sample_rate, int fft_size, VadmConst *Kp, VadmState *s0p,
-                           int *lo, int *hi) {
-  const float sr = (float)sample_rate;
-  const float eval_per_sec = sr / (float)fft_size;
-  auto len_of = [&](float sec) { return std::max<size_t>(1, (size_t)(eval_per_sec * sec)); };
-  auto freq_to_bin = [&](float f) { return (int)std::round(f / (sr / (float)fft_size)); };
-  VadmConst &K = *Kp;
-  K = VadmConst{};
-  *lo = freq_to_bin(c.speech_min_freq);
-  *hi = freq_to_bin(c.speech_max_freq);
-  K.n_lt = (int)len_of(c.long_term_speech_avg_sec);
-  K.n_st = (int)len_of(c.short_term_speech_avg_sec);
-  K.n_r = (int)len_of(c.channel_vol_ratio_avg_sec);
-  K.min_open = (unsigned long long)(size_t)(sr * c.min_consecutive_sec_to_open);
-  K.max_gap = (unsigned long long)(size_t)(sr * c.max_speech_gap_sec);
-  K.rec_pad = (unsigned long long)(sr * 2);
-  K.thr_factor = c.speech_threshold_factor;
-  K.ratio_thr = c.channel_vol_ratio_threshold;
-  K.min_dur = c.min_vad_duration_sec;
-  K.sr = sr;
-  K.has_init = c.has_initial_long_term_avg != 0;
-  K.init = c.initial_long_term_avg;
-  VadmState s0{};
-  if (K.has_init) {
-    // RollingAverage(initial_avg): data = init (a double, VADMachine.zig:89-94)
-    s0.lt_count = (unsigned)K.n_lt;
-    s0.lt_last = initial_avg((size_t)K.n_lt, K.init);
-    s0.lt_has = 1;
-    s0.lt_pre_ok = 1;  // next write is at 0: the next pass starts from 0.0
-    s0.lt_pre = 0.0;
-  }
-  *s0p = s0;
-}
-
-void fvad::vadm_snapshot_of(const VadmState &st, fvad_vadm_snapshot *out) {
-  std::memset(out, 0, sizeof(*out));
-  out->speech_state = st.state;
-  out->speech_start = st.speech_start;
-  out->speech_end = st.speech_end;
-  out->windows = st.windows_done;
-  out->avg[0] = st.lt_last;
-  out->avg[1] = st.st_last;
-  out->avg[2] = st.r_last;
-  out->write_idx[0] = st.lt_widx;
-  out->write_idx[1] = st.st_widx;
-  out->write_idx[2] = st.r_widx;
-  out->written[0] = st.lt_count;
-  out->written[1] = st.st_count;
-  out->written[2] = st.r_count;
-  out->speech_rnn_vad = st.rnn_vad;
-  out->speech_vol_ratio = st.vol_ratio;
-  out->speech_rnn_vad_count = st.rnn_vad_count;
-  out->speech_vol_ratio_count = st.vol_ratio_count;
-  out->n_segments = st.n_segs;
-}
-
-namespace {
 // a fresh machine's state and rolling buffers into the device arrays of v
 int vadm_upload(const fvad_engine *e, const fvad::VadmArgs &v, const std::vector<fvad::VadmState> &init,
                 size_t buf_len) {
@@ -280,23 +214,18 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   long long off = 0;
   std::vector<fvad::VadmState> init((size_t)n * B);
   for (int m = 0; m < n; m++) {
-    fvad::VadmConst &K = v.c[m];
-    fvad::VadmState s0;
-    int lo, hi;
-    fvad::vadm_fill_const(cfgs[m], e->cfg.sample_rate, e->cfg.fft_size, &K, &s0, &lo, &hi);
-    K.slot = -1;
-    for (int b = 0; b < e->cfg.n_bands; b++)
-      if (e->cfg.band_lo[b] == lo && e->cfg.band_hi[b] == hi) K.slot = b;
+    const fvad::VadmDerived d = fvad::vadm_derive(cfgs[m], e->cfg.sample_rate, e->cfg.fft_size);
+    fvad::VadmConst &K = v.c[m] = d.K;
+    K.slot = fvad::band_slot(e->cfg.band_lo, e->cfg.band_hi, e->cfg.n_bands, d.lo, d.hi);
     if (K.slot < 0) return fail(FVAD_EINVAL, "no engine band matches the machine's speech band");
-    K.lt_pitch = (K.n_lt + 3) & ~3;  // 16-byte rows
-    off = (off + 3) & ~3LL;
+    off = (off + 3) & ~3LL;  // (the long-term rows start 16-byte aligned)
     K.lt_off = off;
     off += (long long)K.lt_pitch * B;
     K.st_off = off;
     off += (long long)K.n_st * B;
     K.r_off = off;
     off += (long long)K.n_r * B;
-    for (int s = 0; s < B; s++) init[(size_t)m * B + s] = s0;
+    for (int s = 0; s < B; s++) init[(size_t)m * B + s] = d.s0;
   }
   fvad::dev_ptr<fvad::VadmState> st;
   fvad::dev_ptr<float> buf;
@@ -373,18 +302,11 @@ extern "C" size_t fvad_engine_segments_range(fvad_engine *e, int stream, int mac
   if (hipMemcpy(&st, e->vadm.st + idx, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return 0;
   const size_t n = std::min<size_t>(st.n_segs, (size_t)e->vadm.seg_cap);
   const size_t k = first < n ? std::min(n - first, cap) : 0;
-  if (out && k) {
-    std::vector<fvad::VadmSeg> tmp(k);
-    if (hipMemcpy(tmp.data(), e->vadm.seg + idx * e->vadm.seg_cap + first, k * sizeof(fvad::VadmSeg),
-                  hipMemcpyDeviceToHost) != hipSuccess)
-      return 0;
-    for (size_t i = 0; i < k; i++) {
-      out[i].sample_from = tmp[i].sample_from;
-      out[i].sample_to = tmp[i].sample_to;
-      out[i].debug_rnn_vad = tmp[i].debug_rnn_vad;
-      out[i].debug_avg_speech_vol_ratio = tmp[i].debug_avg_speech_vol_ratio;
-    }
-  }
+  // (a VadmSeg is an fvad_segment: fvad_machine.h)
+  if (out && k &&
+      hipMemcpy(out, e->vadm.seg + idx * e->vadm.seg_cap + first, k * sizeof(fvad_segment), hipMemcpyDeviceToHost) !=
+          hipSuccess)
+    return 0;
   return st.n_segs;
 }
 

@@ -1,297 +1,45 @@
 // Host mirror of the reference's pipeline-side API, above the C ABI:
-//   RollingAverage            (structures/RollingAverage.zig:1-56)
-//   VADMachine                (AudioPipeline/VADMachine.zig:18-310)
 //   AudioPipeline.pushSamples (AudioPipeline.zig:86-120) + VAD frame dispatch
 //                             (VAD.zig:214-251) on a 1-stream engine
 //   multi-stream simulator core (replaces simulator.zig:217-228's thread per
 //                             instance with a lock-step tick loop per GPU)
-//   Evaluator / statistics / formats (Evaluator.zig:90-156,
-//                             Evaluator/statistics.zig:85-284, formats.zig:7-36)
-// The per-frame DSP runs on the GPU (fvad_engine_*); what stays here is the
-// per-window decision logic (cheap: 23.4 windows/s/stream) and the judge.
+// The per-frame DSP and the VADMachines run on the GPU (fvad_engine_*); what
+// stays here is feeding the engines and reading their segments.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
-#include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/fvad.h"
 #include "fvad_internal.h"
-#include "fvad_sweep.h"
+#include "fvad_machine.h"
 
 namespace {
 
 constexpr int kPipelineSegCap = 1 << 16;  // device segment slots per machine (one stream)
 constexpr int kMultiSegCap = 1024;        // per stream and machine in the multi-stream core
 
-// ---------------- RollingAverage ----------------
-struct RollingAverage {
-  std::vector<double> data;
-  bool has_last = false;
-  double last_avg = 0;
-  size_t write_idx = 0, written_count = 0;
-  RollingAverage(size_t count, bool has_init, double init) : data(count, 0.0) {
-    if (has_init) {
-      for (size_t i = 0; i < count; i++) data[i] = init;
-      written_count = count;
-      avg();
-    }
-  }
-  double avg() {
-    double a = 0.0;
-    const double scalar = 1.0 / (double)written_count;
-    for (size_t i = 0; i < written_count; i++) a += data[i] * scalar;
-    last_avg = a;
-    has_last = true;
-    return a;
-  }
-  double push(float sample) {
-    data[write_idx] = (double)sample;
-    write_idx = (write_idx + 1) % data.size();
-    if (written_count < data.size()) written_count++;
-    return avg();
-  }
-};
-
-size_t freq_to_bin(int sample_rate, int nfft, float freq) {
-  const float bin_width = (float)sample_rate / (float)nfft;
-  return (size_t)std::round(freq / bin_width);  // Zig @round: half away from zero
+// the machines of a VAD config, the main one first
+std::vector<fvad_vadm_config> machine_configs(const fvad_vad_config &vc) {
+  std::vector<fvad_vadm_config> cfgs(1, vc.vad_machine_config);
+  cfgs.insert(cfgs.end(), vc.alt_vad_machine_configs, vc.alt_vad_machine_configs + vc.n_alt);
+  return cfgs;
 }
-
-// ---------------- VADMachine ----------------
-struct VADMachine {
-  enum State { kClosed, kOpening, kOpen, kClosing };
-  fvad_vadm_config cfg;
-  int sample_rate, fft_size;
-  State state = kClosed;
-  RollingAverage long_term, short_term, ratio;
-  uint64_t speech_start = 0, speech_end = 0;
-  float rnn_vad = 0;
-  size_t rnn_vad_count = 0;
-  float vol_ratio = 0;
-  size_t vol_ratio_count = 0;
-  std::vector<fvad_segment> segments;
-  int band_slot = 0;  // which engine band this machine reads
-  size_t min_bin, max_bin;
-
-  static size_t len_of(float eval_per_sec, float sec) { return (size_t)(eval_per_sec * sec); }
-  VADMachine(const fvad_vadm_config &c, int sr, int fft)
-      : cfg(c),
-        sample_rate(sr),
-        fft_size(fft),
-        long_term(std::max<size_t>(1, len_of((float)sr / (float)fft, c.long_term_speech_avg_sec)),
-                  c.has_initial_long_term_avg != 0, c.initial_long_term_avg),
-        short_term(std::max<size_t>(1, len_of((float)sr / (float)fft, c.short_term_speech_avg_sec)), false, 0),
-        ratio(std::max<size_t>(1, len_of((float)sr / (float)fft, c.channel_vol_ratio_avg_sec)), false, 0) {
-    segments.reserve(100);
-    min_bin = freq_to_bin(sr, fft, c.speech_min_freq);
-    max_bin = freq_to_bin(sr, fft, c.speech_max_freq);
-  }
-  uint64_t rec_start(uint64_t from) const {
-    const uint64_t sb = (uint64_t)((float)sample_rate * 2);
-    return sb > from ? 0 : from - sb;
-  }
-  uint64_t rec_end(uint64_t to) const { return to + (uint64_t)((float)sample_rate * 2); }
-  void track(float vad, float vr, State from, State to) {
-    if (from == kClosed && to == kOpening) {
-      rnn_vad = vad;
-      rnn_vad_count = 1;
-      vol_ratio = vr;
-      vol_ratio_count = 1;
-    } else if (from == kOpening || from == kOpen) {
-      rnn_vad += vad;
-      rnn_vad_count += 1;
-      vol_ratio += vr;
-      vol_ratio_count += 1;
-    }
-  }
-  void on_speech_end() {
-    const uint64_t len = speech_end - speech_start;
-    const float len_rt = (float)len / (float)sample_rate;
-    if (len_rt >= cfg.min_vad_duration_sec) {
-      fvad_segment s;
-      s.sample_from = rec_start(speech_start);
-      s.sample_to = rec_end(speech_end);
-      s.debug_rnn_vad = rnn_vad / (float)rnn_vad_count;
-      s.debug_avg_speech_vol_ratio = vol_ratio / (float)vol_ratio_count;
-      segments.push_back(s);
-    }
-  }
-  // VADMachine.run: channel band sums of this window, window vad (has_vad) and ratio
-  void run(uint64_t index, const float *band_per_channel, int n_ch, int band_stride, float vad, float vr) {
-    float min_v = 999, max_v = 0;
-    for (int c = 0; c < n_ch; c++) {
-      const float v = band_per_channel[c * band_stride];
-      if (v < min_v) min_v = v;
-      if (v > max_v) max_v = v;
-    }
-    const float sr = (float)sample_rate;
-    const size_t min_open = (size_t)(sr * cfg.min_consecutive_sec_to_open);
-    const size_t max_gap = (size_t)(sr * cfg.max_speech_gap_sec);
-    const double st_avg = short_term.push(min_v);
-    const double r_avg = ratio.push(vr);
-    double base;
-    if (long_term.has_last)
-      base = long_term.last_avg;
-    else if (cfg.has_initial_long_term_avg)
-      base = cfg.initial_long_term_avg;
-    else
-      base = st_avg;
-    const double threshold = base * (double)cfg.speech_threshold_factor;
-    const bool met = st_avg > threshold && r_avg > (double)cfg.channel_vol_ratio_threshold;
-    if (!met) long_term.push(min_v);
-    switch (state) {
-      case kClosed:
-        if (met) {
-          state = kOpening;
-          speech_start = index;
-        }
-        track(vad, vr, kClosed, state);
-        break;
-      case kOpening:
-        if (met && index - speech_start >= min_open)
-          state = kOpen;
-        else if (!met)
-          state = kClosed;
-        track(vad, vr, kOpening, state);
-        break;
-      case kOpen:
-        if (!met) {
-          state = kClosing;
-          speech_end = index;
-        }
-        track(vad, vr, kOpen, state);
-        break;
-      case kClosing:
-        if (met)
-          state = kOpen;
-        else if (index - speech_end >= max_gap) {
-          state = kClosed;
-          on_speech_end();
-        }
-        track(vad, vr, kClosing, state);
-        break;
-    }
-  }
-};
 
 // Engine band slots for a set of machine configs (unique bin ranges).
-int assign_bands(std::vector<VADMachine> &ms, fvad_engine_config &ec) {
+int assign_bands(const std::vector<fvad_vadm_config> &cfgs, fvad_engine_config &ec) {
   ec.n_bands = 0;
-  for (auto &m : ms) {
-    int slot = -1;
-    for (int b = 0; b < ec.n_bands; b++)
-      if (ec.band_lo[b] == (int)m.min_bin && ec.band_hi[b] == (int)m.max_bin) slot = b;
-    if (slot < 0) {
-      if (ec.n_bands == FVAD_MAX_BANDS) return FVAD_EINVAL;
-      slot = ec.n_bands++;
-      ec.band_lo[slot] = (int)m.min_bin;
-      ec.band_hi[slot] = (int)m.max_bin;
-    }
-    m.band_slot = slot;
+  for (const fvad_vadm_config &c : cfgs) {
+    const fvad::VadmDerived d = fvad::vadm_derive(c, ec.sample_rate, ec.fft_size);
+    if (fvad::band_slot(ec.band_lo, ec.band_hi, ec.n_bands, d.lo, d.hi) >= 0) continue;
+    if (ec.n_bands == FVAD_MAX_BANDS) return FVAD_EINVAL;
+    ec.band_lo[ec.n_bands] = d.lo;
+    ec.band_hi[ec.n_bands++] = d.hi;
   }
   return FVAD_OK;
 }
 
-}  // namespace
-
-extern "C" void fvad_vadm_config_default(fvad_vadm_config *c) {
-  c->speech_min_freq = 100;
-  c->speech_max_freq = 1500;
-  c->long_term_speech_avg_sec = 180;
-  c->has_initial_long_term_avg = 1;
-  c->initial_long_term_avg = 0.005;
-  c->short_term_speech_avg_sec = 0.2f;
-  c->speech_threshold_factor = 18;
-  c->channel_vol_ratio_avg_sec = 0.5f;
-  c->channel_vol_ratio_threshold = 0.5f;
-  c->min_consecutive_sec_to_open = 0.2f;
-  c->max_speech_gap_sec = 2;
-  c->min_vad_duration_sec = 0.7f;
-}
-
-// The sweep's host path (fvad_sweep.cpp): one fresh machine over a recorded
-// window sequence, its final state in the device snapshot's terms.
-void fvad::host_vadm_lane(const fvad_vadm_config &c, int sample_rate, int fft_size, int n_channels, int n_bands,
-                          int slot, size_t n_windows, const float *band, const float *vad, const float *vol_ratio,
-                          fvad_vadm_snapshot *snap, std::vector<fvad_segment> *segs) {
-  VADMachine m(c, sample_rate, fft_size);
-  for (size_t w = 0; w < n_windows; w++)
-    m.run((uint64_t)w * (uint64_t)fft_size, band + w * (size_t)n_channels * n_bands + slot, n_channels, n_bands,
-          vad[w], vol_ratio[w]);
-  if (snap) {
-    std::memset(snap, 0, sizeof(*snap));
-    snap->speech_state = (int)m.state;
-    snap->speech_start = m.speech_start;
-    snap->speech_end = m.speech_end;
-    snap->windows = n_windows;
-    const RollingAverage *ra[3] = {&m.long_term, &m.short_term, &m.ratio};
-    for (int k = 0; k < 3; k++) {
-      snap->avg[k] = ra[k]->last_avg;
-      snap->write_idx[k] = ra[k]->write_idx;
-      snap->written[k] = ra[k]->written_count;
-    }
-    snap->speech_rnn_vad = m.rnn_vad;
-    snap->speech_vol_ratio = m.vol_ratio;
-    snap->speech_rnn_vad_count = m.rnn_vad_count;
-    snap->speech_vol_ratio_count = m.vol_ratio_count;
-    snap->n_segments = m.segments.size();
-  }
-  if (segs) *segs = std::move(m.segments);
-}
-
-// ---------------------------------------------------------------------------
-// Standalone VADMachine (host decision logic; testable without a GPU)
-// ---------------------------------------------------------------------------
-struct fvad_vadm {
-  VADMachine m;
-  int n_channels;
-  fvad_vadm(const fvad_vadm_config &c, int sr, int fft, int ch) : m(c, sr, fft), n_channels(ch) {}
-};
-
-extern "C" int fvad_vadm_create(const fvad_vadm_config *cfg, int sample_rate, int fft_size, int n_channels,
-                                fvad_vadm **out) {
-  if (!out || n_channels < 1 || fft_size <= 0 || sample_rate <= 0) return FVAD_EINVAL;
-  fvad_vadm_config def;
-  fvad_vadm_config_default(&def);
-  *out = new fvad_vadm(cfg ? *cfg : def, sample_rate, fft_size, n_channels);
-  return FVAD_OK;
-}
-
-extern "C" void fvad_vadm_destroy(fvad_vadm *v) { delete v; }
-
-extern "C" void fvad_vadm_bins(const fvad_vadm *v, int *lo, int *hi) {
-  if (lo) *lo = (int)v->m.min_bin;
-  if (hi) *hi = (int)v->m.max_bin;
-}
-
-extern "C" int fvad_vadm_run(fvad_vadm *v, uint64_t index, const float *band_per_channel, float vad,
-                             float vol_ratio) {
-  if (!v || !band_per_channel) return FVAD_EINVAL;
-  v->m.run(index, band_per_channel, v->n_channels, 1, vad, vol_ratio);
-  return FVAD_OK;
-}
-
-extern "C" size_t fvad_vadm_segments(const fvad_vadm *v, fvad_segment *out, size_t cap) {
-  const auto &segs = v->m.segments;
-  for (size_t i = 0; i < segs.size() && i < cap; i++) out[i] = segs[i];
-  return segs.size();
-}
-
-extern "C" int fvad_vadm_state(const fvad_vadm *v, int *speech_state, uint64_t *speech_start, uint64_t *speech_end) {
-  if (!v) return FVAD_EINVAL;
-  if (speech_state) *speech_state = (int)v->m.state;
-  if (speech_start) *speech_start = v->m.speech_start;
-  if (speech_end) *speech_end = v->m.speech_end;
-  return FVAD_OK;
-}
-
-namespace {
-struct StreamMachines {
-  std::vector<VADMachine> machines;  // [0] = main; they run on the device (k_vadm_hbm)
-};
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -301,7 +49,7 @@ struct fvad_pipeline {
   int n_channels;
   fvad_engine *engine = nullptr;
   fvad_engine_config ec;
-  StreamMachines sm;
+  size_t n_machines = 0;  // [0] = main; they run on the device (k_vadm_hbm)
   std::vector<std::vector<float>> pending;  // samples not yet forming a full 480 frame
   uint64_t total_write_count = 0;
   std::vector<float> pcm;
@@ -354,21 +102,17 @@ extern "C" int fvad_pipeline_create_ex(int sample_rate, int n_channels, const fv
   if (sample_rate != 48000) return FVAD_ERATE;
   fvad_pipeline *p = new fvad_pipeline();
   p->n_channels = n_channels;
-  p->sm.machines.emplace_back(vc->vad_machine_config, sample_rate, vc->fft_size);
-  for (int i = 0; i < vc->n_alt; i++) p->sm.machines.emplace_back(vc->alt_vad_machine_configs[i], sample_rate, vc->fft_size);
+  const std::vector<fvad_vadm_config> cfgs = machine_configs(*vc);
+  p->n_machines = cfgs.size();
   fvad_engine_config_default(&p->ec, 1, n_channels);
   p->ec.device = device;
   p->ec.max_ticks = 100;
   p->ec.fft_size = vc->fft_size;
   p->ec.use_denoiser = vc->use_denoiser;
-  int rc = assign_bands(p->sm.machines, p->ec);
+  int rc = assign_bands(cfgs, p->ec);
   if (!rc) rc = fvad_engine_create(&p->ec, model, &p->engine);
-  if (!rc) {
-    // the machines run on the device after every push (k_vadm_hbm)
-    std::vector<fvad_vadm_config> cfgs;
-    for (auto &m : p->sm.machines) cfgs.push_back(m.cfg);
-    rc = fvad_engine_attach_vadm(p->engine, cfgs.data(), (int)cfgs.size(), kPipelineSegCap);
-  }
+  // the machines run on the device after every push (k_vadm_hbm)
+  if (!rc) rc = fvad_engine_attach_vadm(p->engine, cfgs.data(), (int)cfgs.size(), kPipelineSegCap);
   if (rc) {
     if (p->engine) fvad_engine_destroy(p->engine);
     delete p;
@@ -483,7 +227,7 @@ extern "C" int fvad_pipeline_push(fvad_pipeline *p, const float *const *pcm, siz
 
 extern "C" size_t fvad_pipeline_segments(const fvad_pipeline *p, int alt, fvad_segment *out, size_t cap) {
   const size_t idx = alt < 0 ? 0 : (size_t)alt + 1;
-  if (!p || idx >= p->sm.machines.size()) return 0;
+  if (!p || idx >= p->n_machines) return 0;
   return fvad_engine_segments(p->engine, 0, (int)idx, out, cap);
 }
 
@@ -522,11 +266,7 @@ extern "C" int fvad_multi_create_ex(int n_streams, const int *n_channels, const 
   m->n_machines = 1 + vc->n_alt;
   m->channels.assign(n_channels, n_channels + n_streams);
   m->where.assign(n_streams, {-1, -1});
-  std::vector<VADMachine> ms;
-  ms.emplace_back(vc->vad_machine_config, 48000, vc->fft_size);
-  for (int i = 0; i < vc->n_alt; i++) ms.emplace_back(vc->alt_vad_machine_configs[i], 48000, vc->fft_size);
-  std::vector<fvad_vadm_config> cfgs;
-  for (auto &x : ms) cfgs.push_back(x.cfg);
+  const std::vector<fvad_vadm_config> cfgs = machine_configs(*vc);
   std::vector<int> groups(m->channels);
   std::sort(groups.begin(), groups.end());
   groups.erase(std::unique(groups.begin(), groups.end()), groups.end());
@@ -546,7 +286,7 @@ extern "C" int fvad_multi_create_ex(int n_streams, const int *n_channels, const 
       p.ec.max_ticks = ticks_per_push;
       p.ec.fft_size = vc->fft_size;
       p.ec.use_denoiser = vc->use_denoiser;
-      int rc = assign_bands(ms, p.ec);
+      int rc = assign_bands(cfgs, p.ec);
       if (!rc) rc = fvad_engine_create(&p.ec, model, &p.engine);
       if (!rc) rc = fvad_engine_attach_vadm(p.engine, cfgs.data(), (int)cfgs.size(), kMultiSegCap);
       if (rc) {
@@ -689,153 +429,3 @@ extern "C" size_t fvad_multi_segments(const fvad_multi *m, int stream, fvad_segm
   return fvad_multi_segments_alt(m, stream, 0, out, cap);
 }
 
-// ---------------------------------------------------------------------------
-// Evaluator / statistics / formats
-// ---------------------------------------------------------------------------
-namespace {
-struct Seg {
-  float from, to;
-  std::vector<size_t> opp;
-};
-float overlap_with(float af, float at, float bf, float bt) {
-  const float max_from = af > bf ? af : bf;
-  const float min_to = at < bt ? at : bt;
-  return min_to - max_from;
-}
-void sort_by_start(std::vector<Seg> &v) {
-  std::stable_sort(v.begin(), v.end(), [](const Seg &a, const Seg &b) { return a.from < b.from; });
-}
-float false_positive(const Seg &v, const std::vector<Seg> &refs, const fvad_stat_config &c) {
-  // extrudeSegments (statistics.zig:191-218) + calcOverlapMany
-  const size_t n = v.opp.size();
-  std::vector<float> f(n), t(n);
-  for (size_t i = 0; i < n; i++) {
-    f[i] = refs[v.opp[i]].from;
-    t[i] = refs[v.opp[i]].to;
-  }
-  if (n > 0) {
-    f[0] -= c.extrude_start;
-    t[n - 1] += c.extrude_end;
-    for (size_t i = 0; i + 1 < n; i++)
-      if (f[i + 1] - t[i] <= c.fill_gaps) t[i] = f[i + 1];
-  }
-  float ov = 0.0f;
-  for (size_t i = 0; i < n; i++) {
-    const float o = overlap_with(v.from, v.to, f[i], t[i]);
-    ov += 0.0f > o ? 0.0f : o;
-  }
-  return (v.to - v.from) - ov;
-}
-float f_score(float beta, float p, float r) {
-  const float b2 = beta * beta;  // std.math.pow(f32, beta, 2)
-  return (1 + b2) * (p * r) / (b2 * p + r);
-}
-}  // namespace
-
-extern "C" int fvad_eval_stats(const float *vad, size_t nv, const float *ref, size_t nr, const fvad_stat_config *cfg,
-                               fvad_single_stats *out) {
-  if ((!vad && nv) || (!ref && nr) || !cfg || !out) return FVAD_EINVAL;
-  std::vector<Seg> vs(nv), rs(nr);
-  for (size_t i = 0; i < nv; i++) vs[i] = {vad[2 * i], vad[2 * i + 1], {}};
-  for (size_t i = 0; i < nr; i++) rs[i] = {ref[2 * i], ref[2 * i + 1], {}};
-  sort_by_start(vs);
-  sort_by_start(rs);
-  for (auto &v : vs)
-    for (size_t j = 0; j < rs.size(); j++)
-      if (overlap_with(v.from, v.to, rs[j].from, rs[j].to) > 0.0f) v.opp.push_back(j);
-  for (auto &r : rs)
-    for (size_t j = 0; j < vs.size(); j++)
-      if (overlap_with(r.from, r.to, vs[j].from, vs[j].to) > 0.0f) r.opp.push_back(j);
-  fvad_single_stats s;
-  std::memset(&s, 0, sizeof(s));
-  for (const auto &v : vs) {
-    s.false_positives_sec += false_positive(v, rs, *cfg);
-    const float tp = (v.to - v.from) - false_positive(v, rs, *cfg);
-    s.true_positives_sec += tp;
-    s.total_positives_sec += tp;
-  }
-  for (const auto &r : rs) {
-    if ((r.to - r.from) < cfg->ignore_shorter_than_sec) continue;
-    float ov = 0.0f;
-    for (size_t j : r.opp) {
-      const float o = overlap_with(r.from, r.to, vs[j].from, vs[j].to);
-      ov += 0.0f > o ? 0.0f : o;
-    }
-    const float fn = (r.to - r.from) - ov;
-    s.false_negatives_sec += fn;
-    s.total_positives_sec += fn;
-  }
-  s.true_positive_rate = s.true_positives_sec / s.total_positives_sec;
-  s.false_negative_rate = s.false_negatives_sec / s.total_positives_sec;
-  s.false_discovery_rate = s.false_positives_sec / (s.false_positives_sec + s.true_positives_sec);
-  s.precision = s.true_positives_sec / (s.true_positives_sec + s.false_positives_sec);
-  s.f_score_beta = 0.7f;
-  s.f_score = f_score(s.f_score_beta, s.precision, s.true_positive_rate);
-  s.fm_index = std::sqrt(s.precision * s.true_positive_rate);
-  *out = s;
-  return FVAD_OK;
-}
-
-extern "C" void fvad_eval_aggregate(const fvad_single_stats *st, size_t n, fvad_aggregate_stats *a) {
-  std::memset(a, 0, sizeof(*a));
-  fvad_agg_stat *aggs[4] = {&a->true_positive_rate, &a->false_negative_rate, &a->false_discovery_rate, &a->precision};
-  for (auto *x : aggs) {
-    x->min = 2;
-    x->max = -2;
-  }
-  float sums[4] = {0, 0, 0, 0};
-  for (size_t i = 0; i < n; i++) {
-    const fvad_single_stats &s = st[i];
-    a->total_positives_sec += s.total_positives_sec;
-    a->true_positives_sec += s.true_positives_sec;
-    a->false_positives_sec += s.false_positives_sec;
-    a->false_negatives_sec += s.false_negatives_sec;
-    const float vals[4] = {s.true_positive_rate, s.false_negative_rate, s.false_discovery_rate, s.precision};
-    for (int k = 0; k < 4; k++) {
-      sums[k] += vals[k];
-      if (vals[k] < aggs[k]->min) aggs[k]->min = vals[k];
-      if (vals[k] > aggs[k]->max) aggs[k]->max = vals[k];
-    }
-  }
-  const float nf = (float)n;
-  a->true_positive_rate.overall = a->true_positives_sec / a->total_positives_sec;
-  a->false_negative_rate.overall = a->false_negatives_sec / a->total_positives_sec;
-  a->false_discovery_rate.overall = a->false_positives_sec / (a->false_positives_sec + a->true_positives_sec);
-  a->precision.overall = a->true_positives_sec / (a->true_positives_sec + a->false_positives_sec);
-  for (int k = 0; k < 4; k++) aggs[k]->avg = sums[k] / nf;
-  a->f_score_beta = 0.7f;
-  a->f_score = f_score(a->f_score_beta, a->precision.overall, a->true_positive_rate.overall);
-  a->fm_index = std::sqrt(a->precision.overall * a->true_positive_rate.overall);
-}
-
-extern "C" long fvad_parse_audacity(const char *txt, size_t len, float *out, size_t cap) {
-  // formats.parseAudacitySegments: split the raw text on '\n' (CRs are NOT
-  // stripped, formats.zig:11-14), each line on '\t'; lines with < 2 fields are
-  // skipped, an unparsable from/to field is an error.
-  long n = 0;
-  size_t pos = 0;
-  while (pos <= len) {
-    size_t e = pos;
-    while (e < len && txt[e] != '\n') e++;
-    size_t t1 = pos;
-    while (t1 < e && txt[t1] != '\t') t1++;
-    if (t1 < e) {
-      size_t t2 = t1 + 1;
-      while (t2 < e && txt[t2] != '\t') t2++;
-      const std::string a(txt + pos, t1 - pos), b(txt + t1 + 1, t2 - t1 - 1);
-      if (a.empty() || b.empty()) return FVAD_EFORMAT;
-      char *end = nullptr;
-      const float from = std::strtof(a.c_str(), &end);
-      if (*end) return FVAD_EFORMAT;
-      const float to = std::strtof(b.c_str(), &end);
-      if (*end) return FVAD_EFORMAT;
-      if ((size_t)n < cap && out) {
-        out[2 * n] = from;
-        out[2 * n + 1] = to;
-      }
-      n++;
-    }
-    pos = e + 1;
-  }
-  return n;
-}

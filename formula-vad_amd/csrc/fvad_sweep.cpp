@@ -1,10 +1,10 @@
 // Config sweep (include/fvad.h: fvad_sweep_*): the recorded windows, the
 // validation, the device run in chunks (k_vadm_sweep, fvad_sweep.hip; with
 // fvad_sweep_run_score each chunk's k_sweep_score behind it,
-// fvad_sweep_score.hip), the host run (the host VADMachine, fvad_host.cpp) and
-// the scores (fvad_sweep_score: the host evaluator; fvad_sweep_run_score: the
-// shared core, fvad_eval_core.h).  Everything but fvad_sweep_run and
-// fvad_sweep_run_score on a device sweep is host code.
+// fvad_sweep_score.hip), the host run (the host VADMachine, fvad_machine.cpp)
+// and the scores (fvad_sweep_score: the host evaluator, fvad_eval.cpp;
+// fvad_sweep_run_score: the shared core, fvad_eval_core.h).  Everything but
+// fvad_sweep_run and fvad_sweep_run_score on a device sweep is host code.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "fvad_eval_core.h"
 #include "fvad_hip_own.h"
 #include "fvad_internal.h"
+#include "fvad_machine.h"
 #include "fvad_sweep.h"
 
 using fvad::set_error;
@@ -40,10 +41,41 @@ struct Lane {  // results of (stream, config)
   fvad_vadm_snapshot snap{};
   std::vector<fvad_segment> segs;  // the first min(total, seg_capacity)
 };
-struct DevBuf {  // device bytes, grown on demand (ensure)
-  fvad::dev_ptr<char> p;
-  size_t cap = 0;
+
+// Device elements of T, grown on demand: never shrinks, holds 256 bytes at
+// least, and is empty (cap 0) after a failed grow.  The copies and the clear
+// count in elements; a count of 0 does nothing (the buffer may not exist).
+template <typename T>
+struct DevBuf {
+  fvad::dev_ptr<T> p;
+  size_t cap = 0;  // elements
+  T *get() const { return p.get(); }
+  int grow(size_t count) {
+    if (count <= cap) return FVAD_OK;
+    p.reset();
+    cap = 0;
+    const size_t n = std::max(count, (256 + sizeof(T) - 1) / sizeof(T));
+    if (const int rc = fvad::make_dev(p, n)) return rc;
+    cap = n;
+    return FVAD_OK;
+  }
+  hipError_t put(const T *src, size_t count) const {
+    return count ? hipMemcpy(p.get(), src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+  }
+  hipError_t put_async(const T *src, size_t count, hipStream_t s) const {
+    return count ? hipMemcpyAsync(p.get(), src, count * sizeof(T), hipMemcpyHostToDevice, s) : hipSuccess;
+  }
+  hipError_t zero_async(size_t count, hipStream_t s) const { return hipMemsetAsync(p.get(), 0, count * sizeof(T), s); }
+  // *back (the run's device-to-host bytes) grows by what was copied; U: T, or
+  // the same record under its API name (VadmSeg as fvad_segment, fvad_machine.h)
+  template <typename U>
+  hipError_t fetch(U *dst, size_t count, size_t *back = nullptr) const {
+    static_assert(sizeof(U) == sizeof(T), "fetch into records of the buffer's size");
+    if (back) *back += count * sizeof(T);
+    return hipMemcpy(dst, p.get(), count * sizeof(T), hipMemcpyDeviceToHost);
+  }
 };
+
 struct Score {  // one fvad_sweep_run_score call: what the lanes are scored against, and their scores
   std::vector<float> lab;      // every stream's (from, to), each stream's stably sorted by start
   std::vector<long long> off;  // [n_streams + 1] first label of a stream
@@ -51,6 +83,28 @@ struct Score {  // one fvad_sweep_run_score call: what the lanes are scored agai
   size_t n_stat = 0;  // 1 or n_cfgs
   std::vector<fvad_single_stats> single;  // [stream][cfg]
   std::vector<unsigned> status;           // [stream][cfg] fvad::kEval*
+};
+
+// The machines of configs [c0, c1) over B streams as the device holds them.
+// Making one places each config's long-term rows (K[m].lt_off).
+struct Chunk {
+  size_t c0, c1, B, seg_cap;
+  size_t lt = 0, max_st = 0, max_r = 0;  // long-term floats; the longest short-term and ratio buffers
+  Chunk(const fvad_sweep_config &c, std::vector<fvad::VadmConst> &K, size_t c0_, size_t c1_)
+      : c0(c0_), c1(c1_), B((size_t)c.n_streams), seg_cap((size_t)c.seg_capacity) {
+    for (size_t m = c0; m < c1; m++) {
+      K[m].lt_off = (long long)lt;
+      lt += (size_t)K[m].lt_pitch * B;
+      max_st = std::max(max_st, (size_t)K[m].n_st);
+      max_r = std::max(max_r, (size_t)K[m].n_r);
+    }
+  }
+  size_t n_cfgs() const { return c1 - c0; }
+  size_t lanes() const { return B * n_cfgs(); }
+  size_t bytes() const {
+    return (lt + (max_st + max_r) * lanes()) * sizeof(float) + lanes() * sizeof(fvad::VadmState) +
+           lanes() * seg_cap * sizeof(fvad::VadmSeg) + n_cfgs() * sizeof(fvad::VadmConst);
+  }
 };
 }  // namespace
 
@@ -71,21 +125,23 @@ struct fvad_sweep {
   bool count_on = false;
   // device (the stream first: it is destroyed after the buffers)
   fvad::stream_ptr stream;
-  DevBuf d_band, d_wmin, d_wvad, d_wvr, d_off, d_nwin, d_K, d_st, d_lt, d_sbuf, d_rbuf, d_seg, d_count;
-  DevBuf d_lab, d_lab_off, d_stat, d_single, d_status;  // fvad_sweep_run_score
+  DevBuf<float> d_band, d_wmin, d_wvad, d_wvr, d_lt, d_sbuf, d_rbuf;
+  DevBuf<long long> d_off;
+  DevBuf<int> d_nwin;
+  DevBuf<fvad::VadmConst> d_K;
+  DevBuf<fvad::VadmState> d_st;
+  DevBuf<fvad::VadmSeg> d_seg;
+  DevBuf<unsigned long long> d_count;
+  // fvad_sweep_run_score
+  DevBuf<float> d_lab;
+  DevBuf<long long> d_lab_off;
+  DevBuf<fvad_stat_config> d_stat;
+  DevBuf<fvad_single_stats> d_single;
+  DevBuf<unsigned> d_status;
   long long n_windows = 0;
 };
 
 namespace {
-int ensure(DevBuf &b, size_t bytes) {
-  if (bytes <= b.cap) return FVAD_OK;
-  b.p.reset();
-  b.cap = 0;
-  if (const int rc = fvad::make_dev(b.p, std::max<size_t>(bytes, 256))) return rc;
-  b.cap = std::max<size_t>(bytes, 256);
-  return FVAD_OK;
-}
-
 int check_config(const fvad_sweep_config &c) {
   if (c.sample_rate != 48000) return set_error(FVAD_ERATE, "only 48 kHz is supported (VAD.zig:101-104)");
   if (c.n_streams < 1 || c.n_streams > 65535 || c.n_channels < 1 || c.n_channels > FVAD_MAX_CHANNELS)
@@ -107,36 +163,40 @@ int prepare(const fvad_sweep_config &c, const fvad_vadm_config *cfgs, size_t n, 
   K->resize(n);
   s0->resize(n);
   for (size_t m = 0; m < n; m++) {
-    int lo, hi;
-    fvad::vadm_fill_const(cfgs[m], c.sample_rate, c.fft_size, &(*K)[m], &(*s0)[m], &lo, &hi);
-    int slot = -1;
-    for (int b = 0; b < c.n_bands; b++)
-      if (c.band_lo[b] == lo && c.band_hi[b] == hi) slot = b;
-    if (slot < 0)
-      return set_error(FVAD_EINVAL, "config " + std::to_string(m) + ": its speech band (bins " + std::to_string(lo) +
-                                        ".." + std::to_string(hi) + ") is none of the sweep's bands");
-    (*K)[m].slot = slot;
-    (*K)[m].lt_pitch = ((*K)[m].n_lt + 3) & ~3;  // 16-byte rows
+    const fvad::VadmDerived d = fvad::vadm_derive(cfgs[m], c.sample_rate, c.fft_size);
+    (*K)[m] = d.K;
+    (*s0)[m] = d.s0;
+    (*K)[m].slot = fvad::band_slot(c.band_lo, c.band_hi, c.n_bands, d.lo, d.hi);
+    if ((*K)[m].slot < 0)
+      return set_error(FVAD_EINVAL, "config " + std::to_string(m) + ": its speech band (bins " + std::to_string(d.lo) +
+                                        ".." + std::to_string(d.hi) + ") is none of the sweep's bands");
   }
   return FVAD_OK;
-}
-
-// device bytes of the machines of configs [c0, c1) over B streams
-size_t chunk_bytes(const fvad_sweep_config &c, const std::vector<fvad::VadmConst> &K, size_t c0, size_t c1) {
-  const size_t B = (size_t)c.n_streams, lanes = B * (c1 - c0);
-  size_t lt = 0, max_st = 0, max_r = 0;
-  for (size_t m = c0; m < c1; m++) {
-    lt += (size_t)K[m].lt_pitch * B;
-    max_st = std::max(max_st, (size_t)K[m].n_st);
-    max_r = std::max(max_r, (size_t)K[m].n_r);
-  }
-  return (lt + (max_st + max_r) * lanes) * sizeof(float) + lanes * sizeof(fvad::VadmState) +
-         lanes * (size_t)c.seg_capacity * sizeof(fvad::VadmSeg) + (c1 - c0) * sizeof(fvad::VadmConst);
 }
 
 int check_run(const fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs) {
   if (!sw || !cfgs || n_cfgs < 1) return set_error(FVAD_EINVAL, "invalid argument");
   if (n_cfgs > ((size_t)1 << 24)) return set_error(FVAD_EINVAL, "n_cfgs above 2^24");
+  return FVAD_OK;
+}
+
+std::string over_capacity(size_t stream, size_t cfg, uint64_t n_segments) {
+  return "stream " + std::to_string(stream) + ", config " + std::to_string(cfg) + ": " + std::to_string(n_segments) +
+         " segments exceed seg_capacity, the score would be of a truncated list";
+}
+
+// Config by config: every stream's statistics (single_of(s, m, &st), an FVAD_*
+// status) into single_out[m][s] where asked for, and their aggregate into agg_out[m]
+template <typename F>
+int aggregate_configs(size_t B, size_t n, F &&single_of, fvad_aggregate_stats *agg_out, fvad_single_stats *single_out) {
+  std::vector<fvad_single_stats> st(B);
+  for (size_t m = 0; m < n; m++) {
+    for (size_t s = 0; s < B; s++) {
+      if (const int rc = single_of(s, m, &st[s])) return rc;
+      if (single_out) single_out[m * B + s] = st[s];
+    }
+    fvad_eval_aggregate(st.data(), B, &agg_out[m]);
+  }
   return FVAD_OK;
 }
 
@@ -159,41 +219,25 @@ int upload_windows(fvad_sweep *sw) {
     std::copy(w.vr.begin(), w.vr.end(), vr.begin() + off[s]);
   }
   int rc;
-  if ((rc = ensure(sw->d_band, band.size() * sizeof(float))) || (rc = ensure(sw->d_wvad, total * sizeof(float))) ||
-      (rc = ensure(sw->d_wvr, total * sizeof(float))) ||
-      (rc = ensure(sw->d_wmin, total * c.n_bands * sizeof(float))) || (rc = ensure(sw->d_off, B * sizeof(long long))) ||
-      (rc = ensure(sw->d_nwin, B * sizeof(int))))
+  if ((rc = sw->d_band.grow(band.size())) || (rc = sw->d_wvad.grow(total)) || (rc = sw->d_wvr.grow(total)) ||
+      (rc = sw->d_wmin.grow(total * c.n_bands)) || (rc = sw->d_off.grow(B)) || (rc = sw->d_nwin.grow(B)))
     return rc;
-  if (total) {
-    HIP_TRY(hipMemcpy(sw->d_band.p.get(), band.data(), band.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sw->d_wvad.p.get(), vad.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sw->d_wvr.p.get(), vr.data(), total * sizeof(float), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMemcpy(sw->d_off.p.get(), off.data(), B * sizeof(long long), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(sw->d_nwin.p.get(), nwin.data(), B * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(sw->d_band.put(band.data(), band.size()));
+  HIP_TRY(sw->d_wvad.put(vad.data(), total));
+  HIP_TRY(sw->d_wvr.put(vr.data(), total));
+  HIP_TRY(sw->d_off.put(off.data(), B));
+  HIP_TRY(sw->d_nwin.put(nwin.data(), B));
   sw->n_windows = (long long)total;
   fvad::SweepArgs a{};
   a.n_channels = c.n_channels;
   a.n_bands = c.n_bands;
   a.n_windows = sw->n_windows;
-  a.band = reinterpret_cast<const float *>(sw->d_band.p.get());
-  a.wmin = reinterpret_cast<float *>(sw->d_wmin.p.get());
+  a.band = sw->d_band.get();
+  a.wmin = sw->d_wmin.get();
   HIP_TRY(fvad::launch_sweep_min(a, sw->stream.get()));
   HIP_TRY(hipStreamSynchronize(sw->stream.get()));
   sw->dirty = false;
   return FVAD_OK;
-}
-
-void lane_from_device(const fvad::VadmState &st, const fvad::VadmSeg *seg, int seg_cap, Lane *l) {
-  fvad::vadm_snapshot_of(st, &l->snap);
-  const size_t k = std::min<size_t>(st.n_segs, (size_t)seg_cap);
-  l->segs.resize(k);
-  for (size_t i = 0; i < k; i++) {
-    l->segs[i].sample_from = seg[i].sample_from;
-    l->segs[i].sample_to = seg[i].sample_to;
-    l->segs[i].debug_rnn_vad = seg[i].debug_rnn_vad;
-    l->segs[i].debug_avg_speech_vol_ratio = seg[i].debug_avg_speech_vol_ratio;
-  }
 }
 
 // sc: null (the segments come back), or the lanes are scored on the device and
@@ -201,29 +245,26 @@ void lane_from_device(const fvad::VadmState &st, const fvad::VadmSeg *seg, int s
 int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vector<fvad::VadmState> &s0, Score *sc) {
   const fvad_sweep_config &c = sw->cfg;
   const size_t B = (size_t)c.n_streams, n = K.size();
+  const hipStream_t stream = sw->stream.get();
   HIP_TRY(hipSetDevice(c.device));
   if (sw->dirty)
     if (const int rc = upload_windows(sw)) return rc;
   int rc;
   if (sw->count_on) {
-    if ((rc = ensure(sw->d_count, fvad::kVadmCounts * sizeof(unsigned long long)))) return rc;
-    HIP_TRY(hipMemsetAsync(sw->d_count.p.get(), 0, fvad::kVadmCounts * sizeof(unsigned long long), sw->stream.get()));
+    if ((rc = sw->d_count.grow(fvad::kVadmCounts))) return rc;
+    HIP_TRY(sw->d_count.zero_async(fvad::kVadmCounts, stream));
   }
   if (sc) {  // the labels and the stat configs, once per call
-    if ((rc = ensure(sw->d_lab, sc->lab.size() * sizeof(float))) ||
-        (rc = ensure(sw->d_lab_off, sc->off.size() * sizeof(long long))) ||
-        (rc = ensure(sw->d_stat, sc->n_stat * sizeof(fvad_stat_config))))
+    if ((rc = sw->d_lab.grow(sc->lab.size())) || (rc = sw->d_lab_off.grow(sc->off.size())) ||
+        (rc = sw->d_stat.grow(sc->n_stat)))
       return rc;
-    const auto up = [&](DevBuf &d, const void *src, size_t bytes) {
-      return bytes ? hipMemcpyAsync(d.p.get(), src, bytes, hipMemcpyHostToDevice, sw->stream.get()) : hipSuccess;
-    };
-    HIP_TRY(up(sw->d_lab, sc->lab.data(), sc->lab.size() * sizeof(float)));
-    HIP_TRY(up(sw->d_lab_off, sc->off.data(), sc->off.size() * sizeof(long long)));
-    HIP_TRY(up(sw->d_stat, sc->stat, sc->n_stat * sizeof(fvad_stat_config)));
+    HIP_TRY(sw->d_lab.put_async(sc->lab.data(), sc->lab.size(), stream));
+    HIP_TRY(sw->d_lab_off.put_async(sc->off.data(), sc->off.size(), stream));
+    HIP_TRY(sw->d_stat.put_async(sc->stat, sc->n_stat, stream));
   }
   std::vector<Lane> lanes(B * n);
   std::vector<fvad::VadmState> st;
-  std::vector<fvad::VadmSeg> seg;
+  std::vector<fvad_segment> seg;  // (a VadmSeg is an fvad_segment: fvad_machine.h)
   std::vector<fvad_single_stats> single;
   std::vector<unsigned> status;
   size_t bytes_back = 0;
@@ -233,56 +274,47 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     if (sw->chunk)
       c1 = std::min(n, c0 + sw->chunk);
     else
-      while (c1 < n && chunk_bytes(c, K, c0, c1 + 1) <= kSweepBudget) c1++;
-    const size_t nc = c1 - c0, nl = B * nc;
-    size_t lt = 0, max_st = 0, max_r = 0;
-    for (size_t m = c0; m < c1; m++) {
-      K[m].lt_off = (long long)lt;
-      lt += (size_t)K[m].lt_pitch * B;
-      max_st = std::max(max_st, (size_t)K[m].n_st);
-      max_r = std::max(max_r, (size_t)K[m].n_r);
-    }
-    if ((rc = ensure(sw->d_K, nc * sizeof(fvad::VadmConst))) || (rc = ensure(sw->d_st, nl * sizeof(fvad::VadmState))) ||
-        (rc = ensure(sw->d_lt, lt * sizeof(float))) || (rc = ensure(sw->d_sbuf, max_st * nl * sizeof(float))) ||
-        (rc = ensure(sw->d_rbuf, max_r * nl * sizeof(float))) ||
-        (rc = ensure(sw->d_seg, nl * (size_t)c.seg_capacity * sizeof(fvad::VadmSeg))))
+      while (c1 < n && Chunk(c, K, c0, c1 + 1).bytes() <= kSweepBudget) c1++;
+    const Chunk ch(c, K, c0, c1);
+    const size_t nc = ch.n_cfgs(), nl = ch.lanes();
+    if ((rc = sw->d_K.grow(nc)) || (rc = sw->d_st.grow(nl)) || (rc = sw->d_lt.grow(ch.lt)) ||
+        (rc = sw->d_sbuf.grow(ch.max_st * nl)) || (rc = sw->d_rbuf.grow(ch.max_r * nl)) ||
+        (rc = sw->d_seg.grow(nl * ch.seg_cap)))
       return rc;
-    if (sc && ((rc = ensure(sw->d_single, nl * sizeof(fvad_single_stats))) ||
-               (rc = ensure(sw->d_status, nl * sizeof(unsigned)))))
-      return rc;
+    if (sc && ((rc = sw->d_single.grow(nl)) || (rc = sw->d_status.grow(nl)))) return rc;
     st.resize(nl);
     for (size_t s = 0; s < B; s++)
       for (size_t m = 0; m < nc; m++) st[s * nc + m] = s0[c0 + m];
-    HIP_TRY(hipMemcpyAsync(sw->d_K.p.get(), K.data() + c0, nc * sizeof(fvad::VadmConst), hipMemcpyHostToDevice, sw->stream.get()));
-    HIP_TRY(hipMemcpyAsync(sw->d_st.p.get(), st.data(), nl * sizeof(fvad::VadmState), hipMemcpyHostToDevice, sw->stream.get()));
+    HIP_TRY(sw->d_K.put_async(K.data() + c0, nc, stream));
+    HIP_TRY(sw->d_st.put_async(st.data(), nl, stream));
     // entries never pushed are never read (lt_nw, the counts); zeroed all the same
-    HIP_TRY(hipMemsetAsync(sw->d_lt.p.get(), 0, lt * sizeof(float), sw->stream.get()));
-    HIP_TRY(hipMemsetAsync(sw->d_sbuf.p.get(), 0, max_st * nl * sizeof(float), sw->stream.get()));
-    HIP_TRY(hipMemsetAsync(sw->d_rbuf.p.get(), 0, max_r * nl * sizeof(float), sw->stream.get()));
+    HIP_TRY(sw->d_lt.zero_async(ch.lt, stream));
+    HIP_TRY(sw->d_sbuf.zero_async(ch.max_st * nl, stream));
+    HIP_TRY(sw->d_rbuf.zero_async(ch.max_r * nl, stream));
     fvad::SweepArgs a{};
     a.n_streams = c.n_streams;
     a.n_cfgs = (int)nc;
     a.n_channels = c.n_channels;
     a.n_bands = c.n_bands;
     a.seg_cap = c.seg_capacity;
-    a.K = reinterpret_cast<const fvad::VadmConst *>(sw->d_K.p.get());
-    a.st = reinterpret_cast<fvad::VadmState *>(sw->d_st.p.get());
-    a.lt = reinterpret_cast<float *>(sw->d_lt.p.get());
-    a.sbuf = reinterpret_cast<float *>(sw->d_sbuf.p.get());
-    a.rbuf = reinterpret_cast<float *>(sw->d_rbuf.p.get());
-    a.seg = reinterpret_cast<fvad::VadmSeg *>(sw->d_seg.p.get());
-    a.win_off = reinterpret_cast<const long long *>(sw->d_off.p.get());
-    a.n_win = reinterpret_cast<const int *>(sw->d_nwin.p.get());
-    a.band = reinterpret_cast<const float *>(sw->d_band.p.get());
-    a.wmin = reinterpret_cast<float *>(sw->d_wmin.p.get());
-    a.wvad = reinterpret_cast<const float *>(sw->d_wvad.p.get());
-    a.wvr = reinterpret_cast<const float *>(sw->d_wvr.p.get());
+    a.K = sw->d_K.get();
+    a.st = sw->d_st.get();
+    a.lt = sw->d_lt.get();
+    a.sbuf = sw->d_sbuf.get();
+    a.rbuf = sw->d_rbuf.get();
+    a.seg = sw->d_seg.get();
+    a.win_off = sw->d_off.get();
+    a.n_win = sw->d_nwin.get();
+    a.band = sw->d_band.get();
+    a.wmin = sw->d_wmin.get();
+    a.wvad = sw->d_wvad.get();
+    a.wvr = sw->d_wvr.get();
     a.n_windows = sw->n_windows;
     a.fft = (unsigned long long)c.fft_size;
     a.bound_scale = sw->bound_scale;
     a.defer_max = sw->defer_max;
-    a.count = sw->count_on ? reinterpret_cast<unsigned long long *>(sw->d_count.p.get()) : nullptr;
-    HIP_TRY(fvad::launch_vadm_sweep(a, sw->stream.get()));
+    a.count = sw->count_on ? sw->d_count.get() : nullptr;
+    HIP_TRY(fvad::launch_vadm_sweep(a, stream));
     if (sc) {
       fvad::ScoreArgs b{};
       b.n_streams = c.n_streams;
@@ -290,42 +322,40 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
       b.seg_cap = c.seg_capacity;
       b.st = a.st;
       b.seg = a.seg;
-      b.lab = reinterpret_cast<const float *>(sw->d_lab.p.get());
-      b.lab_off = reinterpret_cast<const long long *>(sw->d_lab_off.p.get());
+      b.lab = sw->d_lab.get();
+      b.lab_off = sw->d_lab_off.get();
       b.stat_stride = sc->n_stat == 1 ? 0 : 1;
-      b.stat = reinterpret_cast<const fvad_stat_config *>(sw->d_stat.p.get()) + c0 * (size_t)b.stat_stride;
-      b.single = reinterpret_cast<fvad_single_stats *>(sw->d_single.p.get());
-      b.status = reinterpret_cast<unsigned *>(sw->d_status.p.get());
-      HIP_TRY(fvad::launch_sweep_score(b, sw->stream.get()));
+      b.stat = sw->d_stat.get() + c0 * (size_t)b.stat_stride;
+      b.single = sw->d_single.get();
+      b.status = sw->d_status.get();
+      HIP_TRY(fvad::launch_sweep_score(b, stream));
     }
-    HIP_TRY(hipStreamSynchronize(sw->stream.get()));
-    HIP_TRY(hipMemcpy(st.data(), sw->d_st.p.get(), nl * sizeof(fvad::VadmState), hipMemcpyDeviceToHost));
-    bytes_back += nl * sizeof(fvad::VadmState);
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(sw->d_st.fetch(st.data(), nl, &bytes_back));
     if (sc) {
       single.resize(nl);
       status.resize(nl);
-      HIP_TRY(hipMemcpy(single.data(), sw->d_single.p.get(), nl * sizeof(fvad_single_stats), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(status.data(), sw->d_status.p.get(), nl * sizeof(unsigned), hipMemcpyDeviceToHost));
-      bytes_back += nl * (sizeof(fvad_single_stats) + sizeof(unsigned));
-      for (size_t s = 0; s < B; s++)
-        for (size_t m = 0; m < nc; m++) {
-          fvad::vadm_snapshot_of(st[s * nc + m], &lanes[s * n + c0 + m].snap);
-          sc->status[s * n + c0 + m] = status[s * nc + m];
-          sc->single[s * n + c0 + m] = single[s * nc + m];
-        }
+      HIP_TRY(sw->d_single.fetch(single.data(), nl, &bytes_back));
+      HIP_TRY(sw->d_status.fetch(status.data(), nl, &bytes_back));
     } else {
-      seg.resize(nl * (size_t)c.seg_capacity);
-      HIP_TRY(hipMemcpy(seg.data(), sw->d_seg.p.get(), seg.size() * sizeof(fvad::VadmSeg), hipMemcpyDeviceToHost));
-      bytes_back += seg.size() * sizeof(fvad::VadmSeg);
-      for (size_t s = 0; s < B; s++)
-        for (size_t m = 0; m < nc; m++)
-          lane_from_device(st[s * nc + m], seg.data() + (s * nc + m) * (size_t)c.seg_capacity, c.seg_capacity,
-                           &lanes[s * n + c0 + m]);
+      seg.resize(nl * ch.seg_cap);
+      HIP_TRY(sw->d_seg.fetch(seg.data(), seg.size(), &bytes_back));
     }
+    for (size_t s = 0; s < B; s++)
+      for (size_t m = 0; m < nc; m++) {
+        const size_t from = s * nc + m, to = s * n + c0 + m;
+        fvad::vadm_snapshot_of(st[from], &lanes[to].snap);
+        if (sc) {
+          sc->status[to] = status[from];
+          sc->single[to] = single[from];
+        } else {
+          const fvad_segment *g = seg.data() + from * ch.seg_cap;
+          lanes[to].segs.assign(g, g + std::min<size_t>(st[from].n_segs, ch.seg_cap));
+        }
+      }
     c0 = c1;
   }
-  if (sw->count_on)
-    HIP_TRY(hipMemcpy(sw->counts, sw->d_count.p.get(), sizeof(sw->counts), hipMemcpyDeviceToHost));
+  if (sw->count_on) HIP_TRY(sw->d_count.fetch(sw->counts, fvad::kVadmCounts));
   sw->have_counts = sw->count_on;
   sw->lanes = std::move(lanes);
   sw->n_cfgs = n;
@@ -375,6 +405,17 @@ int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fva
   sw->kept = !sc;
   sw->bytes_back = 0;
   return FVAD_OK;
+}
+
+// fvad_sweep_run, _run_host and _run_score: the configs over the recorded
+// windows, on the host for a device = -1 sweep or when forced
+int run(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs, bool force_host, Score *sc) {
+  if (const int rc = check_run(sw, cfgs, n_cfgs)) return rc;
+  std::vector<fvad::VadmConst> K;
+  std::vector<fvad::VadmState> s0;
+  if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
+  if (force_host || sw->cfg.device == -1) return run_host(sw, cfgs, K, sc);
+  return run_device(sw, K, s0, sc);
 }
 
 const Lane *lane_of(const fvad_sweep *sw, int stream, size_t cfg) {
@@ -467,27 +508,19 @@ extern "C" int fvad_sweep_append_outputs(fvad_sweep *sw, const fvad_outputs *out
 }
 
 extern "C" int fvad_sweep_run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs) {
-  if (const int rc = check_run(sw, cfgs, n_cfgs)) return rc;
-  std::vector<fvad::VadmConst> K;
-  std::vector<fvad::VadmState> s0;
-  if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
-  return run_host(sw, cfgs, K, nullptr);
+  return run(sw, cfgs, n_cfgs, true, nullptr);
 }
 
 extern "C" int fvad_sweep_run(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs) {
-  if (const int rc = check_run(sw, cfgs, n_cfgs)) return rc;
-  std::vector<fvad::VadmConst> K;
-  std::vector<fvad::VadmState> s0;
-  if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
-  if (sw->cfg.device == -1) return run_host(sw, cfgs, K, nullptr);
-  return run_device(sw, K, s0, nullptr);
+  return run(sw, cfgs, n_cfgs, false, nullptr);
 }
 
 extern "C" int fvad_sweep_run_score(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs,
                                     const float *const *ref_from_to, const size_t *n_ref,
                                     const fvad_stat_config *stat_cfgs, size_t n_stat_cfgs,
                                     fvad_aggregate_stats *agg_out, fvad_single_stats *single_out) {
-  // everything that can be refused is refused before anything runs
+  // everything that can be refused is refused before anything runs, the
+  // run's own arguments first (run checks them again)
   if (const int rc = check_run(sw, cfgs, n_cfgs)) return rc;
   if (!ref_from_to || !n_ref || !stat_cfgs || !agg_out) return set_error(FVAD_EINVAL, "null argument");
   if (n_stat_cfgs != 1 && n_stat_cfgs != n_cfgs)
@@ -496,9 +529,6 @@ extern "C" int fvad_sweep_run_score(fvad_sweep *sw, const fvad_vadm_config *cfgs
   const size_t B = (size_t)sw->cfg.n_streams, n = n_cfgs;
   for (size_t s = 0; s < B; s++)
     if (n_ref[s] > 0 && !ref_from_to[s]) return set_error(FVAD_EINVAL, "null reference list");
-  std::vector<fvad::VadmConst> K;
-  std::vector<fvad::VadmState> s0;
-  if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
   Score sc;
   sc.stat = stat_cfgs;
   sc.n_stat = n_stat_cfgs;
@@ -518,26 +548,23 @@ extern "C" int fvad_sweep_run_score(fvad_sweep *sw, const fvad_vadm_config *cfgs
   sc.off[B] = (long long)(sc.lab.size() / 2);
   sc.single.resize(B * n);
   sc.status.assign(B * n, fvad::kEvalScored);
-  if (const int rc = sw->cfg.device == -1 ? run_host(sw, cfgs, K, &sc) : run_device(sw, K, s0, &sc)) return rc;
+  if (const int rc = run(sw, cfgs, n_cfgs, false, &sc)) return rc;
   // the run stands (counts, snapshots); a lane that could not be scored fails the call
   for (size_t s = 0; s < B; s++)
     for (size_t m = 0; m < n; m++) {
-      const std::string where = "stream " + std::to_string(s) + ", config " + std::to_string(m) + ": ";
       if (sc.status[s * n + m] == fvad::kEvalOverCapacity)
-        return set_error(FVAD_EINVAL, where + std::to_string(sw->lanes[s * n + m].snap.n_segments) +
-                                          " segments exceed seg_capacity, the score would be of a truncated list");
+        return set_error(FVAD_EINVAL, over_capacity(s, m, sw->lanes[s * n + m].snap.n_segments));
       if (sc.status[s * n + m] != fvad::kEvalScored)
-        return set_error(FVAD_EINVAL, where + "segment starts are not in non-decreasing order, the lane was not scored");
+        return set_error(FVAD_EINVAL, "stream " + std::to_string(s) + ", config " + std::to_string(m) +
+                                          ": segment starts are not in non-decreasing order, the lane was not scored");
     }
-  std::vector<fvad_single_stats> st(B);
-  for (size_t m = 0; m < n; m++) {
-    for (size_t s = 0; s < B; s++) {
-      st[s] = sc.single[s * n + m];
-      if (single_out) single_out[m * B + s] = st[s];
-    }
-    fvad_eval_aggregate(st.data(), B, &agg_out[m]);
-  }
-  return FVAD_OK;
+  return aggregate_configs(
+      B, n,
+      [&](size_t s, size_t m, fvad_single_stats *st) {
+        *st = sc.single[s * n + m];
+        return FVAD_OK;
+      },
+      agg_out, single_out);
 }
 
 extern "C" int fvad_sweep_last_run(const fvad_sweep *sw, size_t *n_cfgs, int *kept_segments, size_t *bytes_back) {
@@ -583,26 +610,20 @@ extern "C" int fvad_sweep_score(const fvad_sweep *sw, const float *const *ref_fr
     if (n_ref[s] > 0 && !ref_from_to[s]) return set_error(FVAD_EINVAL, "null reference list");
     for (size_t m = 0; m < n; m++)
       if (sw->lanes[s * n + m].snap.n_segments > (uint64_t)sw->cfg.seg_capacity)
-        return set_error(FVAD_EINVAL, "stream " + std::to_string(s) + ", config " + std::to_string(m) + ": " +
-                                          std::to_string(sw->lanes[s * n + m].snap.n_segments) +
-                                          " segments exceed seg_capacity, the score would be of a truncated list");
+        return set_error(FVAD_EINVAL, over_capacity(s, m, sw->lanes[s * n + m].snap.n_segments));
   }
-  std::vector<fvad_single_stats> st(B);
   std::vector<float> vs;
-  for (size_t m = 0; m < n; m++) {
-    for (size_t s = 0; s < B; s++) {
-      vs.clear();
-      for (const fvad_segment &g : sw->lanes[s * n + m].segs) {  // as the simulator converts them
-        vs.push_back((float)g.sample_from / 48000.0f);
-        vs.push_back((float)g.sample_to / 48000.0f);
-      }
-      if (const int rc = fvad_eval_stats(vs.data(), vs.size() / 2, ref_from_to[s], n_ref[s], stat_cfg, &st[s]))
-        return rc;
-      if (single_out) single_out[m * B + s] = st[s];
-    }
-    fvad_eval_aggregate(st.data(), B, &agg_out[m]);
-  }
-  return FVAD_OK;
+  return aggregate_configs(
+      B, n,
+      [&](size_t s, size_t m, fvad_single_stats *st) {
+        vs.clear();
+        for (const fvad_segment &g : sw->lanes[s * n + m].segs) {  // as the simulator converts them
+          vs.push_back((float)g.sample_from / 48000.0f);
+          vs.push_back((float)g.sample_to / 48000.0f);
+        }
+        return fvad_eval_stats(vs.data(), vs.size() / 2, ref_from_to[s], n_ref[s], stat_cfg, st);
+      },
+      agg_out, single_out);
 }
 
 extern "C" size_t fvad_sweep_bytes(const fvad_sweep_config *cfg, const fvad_vadm_config *cfgs, size_t n_cfgs) {
@@ -610,7 +631,7 @@ extern "C" size_t fvad_sweep_bytes(const fvad_sweep_config *cfg, const fvad_vadm
   std::vector<fvad::VadmConst> K;
   std::vector<fvad::VadmState> s0;
   if (prepare(*cfg, cfgs, n_cfgs, &K, &s0)) return 0;
-  return chunk_bytes(*cfg, K, 0, n_cfgs);
+  return Chunk(*cfg, K, 0, n_cfgs).bytes();
 }
 
 extern "C" int fvad_sweep_set_debug(fvad_sweep *sw, int key, int value) {

@@ -1,36 +1,12 @@
 // Config sweep (include/fvad.h: fvad_sweep_*): many VADMachine configs over
-// recorded window sequences.  The kernel side (fvad_sweep.hip, fvad_sweep_score.hip), the host
-// pieces it shares with the engine's device machines (fvad_engine.cpp) and
-// with the host VADMachine (fvad_host.cpp).
+// recorded window sequences.  The kernel side (fvad_sweep.hip,
+// fvad_sweep_score.hip) as fvad_sweep.cpp sees it: the kernels' arguments and
+// their launchers.
 #pragma once
-#include <string>
-#include <vector>
-
 #include "../../include/fvad.h"
 #include "fvad_staged.h"
 
 namespace fvad {
-
-// fvad_last_error()'s message; returns code (fvad_engine.cpp)
-int set_error(int code, const std::string &msg);
-
-// A config's device constants and a freshly constructed machine's state
-// (VADMachine.zig:75-100): RollingAverage lengths, thresholds in samples, the
-// initial long-term average folded as RollingAverage.init does.  The buffer
-// offsets (lt_off, st_off, r_off, lt_pitch) and the band slot are the
-// caller's.  *lo / *hi: the speech band as FFT-B bins (FFT.freqToBin).
-// One piece of code for fvad_engine_attach_vadm and the sweep.
-void vadm_fill_const(const fvad_vadm_config &c, int sample_rate, int fft_size, VadmConst *K, VadmState *s0, int *lo,
-                     int *hi);
-// VadmState in the reference's terms (fvad_engine_vadm_snapshot, fvad_sweep_snapshot)
-void vadm_snapshot_of(const VadmState &st, fvad_vadm_snapshot *out);
-
-// The host VADMachine (fvad_host.cpp) over one window sequence from a fresh
-// machine: band [n_windows][n_channels][n_bands], the machine reads slot
-// `slot`; vad / vol_ratio [n_windows]; window w enters with index w * fft_size.
-void host_vadm_lane(const fvad_vadm_config &c, int sample_rate, int fft_size, int n_channels, int n_bands, int slot,
-                    size_t n_windows, const float *band, const float *vad, const float *vol_ratio,
-                    fvad_vadm_snapshot *snap, std::vector<fvad_segment> *segs);
 
 // k_sweep_min + k_vadm_sweep's arguments.  A lane is (stream s, config c of
 // the chunk): lane index s * n_cfgs + c.

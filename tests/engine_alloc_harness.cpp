@@ -1,7 +1,9 @@
-// Ownership of the batched engine's GPU resources under allocation failure.
+// Ownership of the batched engine's and the config sweep's GPU resources under
+// allocation failure.
 //
-// The engine's real host translation units (fvad_engine*.cpp with
-// fvad_model.cpp, fvad_plan.cpp, fvad_synth.cpp) linked against two stubs
+// Their real host translation units (fvad_engine*.cpp, fvad_sweep.cpp with
+// fvad_machine.cpp, fvad_eval.cpp, fvad_model.cpp, fvad_plan.cpp,
+// fvad_synth.cpp) linked against two stubs
 // defined here, so the program needs no GPU:
 //   - a HIP runtime on the heap: device and pinned memory from calloc, copies
 //     are memcpy, events and streams are small heap objects, every query
@@ -15,7 +17,8 @@
 // failure it must leave nothing live and gives the number N of creating
 // calls; then for every k < N the k-th creating call fails: the API call it
 // fails in must report it, destroy must still release everything, and
-// attach_vadm / enable_events must succeed when simply called again.
+// attach_vadm / enable_events must succeed when simply called again.  The
+// sweep's scenario (run_sweep) does the same for a sweep.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,9 +30,12 @@
 #include <vector>
 
 #include "../include/fvad.h"
+#include "fvad_eval_core.h"
 #include "fvad_lifecycle.h"
 #include "fvad_kernels.h"
+#include "fvad_machine.h"
 #include "fvad_staged.h"
+#include "fvad_sweep.h"
 
 // ---------------------------------------------------------------------------
 // stub HIP runtime
@@ -139,6 +145,14 @@ hipError_t launch_vadm_events(const VadmEventArgs &a, hipStream_t) {
   *a.header = VadmEventHeader{a.pass, 0, 0, 0};
   return hipSuccess;
 }
+// the sweep reads back every lane's state (left as uploaded: a fresh machine
+// with no segments) and, scored, its status word and statistics
+hipError_t launch_sweep_min(const SweepArgs &, hipStream_t) { return hipSuccess; }
+hipError_t launch_vadm_sweep(const SweepArgs &, hipStream_t) { return hipSuccess; }
+hipError_t launch_sweep_score(const ScoreArgs &a, hipStream_t) {
+  for (int l = 0; l < a.n_streams * a.n_cfgs; l++) a.status[l] = kEvalScored;
+  return hipSuccess;
+}
 hipError_t launch_stream_clear(const ClearArgs &, hipStream_t) { return hipSuccess; }
 hipError_t launch_stream_vclear(const VClearArgs &, hipStream_t) { return hipSuccess; }
 hipError_t launch_stream_gather(const XferArgs &, hipStream_t) { return hipSuccess; }  // (the staging is zeroed: a valid record)
@@ -182,9 +196,9 @@ fvad_model *g_model = nullptr;
     }                               \
   } while (0)
 
-bool all_released(const char *when, const Kind &k, long fail_at) {
+bool all_released(const char *when, const char *name, long fail_at) {
   const bool ok = g_dev.empty() && g_pinned.empty() && g_events.empty() && g_streams.empty();
-  CHECK(ok, "%s, failing call %ld, %s: live device %zu, pinned %zu, events %zu, streams %zu", k.name, fail_at, when,
+  CHECK(ok, "%s, failing call %ld, %s: live device %zu, pinned %zu, events %zu, streams %zu", name, fail_at, when,
         g_dev.size(), g_pinned.size(), g_events.size(), g_streams.size());
   return ok;
 }
@@ -222,25 +236,16 @@ long run(const Kind &k, long fail_at) {
   cfg.fft_size = k.fft_size;
   cfg.use_denoiser = k.use_denoiser;
   cfg.max_ticks = kTicks;
-  fvad_vadm_config vc{};  // (fvad_vadm_config_default lives in fvad_host.cpp, not linked here)
-  vc.speech_min_freq = 100;
-  vc.speech_max_freq = 1500;
-  vc.long_term_speech_avg_sec = 180;
-  vc.short_term_speech_avg_sec = 0.2f;
-  vc.speech_threshold_factor = 18;
-  vc.channel_vol_ratio_avg_sec = 0.5f;
-  vc.channel_vol_ratio_threshold = 0.5f;
-  vc.min_consecutive_sec_to_open = 0.2f;
-  vc.max_speech_gap_sec = 2;
-  vc.min_vad_duration_sec = 0.7f;
-  // the machine's speech band as an engine band (FFT.freqToBin, as vadm_fill_const)
-  const float bin_hz = (float)cfg.sample_rate / (float)cfg.fft_size;
-  cfg.band_lo[0] = (int)std::round(vc.speech_min_freq / bin_hz);
-  cfg.band_hi[0] = (int)std::round(vc.speech_max_freq / bin_hz);
+  fvad_vadm_config vc;
+  fvad_vadm_config_default(&vc);
+  // the machine's speech band as an engine band
+  const fvad::VadmDerived d = fvad::vadm_derive(vc, cfg.sample_rate, cfg.fft_size);
+  cfg.band_lo[0] = d.lo;
+  cfg.band_hi[0] = d.hi;
 
   step("create", [&] { return fvad_engine_create(&cfg, g_model, &e) < 0; });
   if (!e) {  // create itself failed: nothing to destroy
-    all_released("after the failed create", k, fail_at);
+    all_released("after the failed create", k.name, fail_at);
     return g_fail == fails_before ? g_creates : -1;
   }
   const size_t n_in = (size_t)kTicks * kStreams * kChannels * 480;
@@ -276,9 +281,76 @@ long run(const Kind &k, long fail_at) {
     return fvad_engine_kernel_times(e, ms, &n) < 0;
   });
   fvad_engine_destroy(e);
-  all_released("after destroy", k, fail_at);
+  all_released("after destroy", k.name, fail_at);
   CHECK(fail_at < 0 || fail_at < g_creates, "%s: creating call %ld was never reached (%ld made)", k.name, fail_at,
         g_creates);
+  return g_fail == fails_before ? g_creates : -1;
+}
+
+// The config sweep over the same stubs: create, the windows, fvad_sweep_run
+// and fvad_sweep_run_score, three configs of growing buffer lengths one per
+// chunk (FVAD_SWEEP_DEBUG_CHUNK = 1), so the machines' buffers grow between
+// chunks.  The call a creating call fails in must report FVAD_ENOMEM or
+// FVAD_EDEVICE and succeed when repeated.  Returns as run does.
+long run_sweep(long fail_at) {
+  const char *name = "sweep";
+  g_creates = 0;
+  g_fail_at = fail_at;
+  const int fails_before = g_fail;
+  auto step = [&](const char *what, auto call) {
+    if (g_fail != fails_before) return;
+    const long before = g_creates;
+    const int rc = call();
+    if (fail_at < before || fail_at >= g_creates) {
+      CHECK(rc >= 0, "%s, failing call %ld: %s failed: %s", name, fail_at, what, fvad_last_error());
+      return;
+    }
+    CHECK(rc == FVAD_ENOMEM || rc == FVAD_EDEVICE, "%s: %s returned %d although its creating call %ld failed", name,
+          what, rc, fail_at);
+    CHECK(fvad_last_error()[0] != 0, "%s: %s failed at creating call %ld without a message", name, what, fail_at);
+    CHECK(call() >= 0, "%s: %s repeated after its failed creating call %ld: %s", name, what, fail_at, fvad_last_error());
+  };
+
+  fvad_vadm_config vc[3];
+  fvad_sweep_config cfg{};
+  cfg.n_streams = kStreams;
+  cfg.n_channels = kChannels;
+  cfg.sample_rate = 48000;
+  cfg.fft_size = 2048;
+  cfg.n_bands = 1;
+  cfg.use_denoiser = 1;
+  cfg.seg_capacity = 4;
+  cfg.device = 0;
+  for (int m = 0; m < 3; m++) {  // each config's three buffers outgrow the previous one's (and the 256-byte floor)
+    fvad_vadm_config_default(&vc[m]);
+    vc[m].long_term_speech_avg_sec += 20.0f * m;
+    vc[m].short_term_speech_avg_sec = vc[m].channel_vol_ratio_avg_sec = m ? 2.0f * m : 0.2f;
+  }
+  const fvad::VadmDerived d = fvad::vadm_derive(vc[0], cfg.sample_rate, cfg.fft_size);
+  cfg.band_lo[0] = d.lo;
+  cfg.band_hi[0] = d.hi;
+  const size_t n_win = 3;
+  const std::vector<float> zeros(n_win * kChannels, 0.0f);
+  const float label[2] = {0.0f, 1.0f};
+  const float *refs[kStreams] = {label, label};
+  const size_t n_ref[kStreams] = {1, 1};
+  const fvad_stat_config stat{};
+  fvad_aggregate_stats agg[3];
+
+  fvad_sweep *sw = nullptr;
+  step("sweep_create", [&] { return fvad_sweep_create(&cfg, &sw); });
+  if (sw) {
+    for (int s = 0; s < kStreams; s++)
+      step("set_windows", [&] { return fvad_sweep_set_windows(sw, s, n_win, zeros.data(), zeros.data(), zeros.data()); });
+    step("set_debug", [&] { return fvad_sweep_set_debug(sw, FVAD_SWEEP_DEBUG_CHUNK, 1); });
+    step("sweep_run", [&] { return fvad_sweep_run(sw, vc, 3); });
+    step("sweep_run_score", [&] { return fvad_sweep_run_score(sw, vc, 3, refs, n_ref, &stat, 1, agg, nullptr); });
+    fvad_sweep_destroy(sw);
+  } else {
+    CHECK(false, "%s, failing call %ld: no sweep", name, fail_at);
+  }
+  all_released("after destroy", name, fail_at);
+  CHECK(fail_at < g_creates, "%s: creating call %ld was never reached (%ld made)", name, fail_at, g_creates);
   return g_fail == fails_before ? g_creates : -1;
 }
 
@@ -350,15 +422,18 @@ int main() {
     return 1;
   }
   check_stage_table();
-  for (const Kind &k : kKinds) {
-    const long n = run(k, -1);
-    if (n < 0) continue;
+  // a scenario without a failure, then with each of its creating calls failed in turn
+  auto every_failure = [](const char *name, auto scenario) {
+    const long n = scenario(-1);
+    if (n < 0) return;
     long done = 0;
     for (long f = 0; f < n; f++)
-      if (run(k, f) >= 0) done++;
-    std::printf("%s: %ld creating calls, %ld of them failed in turn and survived\n", k.name, n, done);
-    CHECK(done == n, "%s: %ld of %ld failure runs passed", k.name, done, n);
-  }
+      if (scenario(f) >= 0) done++;
+    std::printf("%s: %ld creating calls, %ld of them failed in turn and survived\n", name, n, done);
+    CHECK(done == n, "%s: %ld of %ld failure runs passed", name, done, n);
+  };
+  for (const Kind &k : kKinds) every_failure(k.name, [&](long f) { return run(k, f); });
+  every_failure("sweep", run_sweep);
   fvad_model_free(g_model);
   CHECK(g_bad == 0, "%d releases of something not live", g_bad);
   std::printf(g_fail ? "FAILED: %d checks\n" : "ok\n", g_fail);

@@ -124,6 +124,67 @@ def test_vadmachine_matches_oracle(fvad_mod, oracle_mod):
     assert got == ref
 
 
+DERIVATION_ALTS = (
+    dict(long_term_speech_avg_sec=7.3, short_term_speech_avg_sec=0.35, speech_threshold_factor=6.0,
+         has_initial_long_term_avg=0),
+    dict(long_term_speech_avg_sec=31.0, channel_vol_ratio_avg_sec=1.1, channel_vol_ratio_threshold=0.3,
+         min_consecutive_sec_to_open=0.05, max_speech_gap_sec=0.6, min_vad_duration_sec=0.2,
+         speech_threshold_factor=9.0),
+    dict(initial_long_term_avg=0.02, speech_threshold_factor=4.0, max_speech_gap_sec=1.0, min_vad_duration_sec=0.3,
+         short_term_speech_avg_sec=0.01),
+)
+
+
+def test_machine_derivation_matches_oracle(fvad_mod, oracle_mod):
+    """How a config becomes a machine (RollingAverage lengths, thresholds in
+    samples, the initial long-term average: fvad_machine.cpp vadm_derive) is
+    one piece of code for the host machine and the device's, so comparing the
+    two no longer catches a wrong derivation: the oracle pins it.  The default
+    config and three alternates with other lengths, thresholds, gaps and
+    initial averages, over the oracle's traced windows of 40 s of a synthetic
+    stream: the host sweep's and the stand-alone VADMachine's segment lists are
+    the oracle's, and every field of the sweep's final snapshot (the averages'
+    bits, write indices and written counts among them) is the oracle's."""
+    O = oracle_mod
+
+    def cfgs(mod):
+        out = [mod.VadmConfig.default()]
+        for changes in DERIVATION_ALTS:
+            c = mod.VadmConfig.default()
+            for k, v in changes.items():
+                setattr(c, k, v)
+            out.append(c)
+        return out
+
+    x, _ = fvad_mod.synth_stream(1, 48000 * 40, 2)
+    ocfgs = cfgs(O)
+    p = O.Pipeline(2, O.Model(seed=1), alt_cfgs=ocfgs[1:], trace_windows=1000)
+    p.push([x[0], x[1]])
+    _, wins = p.trace()
+    assert len(wins) == 48000 * 40 // 2048
+    fcfgs = cfgs(fvad_mod)
+    sw = fvad_mod.Sweep(1, 2, device=-1)
+    sw.set_windows(0, wins["band"][:, :2], wins["ratio"], wins["vad"])
+    sw.run(fcfgs)
+    written = []
+    for m, n_segs in enumerate((3, 0, 2, 4)):
+        ref = p.segments(m - 1)
+        assert len(ref) == n_segs, m
+        assert sw.segments(0, m) == (n_segs, ref), m
+        vm = fvad_mod.VADMachine(fcfgs[m], n_channels=2)
+        for w in wins:
+            vm.run(int(w["index"]), w["band"][:2], float(w["vad"]), float(w["ratio"]))
+        assert vm.segments() == ref, m
+        snap, osnap = sw.snapshot(0, m), p.vadm_snapshot(m - 1)
+        for k, v in osnap.items():
+            assert snap[k] == v, (m, k)
+        assert set(snap) == set(osnap)
+        written.append(snap["written"])
+    assert [w[0] for w in written] == [4218, 171, 726, 4218]
+    assert [w[1] for w in written] == [4, 8, 4, 1]
+    assert [w[2] for w in written] == [11, 11, 25, 11]
+
+
 def test_vadmachine_alt_config_bins(fvad_mod):
     c = fvad_mod.VadmConfig.default()
     c.speech_min_freq, c.speech_max_freq = 300.0, 3000.0
@@ -281,14 +342,23 @@ def test_engine_releases_everything_when_an_allocation_fails():
     and above kMaxFftB), fused, fp16 and use_denoiser = 0 engines.  The failing
     API call reports it, fvad_engine_destroy leaves no device memory, pinned
     memory, event or stream live, and a failed attach_vadm / enable_events
-    succeeds when called again."""
+    succeeds when called again.  The same for a config sweep (fvad_sweep.cpp):
+    create, set_windows, fvad_sweep_run and fvad_sweep_run_score over three
+    configs, one per chunk, whose buffers grow from chunk to chunk; the failing
+    call reports FVAD_ENOMEM or FVAD_EDEVICE and succeeds when repeated.  Its 24
+    creating calls, from the code: the stream (1); the windows' six arrays
+    (6); the first chunk's constants, states, long-term, short-term, ratio and
+    segment buffers (6); the three rolling buffers again in each of the next
+    two chunks (6); in the scoring run the labels, their offsets and the stat
+    config (3), then the statistics and status words (2)."""
     import subprocess
     subprocess.check_call(["make", "-s", "-j", "8", "-C", PKG, "build/engine_alloc_harness"])
     out = subprocess.run([os.path.join(PKG, "build", "engine_alloc_harness")], capture_output=True, text=True,
                          timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.strip().splitlines()
-    assert lines[-1] == "ok" and len(lines) == 6, out.stdout
-    for line in lines[:-1]:
+    assert lines[-1] == "ok" and len(lines) == 7, out.stdout
+    for line in lines[:5]:
         m = re.search(r": (\d+) creating calls, (\d+) of them failed in turn and survived", line)
         assert m and int(m[1]) == int(m[2]) >= 40, line
+    assert lines[5] == "sweep: 24 creating calls, 24 of them failed in turn and survived"
