@@ -572,6 +572,10 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
   a.out_win_flag = e->d_wflag;
   if (c.use_denoiser) {
     HIP_TRY(fvad::launch_prep(a, e->pstream, timed ? e->ev : nullptr));
+    // clip capture: the push's input into the history ring, by the stream that
+    // reads it, before ev_prep_done (and the caller's ev_in_free) are recorded
+    if (e->cap)
+      if (const int rc = capture_append(e, a, b, timed)) return rc;
     HIP_TRY(hipEventRecord(e->ev_prep_done[b].get(), e->pstream));
     HIP_TRY(wait_event(e->stream.get(), e->ev_prep_done[b].get()));
     // window output set b is free once push k-2's k_vadm_hbm has read it
@@ -868,6 +872,11 @@ extern "C" int fvad_engine_clear_times(fvad_engine *e) {
   }
   e->et_ms_sum = 0;
   e->et_timed = 0;
+  if (e->cap)
+    for (int k = 0; k < 2; k++) {
+      e->cap->ms_sum[k] = 0;
+      e->cap->n_timed[k] = 0;
+    }
   e->n_timed = 0;
   e->res_count = 0;
   return FVAD_OK;

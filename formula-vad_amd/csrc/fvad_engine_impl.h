@@ -1,7 +1,7 @@
 // The batched engine's private parts: struct fvad_engine and the functions its
 // translation units share (fvad_engine.cpp, fvad_engine_ingest.cpp,
-// fvad_engine_vadm.cpp, fvad_engine_lifecycle.cpp).  Host code only: not
-// installed, and no .hip file includes it.
+// fvad_engine_vadm.cpp, fvad_engine_lifecycle.cpp, fvad_capture_host.cpp).
+// Host code only: not installed, and no .hip file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 
 #include "../../include/fvad.h"
 #include "fvad_hip_own.h"
+#include "fvad_capture.h"
 #include "fvad_internal.h"
 #include "fvad_kernels.h"
 #include "fvad_lifecycle.h"
@@ -77,6 +78,42 @@ inline uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
   return h;
 }
 
+}  // namespace eng
+}  // namespace fvad
+
+// Clip capture (fvad_engine_enable_capture; DESIGN.md section 7, "Clip
+// capture"): everything it owns, made by the enabling call; an engine without
+// capture has none of it.
+namespace fvad {
+namespace eng {
+struct Capture {
+  int machine = 0;
+  unsigned long long history = 0, H = 0;
+  size_t pool_cap = 0, desc_cap = 0;
+  dev_ptr<float> hist;                // [s][c][H]
+  dev_ptr<CapPos> pos, snap[2];       // the appending stream's positions; their value after the push of each parity
+  dev_ptr<cap::Pend> pend;            // [s][cap::kQueue]
+  dev_ptr<unsigned> pend_n;           // [s]
+  dev_ptr<CapState> state;
+  dev_ptr<CapWork> work;              // [cap::kQueue * n_streams]
+  dev_ptr<unsigned char> flush;       // [s] fvad_engine_capture_flush's list
+  pinned_ptr<float> pool;             // written by the device through dv_pool
+  float *dv_pool = nullptr;
+  pinned_ptr<fvad_clip> desc;
+  CapClip *dv_desc = nullptr;
+  // header slots: a push's pass writes slot pass % kEvHeaders (the event
+  // feed's pass ordinal: events_retire reads both), a flush the last one
+  pinned_ptr<CapHeader> hdr;
+  CapHeader *dv_hdr = nullptr;
+  // behind the capture pass of the push of each parity: the next append of
+  // that parity waits for it (it rewrites the ring words and the snapshot
+  // that pass read)
+  event_ptr ev_pass[2];
+  uint64_t desc_read = 0, desc_end = 0, pool_read = 0, pool_end = 0, lost = 0;
+  EventTimer at[2], pt[2];  // k_hist_append (by push parity) and the pass (by vadm_slot)
+  double ms_sum[2] = {};
+  int n_timed[2] = {};
+};
 }  // namespace eng
 }  // namespace fvad
 
@@ -294,6 +331,8 @@ struct fvad_engine {
   int rt_next = 0;
   double rt_ms[3] = {};
   int rt_n[3] = {};
+  // clip capture, last: released before everything it refers to
+  std::unique_ptr<fvad::eng::Capture> cap;
 };
 
 namespace fvad {
@@ -315,7 +354,15 @@ int tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, const int32_t *
 int vadm_reset(fvad_engine *e);
 int vadm_flush(fvad_engine *e, bool fast = true);
 int events_reset(fvad_engine *e);
+int events_retire(fvad_engine *e, bool wait_oldest);
 int collect_vadm_timing(fvad_engine *e);
+// fvad_capture_host.cpp
+int capture_append(fvad_engine *e, const fvad::StagedArgs &a, int b, bool timed);
+int capture_pass(fvad_engine *e, const fvad::VadmArgs &v, uint64_t push, int b, int slot, bool timed);
+int capture_retire(fvad_engine *e, uint64_t pass);
+int capture_reset(fvad_engine *e);
+int capture_set_streams(fvad_engine *e, const int32_t *streams, const uint64_t *samples, int n);
+int capture_collect_timing(fvad_engine *e);
 
 }  // namespace eng
 }  // namespace fvad

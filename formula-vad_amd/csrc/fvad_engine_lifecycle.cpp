@@ -197,6 +197,9 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
       HIP_TRY(fvad::launch_stream_vclear(va, e->side));
     }
   }
+  // clip capture: the streams' positions restart behind the appends already
+  // queued, their pending clips go behind the passes already queued
+  if (e->cap && (rc = capture_set_streams(e, streams, nullptr, n))) return rc;
   if (rt && ((rc = rt[0].end(e->stream.get())) || (split && (rc = rt[1].end(e->pstream))) ||
              (e->vadm.n > 0 && (rc = rt[2].end(e->side)))))
     return rc;
@@ -300,5 +303,19 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
     HIP_TRY(fvad::launch_stream_scatter(a, e->stream.get()));
   }
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
+  if (e->cap) {
+    // the slots continue at their records' sample counts with nothing held
+    // (a blob carries no audio and no pending clip)
+    std::vector<uint64_t> at((size_t)n);
+    for (int i = 0; i < n; i++) {
+      int ticks;
+      std::memcpy(&ticks, body + (size_t)(index ? index[i] : i) * (size_t)h.stream_bytes + 4 * fvad::st::kFramesDone,
+                  sizeof(ticks));
+      at[i] = (uint64_t)ticks * fvad::kFrame;
+    }
+    if ((rc = capture_set_streams(e, streams, at.data(), n))) return rc;
+    HIP_TRY(hipStreamSynchronize(input_reader(e)));
+    HIP_TRY(hipStreamSynchronize(e->side));
+  }
   return FVAD_OK;
 }

@@ -11,12 +11,11 @@
 
 using namespace fvad::eng;
 
-namespace {
-
 // Event feed: the passes whose `done` event has completed leave ev_flight, the
-// newest one's header giving the ring's valid end and the lost count.  Never
+// newest one's header giving the ring's valid end and the lost count (and,
+// with clip capture, the capture pass's header the clips' valid ends).  Never
 // blocks unless wait_oldest (the header slots are all taken).
-int events_retire(fvad_engine *e, bool wait_oldest) {
+int fvad::eng::events_retire(fvad_engine *e, bool wait_oldest) {
   while (!e->ev_flight.empty()) {
     fvad_engine::EvPass &p = e->ev_flight.front();
     const hipError_t q = hipEventQuery(p.done.get());
@@ -33,11 +32,15 @@ int events_retire(fvad_engine *e, bool wait_oldest) {
     e->ev_end = h->end;
     e->ev_lost = h->lost;
     e->ev_pushes_done = p.push + 1;
+    if (e->cap)
+      if (const int rc = capture_retire(e, p.pass)) return rc;
     e->ev_pool.push_back(std::move(p.done));
     e->ev_flight.pop_front();
   }
   return FVAD_OK;
 }
+
+namespace {
 
 // k_vadm_events behind the machine pass just queued on the side stream
 int enqueue_events(fvad_engine *e, const fvad::VadmArgs &v, uint64_t push, int slot, bool timed) {
@@ -101,6 +104,9 @@ int enqueue_vadm(fvad_engine *e, const fvad::StagedArgs &v, int b, bool timed, b
     // the window outputs are free once the machines have read them: the
     // next push but one does not wait for the event pass
     HIP_TRY(hipEventRecord(e->ev_vadm_b[b].get(), e->side));
+    // the capture pass reads the staged records before k_vadm_events clears
+    // their counts, and becomes visible with that pass's `done` event
+    if (e->cap && (rc = capture_pass(e, vf.vadm, e->vpend_push, b, slot, timed))) return rc;
     if ((rc = enqueue_events(e, vf.vadm, e->vpend_push, slot, timed))) return rc;
     HIP_TRY(hipEventRecord(e->ev_vadm.get(), e->side));
     return FVAD_OK;
@@ -122,7 +128,7 @@ int fvad::eng::events_reset(fvad_engine *e) {
   std::memset(e->h_ev_hdr.get(), 0xff, sizeof(fvad::VadmEventHeader) * fvad_engine::kEvHeaders);
   e->ev_read = e->ev_end = e->ev_lost = e->ev_pass_next = e->ev_pushes_done = 0;
   for (EventTimer &t : e->et) t.pending = false;
-  return FVAD_OK;
+  return e->cap ? capture_reset(e) : FVAD_OK;
 }
 
 // the last push's VADMachine, enqueued now (after its push's kernels);
@@ -161,7 +167,7 @@ int fvad::eng::collect_vadm_timing(fvad_engine *e) {
     if ((rc = e->vt[k].collect(e->vadm_ms_sum[e->vadm_kind[k]], e->vadm_timed[e->vadm_kind[k]]))) return rc;
   for (EventTimer &t : e->et)
     if ((rc = t.collect(e->et_ms_sum, e->et_timed))) return rc;
-  return FVAD_OK;
+  return capture_collect_timing(e);
 }
 
 // ---------------------------------------------------------------------------

@@ -102,6 +102,7 @@ DEBUG_VADM_PAR_SERIAL_EVERY, DEBUG_VADM_ALWAYS_PAR, DEBUG_VADM_LT_FULL, DEBUG_VA
 DEBUG_VADM_BOUND_SCALE, DEBUG_VADM_COUNT, DEBUG_VADM_NEGATE_AT, DEBUG_RESET_TIMES = 5, 6, 7, 8
 DEBUG_EVENTS_CHUNK = 9
 EVENT_SPEECH_OPEN, EVENT_SEGMENT = 1, 2  # fvad_event.kind
+CLIP_HEAD_SHORT, CLIP_TAIL_SHORT, CLIP_NO_AUDIO = 1, 2, 4  # fvad_clip.flags
 SHARE_PREP, SHARE_SIDE = 1, 2  # fvad_engine_share_streams
 
 # stream blobs (fvad_engine_save_streams): include/fvad.h documents the layout
@@ -131,6 +132,16 @@ class Event(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("stream", C.c_int32), ("machine", C.c_int32), ("seq", C.c_uint32),
                 ("push", C.c_uint64), ("sample_from", C.c_uint64), ("sample_to", C.c_uint64),
                 ("debug_rnn_vad", C.c_float), ("debug_avg_speech_vol_ratio", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class Clip(C.Structure):
+    """fvad_clip (include/fvad.h): the descriptor of one captured clip, 64 bytes."""
+    _fields_ = [("stream", C.c_int32), ("seq", C.c_uint32), ("channel", C.c_int32), ("flags", C.c_uint32),
+                ("push", C.c_uint64), ("sample_from", C.c_uint64), ("sample_to", C.c_uint64),
+                ("first_sample", C.c_uint64), ("n_samples", C.c_uint64), ("reserved", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -229,6 +240,10 @@ SYMBOLS = [
                                           C.POINTER(C.c_uint64)]),
     ("fvad_engine_event_progress", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("fvad_engine_event_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("fvad_engine_enable_capture", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_size_t]),
+    ("fvad_engine_poll_clip", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("fvad_engine_capture_flush", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("fvad_engine_capture_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("fvad_engine_set_debug", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("fvad_engine_debug_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("fvad_engine_share_streams", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
@@ -600,6 +615,52 @@ class Engine:
         ms, n = C.c_double(), C.c_int()
         _check(lib().fvad_engine_event_times(self.h, C.byref(ms), C.byref(n)), "fvad_engine_event_times")
         return ms.value, n.value
+
+    def enable_capture(self, machine=0, history_sec=10.0, pool_samples=0):
+        """Record machine's segments on the device (fvad_engine_enable_capture): after
+        attach_vadm and enable_events; history_sec >= 4 of every stream's input is held,
+        pool_samples of finished clips between polls (0: the default, 64 Mi)."""
+        _check(lib().fvad_engine_enable_capture(self.h, machine, history_sec, pool_samples),
+               "fvad_engine_enable_capture")
+
+    def poll_clips(self):
+        """The finished clips, oldest first, as (descriptor dict, float32 samples); never
+        waits for the device.  The clips lost so far: capture_lost()."""
+        out = []
+        info, lost = Clip(), C.c_uint64()
+        buf = np.zeros(0, np.float32)
+        while True:
+            rc = lib().fvad_engine_poll_clip(self.h, C.byref(info), buf.ctypes.data_as(C.c_void_p), buf.size,
+                                             C.byref(lost))
+            if rc == -1 and info.n_samples > buf.size:  # FVAD_EINVAL: the clip is still queued, its size known
+                buf = np.zeros(int(info.n_samples), np.float32)
+                continue
+            _check(min(rc, 0), "fvad_engine_poll_clip")
+            self._clips_lost = lost.value
+            if rc == 0:
+                return out
+            out.append((info.as_dict(), buf[: info.n_samples].copy()))
+
+    def capture_lost(self):
+        """Clips that lost their audio or their descriptor so far, as of the last poll_clips()."""
+        return getattr(self, "_clips_lost", 0)
+
+    def capture_flush(self, ids=None):
+        """Complete the listed streams' pending clips now (None: every stream's), cut at
+        the stream's current sample count (fvad_engine_capture_flush; a sync point)."""
+        if ids is None:
+            _check(lib().fvad_engine_capture_flush(self.h, None, 0), "fvad_engine_capture_flush")
+            return
+        a = _ids(ids)
+        _check(lib().fvad_engine_capture_flush(self.h, a.ctypes.data_as(C.c_void_p), a.size),
+               "fvad_engine_capture_flush")
+
+    def capture_times(self):
+        """({"k_hist_append": ms, "capture_pass": ms} averages over the timed pushes, how
+        many passes) -- a sync point."""
+        ms, n = (C.c_double * 2)(), C.c_int()
+        _check(lib().fvad_engine_capture_times(self.h, ms, C.byref(n)), "fvad_engine_capture_times")
+        return {"k_hist_append": ms[0], "capture_pass": ms[1]}, n.value
 
     def vadm_snapshot(self, stream, machine=0):
         """The device machine's whole state (fvad_engine_vadm_snapshot) as a dict."""

@@ -460,6 +460,69 @@ int fvad_engine_event_progress(fvad_engine *e, uint64_t *pushes_done);
  * last fvad_engine_clear_times, and how many (synchronises the engine) */
 int fvad_engine_event_times(fvad_engine *e, double *ms_avg, int *n_runs);
 
+/* Clip capture: the Recorder (AudioPipeline.zig:134-195, Recorder.zig:52-146)
+ * for the batched engine.  The engine keeps the last history_sec of every
+ * stream's input on the device and, for each SEGMENT event of one machine,
+ * hands over the raw input of [sample_from, sample_to) -- the floats of a
+ * float push, k / 32768.0f of the 16-bit ingest -- on the channel
+ * fvad_recording_channel chooses over exactly the delivered samples.  A clip
+ * completes in the machine pass of the first push at whose end its stream
+ * holds sample_to samples (sample_to = speech_end + 2 s: usually a later push
+ * than the segment's); until then it waits in the stream's queue of 4, and a
+ * clip that finds the queue full is lost (counted).  Clips are delivered in
+ * order of completing push, then stream, then seq -- the same list for the
+ * same pushes whatever the schedule. */
+#define FVAD_CLIP_HEAD_SHORT 1 /* samples before first_sample were no longer held */
+#define FVAD_CLIP_TAIL_SHORT 2 /* cut by fvad_engine_capture_flush before sample_to was pushed */
+#define FVAD_CLIP_NO_AUDIO 4   /* the pool had no room (or nothing was held): n_samples = 0, channel = -1, counted in lost */
+typedef struct {
+  int32_t stream;
+  uint32_t seq; /* the SEGMENT event's seq */
+  int32_t channel;
+  uint32_t flags;
+  uint64_t push;                    /* ordinal of the push whose machine pass completed the clip */
+  uint64_t sample_from, sample_to;  /* the segment's */
+  uint64_t first_sample, n_samples; /* what is delivered: [first_sample, first_sample + n_samples) */
+  uint64_t reserved;                /* 0 */
+} fvad_clip; /* 64 bytes, little endian, no padding */
+/* Start capturing machine `machine`'s segments (the reference records the main
+ * machine, 0).  After fvad_engine_attach_vadm and fvad_engine_enable_events,
+ * once, with no push submitted and not yet collected, on a staged-family
+ * engine (FVAD_MODE_STAGED, FP16, FP16_FUSED, F32_FAST) with use_denoiser = 1:
+ * FVAD_EINVAL otherwise.  A sync point.  history_sec >= 4 bounds how far back
+ * a clip may start: at the end of a push that leaves a stream at sample n the
+ * engine holds [max(base, n - floor(48000 * history_sec)), n) of it, base the
+ * stream's first sample of this life (0, or the position of its last reset or
+ * restore); earlier samples are cut from a clip (FVAD_CLIP_HEAD_SHORT).
+ * pool_samples: the samples of finished clips held between polls, 0 = 64 Mi.
+ * FVAD_ENOMEM leaves the engine unchanged.  An engine that never calls it
+ * allocates and launches nothing for capture. */
+int fvad_engine_enable_capture(fvad_engine *e, int machine, double history_sec, size_t pool_samples);
+/* The oldest finished clip, without waiting for the device: 1 and the clip in
+ * *info and pcm[0, n_samples), or 0 when none is ready.  cap_samples <
+ * n_samples: *info is filled, the clip stays queued, FVAD_EINVAL.  A delivered
+ * clip frees its pool space for later passes.  A pass places its clips in
+ * order behind the unread ones: a full pool loses the newest clips' audio
+ * (the descriptor still arrives, FVAD_CLIP_NO_AUDIO), a full descriptor ring
+ * the descriptor too; *lost (nullable) counts both, and the clips a full
+ * pending queue turned away, so far.  After fvad_engine_sync, polls deliver
+ * every clip completed by every push submitted so far.  fvad_engine_reset
+ * discards pending and unpolled clips and zeroes the counts;
+ * fvad_engine_reset_streams drops the listed streams' pending clips and
+ * restarts their positions at 0 (queued clips stay; no host wait);
+ * fvad_engine_restore_streams sets the listed streams' position to the blob's
+ * sample count: a blob carries no audio history and no pending clip. */
+int fvad_engine_poll_clip(fvad_engine *e, fvad_clip *info, float *pcm, size_t cap_samples, uint64_t *lost);
+/* A sync point: the pending clips of the n listed streams (NULL: of all) are
+ * completed now, each cut at its stream's current sample count
+ * (FVAD_CLIP_TAIL_SHORT), delivered in stream order, then seq, with the last
+ * push's ordinal.  For a stream's end, before fvad_engine_reset_streams. */
+int fvad_engine_capture_flush(fvad_engine *e, const int32_t *streams, int n);
+/* Average times (ms) over the timed pushes since the last
+ * fvad_engine_clear_times: ms_avg[0] k_hist_append, ms_avg[1] the capture pass
+ * (its four kernels); *n_runs (nullable): the timed passes.  Synchronises. */
+int fvad_engine_capture_times(fvad_engine *e, double *ms_avg, int *n_runs);
+
 /* Several engines on one GPU (e.g. a GPU's streams split into sub-partitions
  * that push concurrently): e runs its k_prep3 (FVAD_SHARE_PREP) and / or its
  * device VADMachine kernels (FVAD_SHARE_SIDE, both engines with machines
