@@ -5,10 +5,11 @@
 // What it computes is rnnoise's compute_rnn (rnn.c, called from
 // rnnoise_process_frame at Denoiser.zig:60) plus the recurrent feature work
 // k_rnn3 does (cepstral memory, deltas, spectral variability, gain smoothing).
-// The features, activations, state updates and gain smoothing are the same f32
-// expressions as k_rnn3; only the gate sums change: every neuron's sum
-// b + sum_j W[j] in[j] is a v_mfma_f32_16x16x32_f16 chain with the int8 weights
-// as exact f16 values and the inputs rounded to f16 (f32 accumulation).  That
+// The features and gain smoothing are k_rnn3's own code (fvad_rnnfeat.h), the
+// activations and state updates the same f32 expressions; only the gate sums
+// change: every neuron's sum b + sum_j W[j] in[j] is a v_mfma_f32_16x16x32_f16
+// chain with the int8 weights as exact f16 values and the inputs rounded to
+// f16 (f32 accumulation).  That
 // is the stated tolerance of configs[4] (vad |d| <= 2e-2,
 // segments identical or reported), not bit-exactness.
 //
@@ -40,6 +41,8 @@
 
 #include "fvad_device.h"
 #include "fvad_internal.h"
+#include "fvad_launch.h"
+#include "fvad_rnnfeat.h"
 #include "fvad_staged.h"
 #include "fvad_staged_dev.h"
 #include "fvad_wavedev.h"
@@ -167,8 +170,7 @@ using namespace g16;
 
 constexpr int kGS = 16;      // stream columns per workgroup (MFMA N)
 constexpr int kGNT = 512;    // 8 waves, 2 per SIMD (fragments + operands need > 128 VGPRs)
-constexpr int kPfW = 30;     // raw feature words per stream and frame: Lyf[22], f34[7], silence
-constexpr int kFeatItems = kGS * (kBands + 7 + kCeps);
+constexpr int kFeatItems = kGS * rnnfeat::kItems;
 
 constexpr int kDzrFrags = 12 * 7;  // denoise z|r: the largest matrix lives in LDS (84 KB)
 constexpr int kFr = 20;            // register fragment slots (see the wave plan)
@@ -179,14 +181,8 @@ struct LdsCore {
   alignas(16) float zv[kGS][28], zn[kGS][52], zd[kGS][100];  // update gates z of the frame
   alignas(16) float gout[kGS][24];
   alignas(16) float bias[kBiasRows];
-  float tt[204];
-  float ceps[kGS][kCeps * kBands];
-  float dist[kGS][kCeps * kCeps];
-  float lastg[kGS][kBands];
-  float pf[2][kGS][kPfW];  // raw features of frame f in pf[f & 1]
-  int act[8][kGS];
-  int memid[kGS], nfs[kGS];
-  long long fbase[kGS];
+  RecurLds<kGS> R;            // tt, cepstral memory and distances, lastg, act, memid, nfs, fbase
+  float pf[2][kGS][kRawFeat];  // raw features of frame f in pf[f & 1]
 };
 // k_gru16: the denoise z|r fragments in LDS
 struct LdsSplit : LdsCore {
@@ -265,7 +261,7 @@ __device__ __forceinline__ void epi_zr(LT &L, const f4 &acc, int tile, int lane,
   const int s = lane & 15, r0 = tile * 16 + 4 * (lane >> 4);
   float v[4];
 #pragma unroll
-  for (int i = 0; i < 4; i++) v[i] = sigmoid(L.tt, kWs * acc[i]);
+  for (int i = 0; i < 4; i++) v[i] = sigmoid(L.R.tt, kWs * acc[i]);
   if (r0 < N) {
     *reinterpret_cast<f4 *>(&Z[s][r0]) = f4{v[0], v[1], v[2], v[3]};
   } else {
@@ -291,7 +287,7 @@ __device__ __forceinline__ void epi_h(LT &L, const f4 &acc, int tile, int lane, 
   const f4 z = *reinterpret_cast<const f4 *>(&Z[s][r0]);
   float n[4];
 #pragma unroll
-  for (int i = 0; i < 4; i++) n[i] = z[i] * st[i] + (1 - z[i]) * activate(L.tt, act, kWs * acc[i]);
+  for (int i = 0; i < 4; i++) n[i] = z[i] * st[i] + (1 - z[i]) * activate(L.R.tt, act, kWs * acc[i]);
   *reinterpret_cast<f4 *>(&S[s][r0]) = f4{n[0], n[1], n[2], n[3]};
   put_h4(&L.op[s][dst + r0], n[0], n[1], n[2], n[3]);
 }
@@ -348,8 +344,8 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
   // tile offsets derived from it stay out of the VGPRs (k_fused16's 128
   // would not hold them; k_gru16 0.532 -> 0.514 ms, interleaved A/B)
   const int W = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int sb = blockIdx.x * kSpw;
-  auto sok = [&](int s) { return s < kSpw && sb + s < a.n_streams; };
+  const int sb = blockIdx.x * kSpw, n_own = own_streams(a, sb, kSpw);
+  auto &R = L.R;
   const int *ra = a.rnn_act;
   half8 fr[kFr];
   {
@@ -399,32 +395,12 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
   // ---- LDS: operand rows, states, tables
   for (int i = tid; i < S * kRowHalf; i += NT) (&L.op[0][0])[i] = (_Float16)0;
   for (int i = tid; i < kBiasRows; i += NT) L.bias[i] = a.gru16_bias[i];
-  for (int i = tid; i < 201; i += NT) L.tt[i] = a.plan->tansig[i];
-  for (int idx = tid; idx < S * kCeps * kBands; idx += NT) {
-    const int s = idx / (kCeps * kBands), i = idx - s * (kCeps * kBands);
-    L.ceps[s][i] = sok(s) ? a.state[(size_t)(sb + s) * st::kWords + st::kCepsMem + i] : 0.0f;
-  }
-  for (int idx = tid; idx < S * kCeps * kCeps; idx += NT) {
-    const int s = idx / (kCeps * kCeps), i = idx - s * (kCeps * kCeps);
-    L.dist[s][i] = sok(s) ? a.state[(size_t)(sb + s) * st::kWords + st::kCepsDist + i] : 0.0f;
-  }
-  for (int idx = tid; idx < S * kBands; idx += NT) {
-    const int s = idx / kBands, i = idx - s * kBands;
-    L.lastg[s][i] = sok(s) ? a.state[(size_t)(sb + s) * st::kWords + st::kLastG + i] : 0.0f;
-  }
-  if (tid < 8 * S) L.act[tid / S][tid % S] = 0;
-  if (tid < S) {
-    const int s = sb + tid;
-    const bool ok = sok(tid);
-    L.memid[tid] = ok ? reinterpret_cast<const int *>(a.state)[(size_t)s * st::kWords + st::kMemId] : 0;
-    L.nfs[tid] = ok ? ticks_of(a, s) * a.n_channels : 0;
-    L.fbase[tid] = (long long)s * a.V;
-  }
+  R.load(a, sb, n_own, tid, NT);
   __syncthreads();
   // states before frame 0 = the versions of frame -1 (vad 2, noise 1)
   for (int idx = tid; idx < S * 96; idx += NT) {
     const int s = idx / 96, i = idx - s * 96;
-    const bool ok = sok(s);
+    const bool ok = s < n_own;
     const float *stp = a.state + (size_t)(sb + s) * st::kWords;
     if (i < 24) {
       L.sv[s][i] = ok ? stp[st::kVadGru + i] : 0.0f;
@@ -437,89 +413,38 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
     L.sd[s][i] = ok ? stp[st::kDenGru + i] : 0.0f;
     L.op[s][seg_half(kSd, 0) + i] = (_Float16)L.sd[s][i];
   }
-  int maxnf = 0;
-#pragma unroll
-  for (int s = 0; s < S; s++) maxnf = max(maxnf, L.nfs[s]);
-  // raw feature lane (s, i): i < 22 Lyf, 22..28 f34, 29 silence (the flag's
-  // bits, nonzero = silent: no wait for the load where it is issued)
-  // (k_fused16: the f34 words come from pspec below, not from HBM)
-  const int pfs = tid / kPfW, pfi = tid - pfs * kPfW;
-  const bool pf_lane = tid < S * kPfW && !(kFuse && pfi >= kBands && pfi < kBands + 7);
-  auto fetch = [&](int v) -> float {
-    if (!pf_lane || v >= L.nfs[pfs]) return 1.0f;  // past the end: treated as silent (inactive)
-    const long long f = L.fbase[pfs] + v;
-    if (pfi < kBands) return a.Lyf[f * kBands + pfi];
-    if (pfi < kBands + 7) return a.f34[f * 8 + (pfi - kBands)];
-    return __int_as_float(a.silence[f]);
-  };
-  // features of frame f from L.pf (k_rnn3's F-C: cepstral memory, deltas,
-  // 34..40, the new distance row) into feature version f % 5; item (s, i)
+  const int maxnf = R.max_frames();
+  // raw feature lane (s, i) (raw_feature; k_fused16: the f34 words come from
+  // pspec below, not from HBM)
+  const int pfs = tid / kRawFeat, pfi = tid - pfs * kRawFeat;
+  const bool pf_lane = tid < S * kRawFeat && !(kFuse && pfi >= kBands && pfi < kBands + 7);
+  auto fetch = [&](int v) -> float { return pf_lane ? raw_feature(a, R, pfs, pfi, v) : 1.0f; };
+  // features of frame f from L.pf[f & 1] into feature version f % 5 (k_rnn3's F-C); item (s, i)
   auto feat_c = [&](int f, int idx) {
-    const int s = idx / (kBands + 7 + kCeps), i = idx - s * (kBands + 7 + kCeps);
-    const bool valid = f < L.nfs[s];
-    const bool on = valid && __float_as_int(L.pf[f & 1][s][kPfW - 1]) == 0;
-    if (i == 0) {
-      L.act[f & 7][s] = on;
-      if (valid && !on) a.vadf[L.fbase[s] + f] = 0;  // silent: X passes through, state untouched
-    }
-    if (!on) return;
-    _Float16 *feat = &L.op[s][seg_half(g16::kFeat, f % 5)];
-    const int mi = L.memid[s];
-    const float *c0 = L.pf[f & 1][s];
-    if (i < kBands) {
-      L.ceps[s][mi * kBands + i] = c0[i];
-      if (i < 6) {
-        const float *c1 = L.ceps[s] + ((mi < 1) ? kCeps + mi - 1 : mi - 1) * kBands;
-        const float *c2 = L.ceps[s] + ((mi < 2) ? kCeps + mi - 2 : mi - 2) * kBands;
-        feat[i] = (_Float16)(c0[i] + c1[i] + c2[i]);
-        feat[kBands + i] = (_Float16)(c0[i] - c2[i]);
-        feat[kBands + 6 + i] = (_Float16)(c0[i] - 2 * c1[i] + c2[i]);
-      } else {
-        feat[i] = (_Float16)c0[i];
-      }
-    } else if (i < kBands + 7) {
-      feat[34 + i - kBands] = (_Float16)c0[i];
-    } else {
-      const int j = i - kBands - 7;
-      if (j != mi) {
-        const float *cj = L.ceps[s] + j * kBands;
-        float d = 0;
-#pragma unroll
-        for (int k = 0; k < kBands; k++) {
-          const float tmp = c0[k] - cj[k];
-          d += tmp * tmp;
-        }
-        L.dist[s][mi * kCeps + j] = d;
-        L.dist[s][j * kCeps + mi] = d;
-      }
-    }
+    const int fo = seg_half(g16::kFeat, f % 5);
+    feat_items(R, a, f, idx, L.pf[f & 1], [&](int s, int k, float v) { L.op[s][fo + k] = (_Float16)v; });
   };
   // spectral variability of frame f (feature 41): lane (s, i) = (tid >> 3,
   // tid & 7) takes row i's minimum distance, lane i == 0 adds the 8 minima in
   // row order (the C loop's sum) and advances memid; 128 lanes (w0, w1)
   auto feat_d = [&](int f) {
     const int s = tid >> 3, i = tid & 7;
-    float mindist = 1e15f;
-#pragma unroll
-    for (int j = 0; j < kCeps; j++)
-      if (j != i) mindist = (mindist < L.dist[s][i * kCeps + j]) ? mindist : L.dist[s][i * kCeps + j];
+    const float mindist = rnnfeat::dist_row_min(R.dist[s], i);
     float m[kCeps];
 #pragma unroll
     for (int k = 0; k < kCeps; k++) m[k] = __shfl(mindist, (lane & ~7) + k);
-    if (i != 0 || !L.act[f & 7][s]) return;
+    if (i != 0 || !R.act[f & 7][s]) return;
     float sv = 0;
 #pragma unroll
     for (int k = 0; k < kCeps; k++) sv += m[k];
-    L.op[s][seg_half(g16::kFeat, f % 5) + 41] = (_Float16)(float)(sv / kCeps - 2.1);
-    int mid = L.memid[s] + 1;
-    if (mid == kCeps) mid = 0;
-    L.memid[s] = mid;
+    L.op[s][seg_half(g16::kFeat, f % 5) + 41] = (_Float16)rnnfeat::spec_variability(sv);
+    R.memid[s] = rnnfeat::memid_next(R.memid[s]);
   };
   // k_fused16: waves kGNT / 64 + j are stream j's pitch-spectrum waves (their
   // loop is below the GRU's); pframe(v): stream j's frame v, or -1
   const bool fft_wave = kFuse && W >= kGNT / 64;
   const int fj = W - kGNT / 64;
-  auto pframe = [&](int v) { return (kFuse && sok(fj) && v < L.nfs[fj]) ? (int)(L.fbase[fj] + v) : -1; };
+  auto pframe = [&](int v) { return (kFuse && fj < n_own && v < R.nfs[fj]) ? (int)(R.fbase[fj] + v) : -1; };
   // prologue: features of frame 0, raw features of frame 1 staged
   if (pf_lane) L.pf[0][pfs][pfi] = fetch(0);
   if constexpr (kFuse) {
@@ -550,23 +475,11 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
     const int r0 = tile * 16 + 4 * (lane >> 4);
 #pragma unroll
     for (int i = 0; i < 4; i++)
-      if (r0 + i < kBands) L.gout[col][r0 + i] = activate(L.tt, ra[7], kWs * acc[i]);
+      if (r0 + i < kBands) L.gout[col][r0 + i] = activate(L.R.tt, ra[7], kWs * acc[i]);
   };
-  auto on_of = [&](int f) { return L.act[f & 7][col] != 0; };
+  auto on_of = [&](int f) { return R.act[f & 7][col] != 0; };
   STAMP_INIT();
-#ifdef FVAD_STAMPS
-  // per-wave busy cycles of each phase (lane 0 of every wave): stamps[0..7] A, [8..15] B
-  unsigned long long wacc[2] = {0, 0}, wt0 = 0;
-#define WSTAMP_BEGIN() wt0 = __builtin_amdgcn_s_memtime()
-#define WSTAMP_END(p) wacc[p] += __builtin_amdgcn_s_memtime() - wt0
-#else
-#define WSTAMP_BEGIN() \
-  do {                 \
-  } while (0)
-#define WSTAMP_END(p) \
-  do {                \
-  } while (0)
-#endif
+  PHASE_INIT();  // per-wave busy cycles of each phase (lane 0 of every wave): stamps[0..7] A, [8..15] B
   if (fft_wave) {
     // k_fused16's pitch-spectrum waves, in step with the GRU waves' barriers
     // (two per superstep): at superstep u the transform of frame u + 2 in
@@ -582,7 +495,7 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
       for (int u = 0; u < maxnf + 4; u++) {
         const int f = f2, pit = pit2;  // frame u + 2
         asm volatile("" : "+v"(lane));  // lane-derived table addresses: per step, not held (as the GRU loop)
-        WSTAMP_BEGIN();
+        PHASE_BEGIN();
         float exl = 0.0f;
         if (f >= 0) {
           PspecIn in;
@@ -599,14 +512,14 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
         f3 = -1;
 #endif
         pit3 = f3 >= 0 ? a.pitch[f3] : 0;
-        WSTAMP_END(0);
+        PHASE_END(0);
         lds_sync();
-        WSTAMP_BEGIN();
+        PHASE_BEGIN();
         if (f >= 0) {
           const float v34 = pspec_features(a, f, pit, L.tb, L.Rg[fj], lane, exl);
           if (lane < 7) L.pf[u & 1][fj][kBands + lane] = v34;
         }
-        WSTAMP_END(1);
+        PHASE_END(1);
         lds_sync();
       }
     }
@@ -626,7 +539,7 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
     const float pf_next = fetch(u + 2);  // raw features of u + 2, staged at the end of phase B
     // ---- phase A: z|r gates of vad(u-1), noise(u-2), denoise(u-3); dense(u),
     // vad_out(u-2), den_out(u-4); features(u+1)
-    WSTAMP_BEGIN();
+    PHASE_BEGIN();
     // waves 5..7 carry the longest phase-A chains (stamps): they issue first
     // (k_gru16 0.512 -> 0.505 ms interleaved; w5 and w7 only 0.512, phase B's
     // longest waves raised as well 0.514-0.523)
@@ -642,7 +555,7 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
         if (r0 < 24) {
           float v[4];
 #pragma unroll
-          for (int i = 0; i < 4; i++) v[i] = activate(L.tt, ra[0], kWs * acc[i]);
+          for (int i = 0; i < 4; i++) v[i] = activate(L.R.tt, ra[0], kWs * acc[i]);
           put_h4(&L.op[col][seg_half(kDense, u % 3) + r0], v[0], v[1], v[2], v[3]);
         }
       }
@@ -653,7 +566,7 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
       if (live(fN)) {
         epi_zr<48>(L, mma_job<2, 3>(fr, 0, L, dzs, lane, fN), 0, lane, L.zn, L.sn, kRsn);
         const f4 acc = mma_job<7, 8>(fr, 0, L, dzs, lane, fN);
-        if (lane < 16 && on_of(fN)) a.vadf[L.fbase[col] + fN] = activate(L.tt, ra[8], kWs * acc[0]);
+        if (lane < 16 && on_of(fN)) a.vadf[R.fbase[col] + fN] = activate(L.R.tt, ra[8], kWs * acc[0]);
       }
     } else if (W < 7) {
       if (live(fN)) {
@@ -675,10 +588,10 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
           feat_c(u + 1, (k / kLight) * kIt + k % kLight);
     }
     if (W >= 5) __builtin_amdgcn_s_setprio(0);
-    WSTAMP_END(0);
+    PHASE_END(0);
     lds_sync();
     RSTAMP(0);
-    WSTAMP_BEGIN();
+    PHASE_BEGIN();
     // ---- phase B: candidates of vad(u-1), noise(u-2), denoise(u-3); gains(u-4);
     // spectral variability(u+1); raw features of u+2 staged
     if (W < 6) {
@@ -695,19 +608,12 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
       if (W == 4 && live(fN))
         epi_h<48>(L, mma_job<15, 4>(fr, 1, L, dzs, lane, fN), 1, lane, ra[4], L.zn, L.sn, seg_half(kSn, fN & 1), on_of(fN));
       if (W < 2 && u + 1 < maxnf) feat_d(u + 1);
-      // gain smoothing g = max(g, .6*lastg) (denoise.c), frame u-4, on w2, w3, w5
+      // gain smoothing (gains_of), frame u-4, on w2, w3, w5
       if ((W == 2 || W == 3 || W == 5) && live(fO)) {
         const int gl = lane + 64 * (W == 5 ? 2 : W - 2);
         for (int idx = gl; idx < S * kBands; idx += 3 * 64) {
           const int s = idx / kBands, i = idx - s * kBands;
-          if (!L.act[fO & 7][s]) continue;
-          const long long f = L.fbase[s] + fO;
-          const float gi = L.gout[s][i];
-          const float al = .6f * L.lastg[s][i];
-          const float gsm = (gi > al) ? gi : al;
-          L.lastg[s][i] = gsm;
-          a.gr[f * kBands + i] = gi;
-          a.gs[f * kBands + i] = gsm;
+          gains_of(R, a, fO, s, i, L.gout[s][i]);
         }
       }
     } else {
@@ -723,43 +629,28 @@ __device__ __forceinline__ void gru16_body(const StagedArgs &a) {
       }
     }
     if (pf_lane) L.pf[u & 1][pfs][pfi] = pf_next;  // frame u + 2: read from the next phase A on
-    WSTAMP_END(1);
+    PHASE_END(1);
     lds_sync();
     RSTAMP(1);
   }
   }  // GRU waves
 #ifdef FVAD_STAMPS
   if (lane == 0 && a.stamps) {  // k_fused16's pitch-spectrum waves: [16..23] A, [24..31] B
-    atomicAdd(&a.stamps[W < 8 ? W : W + 8], wacc[0]);
-    atomicAdd(&a.stamps[W < 8 ? 8 + W : W + 16], wacc[1]);
+    atomicAdd(&a.stamps[W < 8 ? W : W + 8], ph_acc[0]);
+    atomicAdd(&a.stamps[W < 8 ? 8 + W : W + 16], ph_acc[1]);
   }
 #endif
-#undef WSTAMP_BEGIN
-#undef WSTAMP_END
   STAMP_FLUSH(48, 2);
   // ---- state write-back (streams that ran at least one frame)
-  for (int idx = tid; idx < S * kCeps * kBands; idx += NT) {
-    const int s = idx / (kCeps * kBands), i = idx - s * (kCeps * kBands);
-    if (sok(s) && L.nfs[s] > 0) a.state[(size_t)(sb + s) * st::kWords + st::kCepsMem + i] = L.ceps[s][i];
-  }
-  for (int idx = tid; idx < S * kCeps * kCeps; idx += NT) {
-    const int s = idx / (kCeps * kCeps), i = idx - s * (kCeps * kCeps);
-    if (sok(s) && L.nfs[s] > 0) a.state[(size_t)(sb + s) * st::kWords + st::kCepsDist + i] = L.dist[s][i];
-  }
-  for (int idx = tid; idx < S * kBands; idx += NT) {
-    const int s = idx / kBands, i = idx - s * kBands;
-    if (sok(s) && L.nfs[s] > 0) a.state[(size_t)(sb + s) * st::kWords + st::kLastG + i] = L.lastg[s][i];
-  }
+  R.store(a, sb, n_own, tid, NT);
   for (int idx = tid; idx < S * 96; idx += NT) {
     const int s = idx / 96, i = idx - s * 96;
-    if (!sok(s) || L.nfs[s] <= 0) continue;
+    if (!R.ran(s, n_own)) continue;
     float *stp = a.state + (size_t)(sb + s) * st::kWords;
     if (i < 24) stp[st::kVadGru + i] = L.sv[s][i];
     if (i < 48) stp[st::kNoiseGru + i] = L.sn[s][i];
     stp[st::kDenGru + i] = L.sd[s][i];
   }
-  if (tid < S && sok(tid) && L.nfs[tid] > 0)
-    reinterpret_cast<int *>(a.state)[(size_t)(sb + tid) * st::kWords + st::kMemId] = L.memid[tid];
 }
 
 __global__ void __launch_bounds__(kGNT) k_gru16(StagedArgs a) { gru16_body<8, false>(a); }
@@ -767,10 +658,10 @@ __global__ void __launch_bounds__(kFNT) k_fused16(StagedArgs a) { gru16_body<8, 
 
 hipError_t launch_gru16(const StagedArgs &a, hipStream_t stream) {
   if (a.fuse16)
-    hipLaunchKernelGGL(k_fused16, dim3((a.n_streams + 7) / 8), dim3(kFNT), 0, stream, a);
+    FVAD_KERNEL_TRY(k_fused16, dim3((a.n_streams + 7) / 8), dim3(kFNT), 0, stream, a);
   else
-    hipLaunchKernelGGL(k_gru16, dim3((a.n_streams + 7) / 8), dim3(kGNT), 0, stream, a);
-  return hipGetLastError();
+    FVAD_KERNEL_TRY(k_gru16, dim3((a.n_streams + 7) / 8), dim3(kGNT), 0, stream, a);
+  return hipSuccess;
 }
 
 }  // namespace fvad

@@ -6,6 +6,7 @@
 #include "fvad_device.h"
 #include "fvad_internal.h"
 #include "fvad_launch.h"
+#include "fvad_rnnfeat.h"
 #include "fvad_staged.h"
 #include "fvad_staged_dev.h"
 
@@ -20,7 +21,6 @@ namespace fvad {
 // read.  GRU inputs are read in place from their segments (no concatenation
 // copies) and GRU states live in rings indexed by frame (no copy-back phase).
 // ---------------------------------------------------------------------------
-constexpr int kRnnPf = 30; // prefetched words per stream and frame: Lyf[22], f34[7], silence
 
 // acc[q] += w[j] * v[j][s0 + q] for the n terms of one segment, C order.  The
 // segment's weights start 8-byte aligned: 8 terms = one 64-bit LDS read plus
@@ -297,132 +297,55 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
     alignas(16) float zpre[192 * S];  // denoise z|r: b + the vad-state segment of the frame P1 continues
     alignas(16) float gout[2][22 * S];  // denoise_output of frame f in slot f & 1
     alignas(16) float vo[S];  // vad_output of the frame P2 computed last
-    float tt[204];
-    float ceps[S][kCeps * kBands];
-    float dist[S][kCeps * kCeps];
-    float lastg[S][kBands];
-    float pf[S][kRnnPf];  // features of the frame the next F-C stage reads
-    int act[8][S];        // frame f in slot f & 7: valid and not silent
-    int memid[S], nfs[S];
-    long long fbase[S];
+    RecurLds<S> R;           // tt, cepstral memory and distances, lastg, act, memid, nfs, fbase
+    float pf[S][kRawFeat];   // raw features of the frame the next F-C stage reads
     alignas(16) int8_t W[rnnimg::kBytes];
   };
   __shared__ Lds L;
   const int tid = threadIdx.x;
-  const int sb = blockIdx.x * S;
+  const int sb = blockIdx.x * S, n_own = own_streams(a, sb, S);
+  auto &R = L.R;
   const int *ra = a.rnn_act;
   {
     const int4 *src = reinterpret_cast<const int4 *>(a.rnn_img);
     int4 *dst = reinterpret_cast<int4 *>(L.W);
     for (int i = tid; i < rnnimg::kBytes / 16; i += NT) dst[i] = src[i];
-    for (int i = tid; i < 201; i += NT) L.tt[i] = a.plan->tansig[i];
   }
-  for (int idx = tid; idx < S * kCeps * kBands; idx += NT) {
-    const int s = idx / (kCeps * kBands), i = idx - s * (kCeps * kBands);
-    L.ceps[s][i] = (sb + s < a.n_streams) ? a.state[(size_t)(sb + s) * st::kWords + st::kCepsMem + i] : 0.0f;
-  }
-  for (int idx = tid; idx < S * kCeps * kCeps; idx += NT) {
-    const int s = idx / (kCeps * kCeps), i = idx - s * (kCeps * kCeps);
-    L.dist[s][i] = (sb + s < a.n_streams) ? a.state[(size_t)(sb + s) * st::kWords + st::kCepsDist + i] : 0.0f;
-  }
-  for (int idx = tid; idx < S * kBands; idx += NT) {
-    const int s = idx / kBands, i = idx - s * kBands;
-    L.lastg[s][i] = (sb + s < a.n_streams) ? a.state[(size_t)(sb + s) * st::kWords + st::kLastG + i] : 0.0f;
-  }
+  R.load(a, sb, n_own, tid, NT);
   // states before frame 0 = "frame -1": gv slot 3, gn / gd slot 1
   for (int idx = tid; idx < S * 96; idx += NT) {
     const int s = idx / 96, i = idx - s * 96;
-    const bool ok = sb + s < a.n_streams;
+    const bool ok = s < n_own;
     const float *stp = a.state + (size_t)(sb + s) * st::kWords;
     if (i < 24) L.gvT[3][i * S + s] = ok ? stp[st::kVadGru + i] : 0.0f;
     if (i < 48) L.gnT[1][i * S + s] = ok ? stp[st::kNoiseGru + i] : 0.0f;
     L.gdT[1][i * S + s] = ok ? stp[st::kDenGru + i] : 0.0f;
   }
-  if (tid < 8 * S) L.act[tid / S][tid % S] = 0;
-  if (tid < S) {
-    const int s = sb + tid;
-    const bool ok = s < a.n_streams;
-    L.memid[tid] = ok ? reinterpret_cast<const int *>(a.state)[(size_t)s * st::kWords + st::kMemId] : 0;
-    L.nfs[tid] = ok ? ticks_of(a, s) * a.n_channels : 0;
-    L.fbase[tid] = (long long)s * a.V;
-  }
   __syncthreads();
-  int maxnf = 0;
-#pragma unroll
-  for (int s = 0; s < S; s++) maxnf = max(maxnf, L.nfs[s]);
-  // prefetch lane (s, i): i < 22 Lyf, 22..28 f34, 29 silence (the flag's bits,
-  // nonzero = silent: converting it here would wait for the load at the top of
-  // every step, before the lane's P1 role)
-  const int pfs = tid / kRnnPf, pfi = tid - pfs * kRnnPf;
-  const bool pf_lane = tid < S * kRnnPf;
-  auto fetch = [&](int v) -> float {
-    if (!pf_lane || v >= L.nfs[pfs]) return 1.0f;  // past the end: treated as silent (inactive)
-    const long long f = L.fbase[pfs] + v;
-    if (pfi < kBands) return a.Lyf[f * kBands + pfi];
-    if (pfi < kBands + 7) return a.f34[f * 8 + (pfi - kBands)];
-    return __int_as_float(a.silence[f]);
-  };
-  // F-C: frame f's features from L.pf (cepstral memory, deltas, 34..40, the
-  // new distance row); item (s, i), i < 37; item i == 0 records act(f)
+  const int maxnf = R.max_frames();
+  // prefetch lane (s, i) of the raw features (raw_feature: the silence word
+  // unconverted, or the lane would wait for the load at the top of every step,
+  // before its P1 role)
+  const int pfs = tid / kRawFeat, pfi = tid - pfs * kRawFeat;
+  const bool pf_lane = tid < S * kRawFeat;
+  auto fetch = [&](int v) -> float { return pf_lane ? raw_feature(a, R, pfs, pfi, v) : 1.0f; };
+  // F-C: frame f's features from L.pf into featT slot f & 7; item (s, i), i < 37
   auto feat_c = [&](int f, int idx) {
-    const int s = idx / (kBands + 7 + kCeps), i = idx - s * (kBands + 7 + kCeps);
-    const bool valid = f < L.nfs[s];
-    const bool on = valid && __float_as_int(L.pf[s][kRnnPf - 1]) == 0;
-    if (i == 0) {
-      L.act[f & 7][s] = on;
-      if (valid && !on) a.vadf[L.fbase[s] + f] = 0;  // silent: X passes through, state untouched
-    }
-    if (!on) return;
     float *featT = L.featT[f & 7];
-    const int mi = L.memid[s];
-    const float *c0 = L.pf[s];  // ceps_0 (the row being written at memid)
-    if (i < kBands) {
-      L.ceps[s][mi * kBands + i] = c0[i];
-      if (i < 6) {
-        const float *c1 = L.ceps[s] + ((mi < 1) ? kCeps + mi - 1 : mi - 1) * kBands;
-        const float *c2 = L.ceps[s] + ((mi < 2) ? kCeps + mi - 2 : mi - 2) * kBands;
-        featT[i * S + s] = c0[i] + c1[i] + c2[i];
-        featT[(kBands + i) * S + s] = c0[i] - c2[i];
-        featT[(kBands + 6 + i) * S + s] = c0[i] - 2 * c1[i] + c2[i];
-      } else {
-        featT[i * S + s] = c0[i];
-      }
-    } else if (i < kBands + 7) {
-      featT[(34 + i - kBands) * S + s] = c0[i];
-    } else {
-      const int j = i - kBands - 7;
-      if (j != mi) {
-        const float *cj = L.ceps[s] + j * kBands;
-        float d = 0;
-#pragma unroll
-        for (int k = 0; k < kBands; k++) {
-          const float tmp = c0[k] - cj[k];
-          d += tmp * tmp;
-        }
-        L.dist[s][mi * kCeps + j] = d;
-        L.dist[s][j * kCeps + mi] = d;
-      }
-    }
+    feat_items(R, a, f, idx, L.pf, [&](int s, int k, float v) { featT[k * S + s] = v; });
   };
   // F-D: spectral variability of frame f, stream s
   auto feat_d = [&](int f, int s) {
-    if (!L.act[f & 7][s]) return;
+    if (!R.act[f & 7][s]) return;
     float sv = 0;
-    for (int i = 0; i < kCeps; i++) {
-      float mindist = 1e15f;
-      for (int j = 0; j < kCeps; j++)
-        if (j != i) mindist = (mindist < L.dist[s][i * kCeps + j]) ? mindist : L.dist[s][i * kCeps + j];
-      sv += mindist;
-    }
-    L.featT[f & 7][41 * S + s] = (float)(sv / kCeps - 2.1);
-    int mid = L.memid[s] + 1;
-    if (mid == kCeps) mid = 0;
-    L.memid[s] = mid;
+    for (int i = 0; i < kCeps; i++) sv += rnnfeat::dist_row_min(R.dist[s], i);
+    L.featT[f & 7][41 * S + s] = rnnfeat::spec_variability(sv);
+    R.memid[s] = rnnfeat::memid_next(R.memid[s]);
   };
   // prologue: features of frame 0 (its spectral variability: P1 of step 0)
   if (pf_lane) L.pf[pfs][pfi] = fetch(0);
   __syncthreads();
-  for (int idx = tid; idx < S * (kBands + 7 + kCeps); idx += NT) feat_c(0, idx);
+  for (int idx = tid; idx < S * rnnfeat::kItems; idx += NT) feat_c(0, idx);
   __syncthreads();
   // P1 wave plan (w = tid >> 6).  Waves w, w+4, w+8, w+12 share a SIMD under
   // the cyclic wave placement, so the heavy roles are spread over the four
@@ -450,48 +373,18 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
   // stretched the other roles: 15.3 vs 14.6 k per phase.)
   [[maybe_unused]] constexpr int kP2Den = 0, kP2Noise = 192, kP2Vad = 320, kP2Dense = 448, kP2Out = 256, kP2VadOut = 512,
                 kP2Feat = 576;
-  constexpr int kFeatItems = S * (kBands + 7 + kCeps);
+  constexpr int kFeatItems = S * rnnfeat::kItems;
   static_assert(kP2Feat + kFeatItems <= 14 * 64 && 96 * kR3G == 192 && 48 * kR3G <= 128 && 22 * kR3G <= 64 &&
                     24 * kR3G <= 64,
                 "P2 wave plan");
   STAMP_INIT();
-#ifdef FVAD_STAMPS
-  // role finish times: the first thread of each role adds (its role's end -
-  // its phase start) to stamps[2 + role]
-  unsigned long long ph0 = 0, racc = 0;
-  int rslot = -1;
-  {
-    const int l1[5] = {kP1Den, kP1Noise, kP1Vad, kP1Var, kP1Gain};
-    const int l2[7] = {kP2Den, kP2Noise, kP2Vad, kP2Dense, kP2Out, kP2VadOut, kP2Feat};
-    for (int i = 0; i < 5; i++)
-      if (tid == l1[i]) rslot = i;
-    for (int i = 0; i < 7; i++)
-      if (tid == l2[i]) rslot = (rslot < 0) ? 16 + i : rslot;  // tid 0 / 384 lead in both phases
-  }
-  unsigned long long racc2[2] = {0, 0};
-#define ROLE_BEGIN() ph0 = __builtin_amdgcn_s_memtime()
-#define ROLE_END(ph) racc2[ph] += __builtin_amdgcn_s_memtime() - ph0
-#else
-#define ROLE_BEGIN() \
-  do {               \
-  } while (0)
-#define ROLE_END(ph) \
-  do {               \
-  } while (0)
-#endif
-  // gain smoothing g = max(g, .6*lastg) (denoise.c) of frame f5 on lanes
-  // i0, i0 + n, ...; reads denoise_output slot f5 & 1
+  PHASE_INIT();  // a role's finish time: its first thread's busy cycles of the phase
+  // gain smoothing (gains_of) of frame f5 on lanes i0, i0 + n, ...; reads
+  // denoise_output slot f5 & 1
   auto gains = [&](int f5, int i0, int n) {
     for (int idx = i0; f5 >= 0 && idx < S * kBands; idx += n) {
       const int s = idx / kBands, i = idx - s * kBands;
-      if (!L.act[f5 & 7][s]) continue;
-      const long long f = L.fbase[s] + f5;
-      const float gi = L.gout[f5 & 1][i * S + s];
-      const float al = .6f * L.lastg[s][i];
-      const float gsm = (gi > al) ? gi : al;
-      L.lastg[s][i] = gsm;
-      a.gr[f * kBands + i] = gi;
-      a.gs[f * kBands + i] = gsm;
+      gains_of(R, a, f5, s, i, L.gout[f5 & 1][i * S + s]);
     }
   };
   for (int t = 0; t <= maxnf + 4; t++) {
@@ -501,7 +394,7 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
     int tq = tid;
     asm volatile("" : "+v"(tq));
     const int fv = t - 1, fn = t - 2, fd = t - 3;
-    ROLE_BEGIN();
+    PHASE_BEGIN();
     // frame t+1's raw features, staged at the end of P1 for P2's feat_c:
     // issued here, so no load is outstanding across a step boundary (a
     // loop-carried register would make the step's last barrier wait for it)
@@ -513,15 +406,15 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
     if (wv < 6) {
       if (fd >= 0 && fd < maxnf)
         rnn_gates<FMA, 5, S, G, 0, 5>(L.W, RnnIn{L.gvT[fd & 3], L.gnT[fd & 1], L.featT[fd & 7]}, L.gdT[(fd + 1) & 1],
-                                 L.zrd, kActSigmoid, L.tt, tq, L.zpre);
+                                 L.zrd, kActSigmoid, R.tt, tq, L.zpre);
     } else if (wv == 6 || wv == 7 || wv == 10) {
       if (fn >= 0 && fn < maxnf)
         rnn_gates<FMA, 3, S, G, 0>(L.W, RnnIn{L.doutT[fn & 3], L.gvT[fn & 3], L.featT[fn & 7]}, L.gnT[(fn + 1) & 1], L.zrn,
-                              kActSigmoid, L.tt, (wv == 10 ? 128 : 64 * (wv - 6)) + ln);
+                              kActSigmoid, R.tt, (wv == 10 ? 128 : 64 * (wv - 6)) + ln);
     } else if (wv == 11 || wv == 14) {
       if (fv >= 0 && fv < maxnf)
         rnn_gates<FMA, 1, S, G, 0>(L.W, RnnIn{L.doutT[fv & 3], nullptr, nullptr}, L.gvT[(fv + 3) & 3], L.zrv, kActSigmoid,
-                              L.tt, (wv == 14 ? 64 : 0) + ln);
+                              R.tt, (wv == 14 ? 64 : 0) + ln);
     } else if (wv == 12 || wv == 13 || wv == 15) {
       // denoise candidate input prefixes of frame t-3
       if (fd >= 0 && fd < maxnf)
@@ -533,51 +426,51 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
       if (t < maxnf) feat_d(t, ln);
     } else if (wv == 8 && ln >= 48 && ln < 48 + S) {  // vad_output of frame t-3 (P2 of step t-1)
       const int s = ln - 48, fw = t - 3;
-      if (fw >= 0 && fw < maxnf && L.act[fw & 7][s]) a.vadf[L.fbase[s] + fw] = L.vo[s];
+      if (fw >= 0 && fw < maxnf && R.act[fw & 7][s]) a.vadf[R.fbase[s] + fw] = L.vo[s];
     }
-    ROLE_END(0);
+    PHASE_END(0);
     if (pf_lane) L.pf[pfs][pfi] = pf_now;
     lds_sync();
     RSTAMP(0);
-    ROLE_BEGIN();
+    PHASE_BEGIN();
     // ---- P2
     const int fo = t - 4;
     if (wv < 3) {
       if (fd >= 0 && fd < maxnf)
         rnn_cand<FMA, 6, S, G, 0, 2>(L.W, RnnIn{nullptr, nullptr, nullptr}, L.gdT[(fd + 1) & 1], L.zrd, L.gdT[fd & 1],
-                                L.act[fd & 7], ra[6], L.tt, tq, L.dhp[fd & 1]);
+                                R.act[fd & 7], ra[6], R.tt, tq, L.dhp[fd & 1]);
     } else if (wv == 3 || wv == 6) {
       if (FVAD_PRIO & 2) __builtin_amdgcn_s_setprio(3);
       if (fn >= 0 && fn < maxnf)
         rnn_cand<FMA, 4, S, G, 0>(L.W, RnnIn{L.doutT[fn & 3], L.gvT[fn & 3], L.featT[fn & 7]}, L.gnT[(fn + 1) & 1], L.zrn,
-                             L.gnT[fn & 1], L.act[fn & 7], ra[4], L.tt, (wv == 6 ? 64 : 0) + ln);
+                             L.gnT[fn & 1], R.act[fn & 7], ra[4], R.tt, (wv == 6 ? 64 : 0) + ln);
       if (FVAD_PRIO & 2) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 5) {
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(2);
       if (fv >= 0 && fv < maxnf)
         rnn_cand<FMA, 2, S, G, 0>(L.W, RnnIn{L.doutT[fv & 3], nullptr, nullptr}, L.gvT[(fv + 3) & 3], L.zrv, L.gvT[fv & 3],
-                             L.act[fv & 7], ra[2], L.tt, ln);
+                             R.act[fv & 7], ra[2], R.tt, ln);
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 7) {
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(2);
       if (t < maxnf)
-        rnn_gates<FMA, 0, S, G, 0>(L.W, RnnIn{L.featT[t & 7], nullptr, nullptr}, nullptr, L.doutT[t & 3], ra[0], L.tt, ln);
+        rnn_gates<FMA, 0, S, G, 0>(L.W, RnnIn{L.featT[t & 7], nullptr, nullptr}, nullptr, L.doutT[t & 3], ra[0], R.tt, ln);
       if (FVAD_PRIO & 8) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 4) {
       if (FVAD_PRIO & 4) __builtin_amdgcn_s_setprio(2);
       if (fo >= 0 && fo < maxnf)
-        rnn_gates<FMA, 7, S, G, 0>(L.W, RnnIn{L.gdT[fo & 1], nullptr, nullptr}, nullptr, L.gout[fo & 1], ra[7], L.tt, ln);
+        rnn_gates<FMA, 7, S, G, 0>(L.W, RnnIn{L.gdT[fo & 1], nullptr, nullptr}, nullptr, L.gout[fo & 1], ra[7], R.tt, ln);
       if (FVAD_PRIO & 4) __builtin_amdgcn_s_setprio(0);
     } else if (wv == 8 && ln < G) {
       // vad_output(t-2) -> L.vo, stored by the next step's P1
       if (fn >= 0 && fn < maxnf)
-        rnn_gates<FMA, 8, S, G, 0>(L.W, RnnIn{L.gvT[fn & 3], nullptr, nullptr}, nullptr, L.vo, ra[8], L.tt, ln);
+        rnn_gates<FMA, 8, S, G, 0>(L.W, RnnIn{L.gvT[fn & 3], nullptr, nullptr}, nullptr, L.vo, ra[8], R.tt, ln);
     } else if (tq >= kP2Feat && tq < kP2Feat + 192) {  // features of t+1 on waves 9..11
       for (int idx = tq - kP2Feat; t + 1 < maxnf && idx < kFeatItems; idx += 192) feat_c(t + 1, idx);
     } else if (wv >= 12 && wv <= 14) {  // denoise z|r of frame t-2: b + the vad-state segment
       const int fz = t - 2;
       if (fz >= 0 && fz < maxnf)
-        rnn_gates<FMA, 5, S, G, 192, 3>(L.W, RnnIn{L.gvT[fz & 3], nullptr, nullptr}, nullptr, nullptr, kActSigmoid, L.tt,
+        rnn_gates<FMA, 5, S, G, 192, 3>(L.W, RnnIn{L.gvT[fz & 3], nullptr, nullptr}, nullptr, nullptr, kActSigmoid, R.tt,
                                    tq - 768, L.zpre);
     } else if (wv == 15) {  // denoise candidates of frame t-2: b + the vad-state segment
       const int fz = t - 2;
@@ -587,7 +480,7 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
                                  nullptr, ln, L.dhp[fz & 1]);
       if (FVAD_PRIO & 128) __builtin_amdgcn_s_setprio(0);
     }
-    ROLE_END(1);
+    PHASE_END(1);
     lds_sync();
     RSTAMP(1);
   }
@@ -599,43 +492,26 @@ __device__ __forceinline__ void rnn3_body(StagedArgs a) {
     const int p1[5] = {kP1Den, kP1Noise, kP1Vad, kP1Var, kP1Gain};
     const int p2[7] = {kP2Den, kP2Noise, kP2Vad, kP2Dense, kP2Out, kP2VadOut, kP2Feat};
     for (int i = 0; i < 5; i++)
-      if (tid == p1[i]) atomicAdd(&a.stamps[2 + i], racc2[0]);
+      if (tid == p1[i]) atomicAdd(&a.stamps[2 + i], ph_acc[0]);
     for (int i = 0; i < 7; i++)
-      if (tid == p2[i]) atomicAdd(&a.stamps[8 + i], racc2[1]);
+      if (tid == p2[i]) atomicAdd(&a.stamps[8 + i], ph_acc[1]);
   }
   // every wave's busy cycles per phase (lane 0): stamps[64 + w] P1, [80 + w] P2
   if (a.stamps && (tid & 63) == 0) {
-    atomicAdd(&a.stamps[64 + (tid >> 6)], racc2[0]);
-    atomicAdd(&a.stamps[80 + (tid >> 6)], racc2[1]);
+    atomicAdd(&a.stamps[64 + (tid >> 6)], ph_acc[0]);
+    atomicAdd(&a.stamps[80 + (tid >> 6)], ph_acc[1]);
   }
-  (void)racc;
-  (void)rslot;
 #endif
-#undef ROLE_BEGIN
-#undef ROLE_END
   const int fin = maxnf - 1;  // the slots of the latest states ("frame -1" if there were none)
-  for (int idx = tid; idx < S * kCeps * kBands; idx += NT) {
-    const int s = idx / (kCeps * kBands), i = idx - s * (kCeps * kBands);
-    if (sb + s < a.n_streams && L.nfs[s] > 0) a.state[(size_t)(sb + s) * st::kWords + st::kCepsMem + i] = L.ceps[s][i];
-  }
-  for (int idx = tid; idx < S * kCeps * kCeps; idx += NT) {
-    const int s = idx / (kCeps * kCeps), i = idx - s * (kCeps * kCeps);
-    if (sb + s < a.n_streams && L.nfs[s] > 0) a.state[(size_t)(sb + s) * st::kWords + st::kCepsDist + i] = L.dist[s][i];
-  }
-  for (int idx = tid; idx < S * kBands; idx += NT) {
-    const int s = idx / kBands, i = idx - s * kBands;
-    if (sb + s < a.n_streams && L.nfs[s] > 0) a.state[(size_t)(sb + s) * st::kWords + st::kLastG + i] = L.lastg[s][i];
-  }
+  R.store(a, sb, n_own, tid, NT);
   for (int idx = tid; idx < S * 96; idx += NT) {
     const int s = idx / 96, i = idx - s * 96;
-    if (sb + s >= a.n_streams || L.nfs[s] <= 0) continue;
+    if (!R.ran(s, n_own)) continue;
     float *stp = a.state + (size_t)(sb + s) * st::kWords;
     if (i < 24) stp[st::kVadGru + i] = L.gvT[fin & 3][i * S + s];
     if (i < 48) stp[st::kNoiseGru + i] = L.gnT[fin & 1][i * S + s];
     stp[st::kDenGru + i] = L.gdT[fin & 1][i * S + s];
   }
-  if (tid < S && sb + tid < a.n_streams && L.nfs[tid] > 0)
-    reinterpret_cast<int *>(a.state)[(size_t)(sb + tid) * st::kWords + st::kMemId] = L.memid[tid];
 }
 __global__ void __launch_bounds__(kR3NT) k_rnn3(StagedArgs a) { rnn3_body<false>(a); }
 __global__ void __launch_bounds__(kR3NT) k_rnn3f(StagedArgs a) { rnn3_body<true>(a); }

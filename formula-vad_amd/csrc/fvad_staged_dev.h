@@ -109,16 +109,20 @@ __device__ __forceinline__ void wave_sync() {
     if (tid == 0 && a.stamps)                                                 \
       for (int i_ = 0; i_ < (n); i_++) atomicAdd(&a.stamps[(base) + i_], st_acc[i_]); \
   } while (0)
+// every thread's busy cycles per phase p (up to its barrier wait): ph_acc[p]
+#define PHASE_INIT() unsigned long long ph_acc[2] = {0, 0}, ph_t0 = 0
+#define PHASE_BEGIN() ph_t0 = __builtin_amdgcn_s_memtime()
+#define PHASE_END(p) ph_acc[p] += __builtin_amdgcn_s_memtime() - ph_t0
 #else
-#define STAMP_INIT() \
-  do {               \
+#define STAMP_NOP() \
+  do {              \
   } while (0)
-#define RSTAMP(id) \
-  do {             \
-  } while (0)
-#define STAMP_FLUSH(base, n) \
-  do {                       \
-  } while (0)
+#define STAMP_INIT() STAMP_NOP()
+#define RSTAMP(id) STAMP_NOP()
+#define STAMP_FLUSH(base, n) STAMP_NOP()
+#define PHASE_INIT() STAMP_NOP()
+#define PHASE_BEGIN() STAMP_NOP()
+#define PHASE_END(p) STAMP_NOP()
 #endif
 
 // remove_doubling's candidate loop that does not depend on the previous

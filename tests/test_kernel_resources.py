@@ -20,8 +20,8 @@ NO_SLP = {"fvad_wave.hip", "fvad_pitch.hip"}  # Makefile: built without SLP vect
 # kernel -> (waves per SIMD, max scratch-spilled VGPRs)
 EXPECT = {
     "k_prep3": (4, 0), "k_plpc": (2, 0), "k_pcorr": (4, 0), "k_select": (4, 0), "k_rnn3": (4, 0),
-    "k_fftAw": (3, 0), "k_pspecw": (4, 0), "k_synthw": (4, 0), "k_olafb": (3, 0), "k_vadm_hbm": (3, 0),
-    "k_vadm_par": (2, 0), "k_gru16": (2, 0), "k_fused16": (4, 64),
+    "k_rnn3f": (4, 0), "k_fftAw": (3, 0), "k_pspecw": (4, 0), "k_synthw": (4, 0), "k_olafb": (3, 0),
+    "k_vadm_hbm": (3, 0), "k_vadm_par": (2, 0), "k_gru16": (2, 0), "k_fused16": (4, 64),
 }
 
 
