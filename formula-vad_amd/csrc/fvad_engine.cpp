@@ -892,8 +892,9 @@ extern "C" int fvad_engine_fetch(fvad_engine *e, int n_ticks, fvad_outputs *out)
 extern "C" int fvad_engine_windows_per_tick(const fvad_engine *e) { return e ? e->wpt : FVAD_EINVAL; }
 
 extern "C" const char *fvad_engine_kernel_name(const fvad_engine *e, int i) {
-  if (e && i == e->n_kernels && e->vadm.n > 0) return "k_vadm_hbm";
-  if (e && i == e->n_kernels + 1 && e->vadm.n > 0) return "k_vadm_par";
+  // (per-stream configs run the _ps kernels, reported in the same two slots)
+  if (e && i == e->n_kernels && e->vadm.n > 0) return e->vadm_ps ? "k_vadm_hbm_ps" : "k_vadm_hbm";
+  if (e && i == e->n_kernels + 1 && e->vadm.n > 0) return e->vadm_ps ? "k_vadm_par_ps" : "k_vadm_par";
   if (!e || i < 0 || i >= e->n_kernels) return nullptr;
   if (e->cfg.mode == FVAD_MODE_FUSED) return i == 0 ? "k_prep" : "k_frame";
   return e->kernels.k[i].name;

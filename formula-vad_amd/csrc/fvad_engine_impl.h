@@ -255,6 +255,17 @@ struct fvad_engine {
   std::vector<int> log_ticks;
   std::vector<fvad::VadmState> vadm_init;  // [m][stream] initial states
   size_t vadm_buf_len = 0;
+  // Per-stream configs (fvad_engine_attach_vadm_ex): the
+  // device table vadm.tab [m][stream] and its host mirror -- the rows, the
+  // configs they came from, and vadm_init above, which then holds each
+  // stream's own fresh machine.  vadm.c[m] carries the room's lengths (the
+  // buffers' layout).  vadm_nopar: rows without an initial average; while
+  // there is one, sync points run k_vadm_hbm_ps (launch_vadm).
+  bool vadm_ps = false;
+  fvad::dev_ptr<fvad::VadmRow> vadm_tab;
+  std::vector<fvad::VadmRow> vadm_rows;
+  std::vector<fvad_vadm_config> vadm_stream_cfgs;
+  size_t vadm_nopar = 0;
   int rnn_act[fvad::rnnimg::kMats] = {};
   int V = 0, L = 0, LX = 0, wmax = 0, grid_frames = 0;
   int wpt = 1;  // window slots per (tick, stream): windows_per_tick(fft_size)
@@ -363,6 +374,8 @@ int capture_retire(fvad_engine *e, uint64_t pass);
 int capture_reset(fvad_engine *e);
 int capture_set_streams(fvad_engine *e, const int32_t *streams, const uint64_t *samples, int n);
 int capture_collect_timing(fvad_engine *e);
+// fvad_engine_lifecycle.cpp: n distinct stream indices in range
+int check_stream_list(const fvad_engine *e, const int32_t *streams, int n);
 
 }  // namespace eng
 }  // namespace fvad

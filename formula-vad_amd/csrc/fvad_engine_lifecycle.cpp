@@ -21,19 +21,6 @@ uint64_t fnv_add(uint64_t h, const T &v) {
   return fnv1a(h, &v, sizeof(T));
 }
 
-// n distinct indices in [0, n_streams)
-int check_stream_list(const fvad_engine *e, const int32_t *streams, int n) {
-  if (n < 0 || (n > 0 && !streams)) return fail(FVAD_EINVAL, "invalid stream list");
-  if (n > e->cfg.n_streams) return fail(FVAD_EINVAL, "more listed streams than the engine has (duplicates)");
-  std::vector<char> seen((size_t)e->cfg.n_streams, 0);
-  for (int i = 0; i < n; i++) {
-    if (streams[i] < 0 || streams[i] >= e->cfg.n_streams) return fail(FVAD_EINVAL, "stream index out of range");
-    if (seen[streams[i]]) return fail(FVAD_EINVAL, "duplicate stream index");
-    seen[streams[i]] = 1;
-  }
-  return FVAD_OK;
-}
-
 // a save's or restore's compatibility fields (include/fvad.h)
 uint64_t config_hash_of(const fvad_engine *e) {
   const fvad_engine_config &c = e->cfg;
@@ -141,7 +128,27 @@ int check_record(const fvad_engine *e, const fvad::BlobLayout &lay, const float 
   return FVAD_OK;
 }
 
+// blobs of engines with per-stream configs are a later change: a v1 record's
+// layout and config_hash assume one config per machine (include/fvad.h)
+int refuse_per_stream(const fvad_engine *e, const char *what) {
+  if (!e->vadm_ps) return FVAD_OK;
+  return fail(FVAD_EINVAL, std::string(what) + " is not available on an engine attached with fvad_engine_attach_vadm_ex");
+}
+
 }  // namespace
+
+// n distinct indices in [0, n_streams)
+int fvad::eng::check_stream_list(const fvad_engine *e, const int32_t *streams, int n) {
+  if (n < 0 || (n > 0 && !streams)) return fail(FVAD_EINVAL, "invalid stream list");
+  if (n > e->cfg.n_streams) return fail(FVAD_EINVAL, "more listed streams than the engine has (duplicates)");
+  std::vector<char> seen((size_t)e->cfg.n_streams, 0);
+  for (int i = 0; i < n; i++) {
+    if (streams[i] < 0 || streams[i] >= e->cfg.n_streams) return fail(FVAD_EINVAL, "stream index out of range");
+    if (seen[streams[i]]) return fail(FVAD_EINVAL, "duplicate stream index");
+    seen[streams[i]] = 1;
+  }
+  return FVAD_OK;
+}
 
 // Three launches at most, each in order on the stream whose kernels own what
 // it clears: st::kPitch / st::kHp are k_prep3's, on the
@@ -233,6 +240,7 @@ extern "C" int fvad_stream_blob_info(const void *blob, size_t len, fvad_stream_b
 // gather the listed streams into one device staging buffer, one copy to the host
 extern "C" int fvad_engine_save_streams(fvad_engine *e, const int32_t *streams, int n, void *blob, size_t cap) {
   if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (const int rc = refuse_per_stream(e, "fvad_engine_save_streams")) return rc;
   if (const int rc = check_stream_list(e, streams, n)) return rc;
   if (n == 0) return FVAD_OK;
   if (!blob || cap < fvad_engine_save_size(e, n)) return fail(FVAD_EINVAL, "blob buffer smaller than fvad_engine_save_size");
@@ -261,8 +269,9 @@ extern "C" int fvad_engine_save_streams(fvad_engine *e, const int32_t *streams, 
 extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *streams, int n, const void *blob, size_t len,
                                            const int32_t *index) {
   if (!e) return fail(FVAD_EINVAL, "null engine");
-  int rc = check_stream_list(e, streams, n);
+  int rc = refuse_per_stream(e, "fvad_engine_restore_streams");
   if (rc) return rc;
+  if ((rc = check_stream_list(e, streams, n))) return rc;
   if (n == 0) return FVAD_OK;
   fvad_stream_blob_header h;
   if ((rc = parse_blob_header(blob, len, &h))) return rc;

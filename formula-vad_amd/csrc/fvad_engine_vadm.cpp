@@ -91,7 +91,11 @@ int enqueue_vadm(fvad_engine *e, const fvad::StagedArgs &v, int b, bool timed, b
   fvad::StagedArgs vf = v;
   vf.vadm.vfinal = (fast || e->dbg_always_par) ? 1 : 0;
   e->vowed = false;  // (a final pass resolves every machine, those without ticks included)
-  HIP_TRY(fvad::launch_vadm(vf, e->side, fast || e->dbg_always_par, &par));
+  // per-stream configs: k_vadm_par_ps only while every row has an initial
+  // average (a machine whose long-term buffer is still filling folds it whole
+  // at every push: k_vadm_hbm_ps' lane each, not a group's leader lane)
+  const bool rows_par = !e->vadm_ps || e->vadm_nopar == 0;
+  HIP_TRY(fvad::launch_vadm(vf, e->side, (fast || e->dbg_always_par) && rows_par, &par));
   if (!vf.vadm.vfinal) {
     e->vowed = true;
     e->vowed_args = vf;
@@ -190,9 +194,14 @@ int vadm_upload(const fvad_engine *e, const fvad::VadmArgs &v, const std::vector
     const int B = e->cfg.n_streams;
     for (int m = 0; m < v.n; m++) {
       const fvad::VadmConst &K = v.c[m];
-      for (int s = 0; s < B; s++)
-        for (int i = 0; i < K.n_lt; i++) buf[K.lt_off + (size_t)s * K.lt_pitch + i] = (float)K.init;
-      for (int s = 0; s < B; s++) st[(size_t)m * B + s].lt_nw = (unsigned)K.n_lt;
+      for (int s = 0; s < B; s++) {
+        // (per-stream configs: the stream's own length and initial average)
+        const fvad::VadmRow *row = e->vadm_ps ? &e->vadm_rows[(size_t)m * B + s] : nullptr;
+        const int n_lt = row ? row->n_lt : K.n_lt;
+        const float init = (float)(row ? row->init : K.init);
+        for (int i = 0; i < n_lt; i++) buf[K.lt_off + (size_t)s * K.lt_pitch + i] = init;
+        st[(size_t)m * B + s].lt_nw = (unsigned)n_lt;
+      }
     }
     HIP_TRY(hipMemcpy(v.buf, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
   }
@@ -203,11 +212,17 @@ int vadm_upload(const fvad_engine *e, const fvad::VadmArgs &v, const std::vector
 
 int fvad::eng::vadm_reset(fvad_engine *e) { return vadm_upload(e, e->vadm, e->vadm_init, e->vadm_buf_len); }
 
+namespace {
 // All or nothing: every buffer, the side stream, the events and the initial
 // state upload are made into locals, and move into the engine after the last
 // step that can fail.  A failed call leaves the engine unattached.
-extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *cfgs, int n, int seg_capacity) {
-  if (!e || !cfgs || n < 1 || n > FVAD_MAX_BANDS || seg_capacity < 1) return fail(FVAD_EINVAL, "invalid argument");
+// ps (fvad_engine_attach_vadm_ex): a constant table row per (machine, stream),
+// every stream starting on cfgs[m]; the rolling buffers are laid out for the
+// room, each of a machine's three lengths the maximum over cfgs[m] and room[].
+int attach(fvad_engine *e, const fvad_vadm_config *cfgs, int n, int seg_capacity, bool ps,
+           const fvad_vadm_config *room, int n_room) {
+  if (!e || !cfgs || n < 1 || n > FVAD_MAX_BANDS || seg_capacity < 1 || n_room < 0 || (n_room > 0 && !room))
+    return fail(FVAD_EINVAL, "invalid argument");
   if (e->cfg.mode == FVAD_MODE_FUSED) return fail(FVAD_EINVAL, "device VADMachines need the staged engine");
   if (e->vadm.n > 0) return fail(FVAD_EINVAL, "VADMachines already attached");
   HIP_TRY(hipSetDevice(e->cfg.device));
@@ -219,11 +234,24 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   v.negate_at = -1;
   long long off = 0;
   std::vector<fvad::VadmState> init((size_t)n * B);
+  std::vector<fvad::VadmRow> rows(ps ? (size_t)n * B : 0);
+  size_t nopar = 0;
   for (int m = 0; m < n; m++) {
     const fvad::VadmDerived d = fvad::vadm_derive(cfgs[m], e->cfg.sample_rate, e->cfg.fft_size);
     fvad::VadmConst &K = v.c[m] = d.K;
     K.slot = fvad::band_slot(e->cfg.band_lo, e->cfg.band_hi, e->cfg.n_bands, d.lo, d.hi);
     if (K.slot < 0) return fail(FVAD_EINVAL, "no engine band matches the machine's speech band");
+    if (ps) {
+      for (int s = 0; s < B; s++) rows[(size_t)m * B + s] = fvad::vadm_row(d, K.slot);
+      if (!K.has_init) nopar += (size_t)B;
+      for (int i = 0; i < n_room; i++) {
+        const fvad::VadmConst R = fvad::vadm_derive(room[i], e->cfg.sample_rate, e->cfg.fft_size).K;
+        K.n_lt = std::max(K.n_lt, R.n_lt);
+        K.n_st = std::max(K.n_st, R.n_st);
+        K.n_r = std::max(K.n_r, R.n_r);
+      }
+      K.lt_pitch = (K.n_lt + 3) & ~3;
+    }
     off = (off + 3) & ~3LL;  // (the long-term rows start 16-byte aligned)
     K.lt_off = off;
     off += (long long)K.lt_pitch * B;
@@ -236,12 +264,14 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   fvad::dev_ptr<fvad::VadmState> st;
   fvad::dev_ptr<float> buf;
   fvad::dev_ptr<fvad::VadmSeg> seg;
+  fvad::dev_ptr<fvad::VadmRow> tab;
   fvad_engine::WinOut set1;  // the second window-output set (push parity 1); set 0 is the engine's own
   fvad::dev_ptr<int32_t> vticks0;
   fvad::stream_ptr side;
   fvad::event_ptr ev_vadm, ev_vadm_b[2];
   EventTimer vt[2];
   int rc;
+  if (ps && (rc = fvad::make_dev(tab, rows.size()))) return rc;
   if ((rc = fvad::make_dev(st, init.size())) || (rc = fvad::make_dev(buf, (size_t)off)) ||
       (rc = fvad::make_dev(seg, (size_t)n * B * seg_capacity)) || (rc = make_win_out(e, set1)) ||
       (rc = fvad::make_dev(vticks0, (size_t)B)) || (rc = fvad::make_dev(set1.vticks, (size_t)B)) ||
@@ -254,7 +284,9 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   v.st = st.get();
   v.buf = buf.get();
   v.seg = seg.get();
+  v.tab = tab.get();
   if ((rc = vadm_upload(e, v, init, (size_t)off))) return rc;
+  if (ps) HIP_TRY(hipMemcpy(v.tab, rows.data(), rows.size() * sizeof(fvad::VadmRow), hipMemcpyHostToDevice));
   // nothing below fails
   e->vadm = v;
   e->vadm_st = std::move(st);
@@ -263,6 +295,14 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
   e->vadm_init = std::move(init);
   e->vadm_cfgs.assign(cfgs, cfgs + n);
   e->vadm_buf_len = (size_t)off;
+  e->vadm_ps = ps;
+  e->vadm_tab = std::move(tab);
+  e->vadm_rows = std::move(rows);
+  e->vadm_nopar = nopar;
+  if (ps) {
+    e->vadm_stream_cfgs.resize((size_t)n * B);
+    for (int m = 0; m < n; m++) std::fill_n(e->vadm_stream_cfgs.begin() + (size_t)m * B, (size_t)B, cfgs[m]);
+  }
   e->wout[0].vticks = std::move(vticks0);
   e->wout[1] = std::move(set1);
   e->side_ref = std::move(side);
@@ -272,6 +312,91 @@ extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *c
     e->ev_vadm_b[k] = std::move(ev_vadm_b[k]);
     e->vt[k] = std::move(vt[k]);
   }
+  return FVAD_OK;
+}
+}  // namespace
+
+extern "C" int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *cfgs, int n, int seg_capacity) {
+  return attach(e, cfgs, n, seg_capacity, false, nullptr, 0);
+}
+
+extern "C" int fvad_engine_attach_vadm_ex(fvad_engine *e, const fvad_vadm_config *cfgs, int n, int seg_capacity,
+                                          const fvad_vadm_config *room, int n_room) {
+  return attach(e, cfgs, n, seg_capacity, true, room, n_room);
+}
+
+// Everything is checked and every row derived before the first launch; the
+// launches then go on the side stream behind the pending machine pass, the
+// rows in their argument blocks (kRetargetMax per launch), and the host mirror
+// follows each launch that was queued.
+extern "C" int fvad_engine_set_stream_vadm(fvad_engine *e, const int32_t *streams, int n, int machine,
+                                           const fvad_vadm_config *cfgs) {
+  if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (!e->vadm_ps)
+    return fail(FVAD_EINVAL, "fvad_engine_set_stream_vadm needs an engine attached with fvad_engine_attach_vadm_ex");
+  if (const int rc = check_stream_list(e, streams, n)) return rc;
+  if (machine < 0 || machine >= e->vadm.n) return fail(FVAD_EINVAL, "no such attached machine");
+  if (n == 0) return FVAD_OK;
+  if (!cfgs) return fail(FVAD_EINVAL, "null configs");
+  if (e->dbg_lt_full)
+    return fail(FVAD_EINVAL, "fvad_engine_set_stream_vadm is not available under FVAD_DEBUG_VADM_LT_FULL");
+  const int B = e->cfg.n_streams;
+  const fvad::VadmConst &K = e->vadm.c[machine];  // the room
+  std::vector<fvad::VadmRow> rows((size_t)n);
+  std::vector<fvad::VadmState> fresh((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const fvad::VadmDerived d = fvad::vadm_derive(cfgs[i], e->cfg.sample_rate, e->cfg.fft_size);
+    const int slot = fvad::band_slot(e->cfg.band_lo, e->cfg.band_hi, e->cfg.n_bands, d.lo, d.hi);
+    if (slot < 0)
+      return fail(FVAD_EINVAL, "stream " + std::to_string(streams[i]) + ": no engine band matches the config's speech band");
+    const int len[3] = {d.K.n_lt, d.K.n_st, d.K.n_r}, cap[3] = {K.n_lt, K.n_st, K.n_r};
+    static const char *const name[3] = {"long-term", "short-term", "volume ratio"};
+    for (int k = 0; k < 3; k++)
+      if (len[k] > cap[k])
+        return fail(FVAD_EINVAL, "stream " + std::to_string(streams[i]) + ": " + name[k] + " length " +
+                                     std::to_string(len[k]) + " exceeds the attached room of " + std::to_string(cap[k]));
+    rows[i] = fvad::vadm_row(d, slot);
+    fresh[i] = d.s0;
+  }
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  // the previous push's machine pass sees the old configs: queued first
+  if (e->vpend)
+    if (const int rc = vadm_flush(e, false)) return rc;
+  fvad::RetargetArgs a{};
+  a.st = e->vadm.st;
+  a.buf = e->vadm.buf;
+  a.tab = e->vadm.tab;
+  a.n_streams = B;
+  a.machine = machine;
+  a.lt_pitch = K.lt_pitch;
+  a.n_st = K.n_st;
+  a.n_r = K.n_r;
+  a.lt_off = K.lt_off;
+  a.st_off = K.st_off;
+  a.r_off = K.r_off;
+  for (int i0 = 0; i0 < n; i0 += fvad::kRetargetMax) {
+    a.n = std::min(fvad::kRetargetMax, n - i0);
+    for (int i = 0; i < a.n; i++) {
+      a.id[i] = streams[i0 + i];
+      a.row[i] = rows[i0 + i];
+    }
+    HIP_TRY(fvad::launch_vadm_retarget(a, e->side));
+    for (int i = 0; i < a.n; i++) {
+      const size_t idx = (size_t)machine * B + streams[i0 + i];
+      e->vadm_nopar += (size_t)!rows[i0 + i].has_init;
+      e->vadm_nopar -= (size_t)!e->vadm_rows[idx].has_init;
+      e->vadm_rows[idx] = rows[i0 + i];
+      e->vadm_stream_cfgs[idx] = cfgs[i0 + i];
+      e->vadm_init[idx] = fresh[i0 + i];
+    }
+  }
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_stream_vadm_config(const fvad_engine *e, int stream, int machine, fvad_vadm_config *out) {
+  if (!e || !out || e->vadm.n == 0 || stream < 0 || stream >= e->cfg.n_streams || machine < 0 || machine >= e->vadm.n)
+    return fail(FVAD_EINVAL, "no such attached machine");
+  *out = e->vadm_ps ? e->vadm_stream_cfgs[(size_t)machine * e->cfg.n_streams + stream] : e->vadm_cfgs[machine];
   return FVAD_OK;
 }
 
@@ -443,9 +568,15 @@ extern "C" long fvad_engine_vadm_rolling(fvad_engine *e, int stream, int machine
   fvad::VadmState st;
   if (const int rc = vadm_read_state(e, stream, machine, &st)) return rc;
   const fvad::VadmConst &K = e->vadm.c[machine];
-  const int n = which == 0 ? K.n_lt : which == 1 ? K.n_st : K.n_r;
+  const size_t B = e->cfg.n_streams;
+  // per-stream configs: the stream's own lengths and initial average inside the room's layout
+  const fvad::VadmRow *row = e->vadm_ps ? &e->vadm_rows[(size_t)machine * B + stream] : nullptr;
+  const int n = row ? (which == 0 ? row->n_lt : which == 1 ? row->n_st : row->n_r)
+                    : (which == 0 ? K.n_lt : which == 1 ? K.n_st : K.n_r);
+  const int has_init = row ? row->has_init : K.has_init;
+  const double init = row ? row->init : K.init;
   const long long off = which == 0 ? K.lt_off : which == 1 ? K.st_off : K.r_off;
-  const size_t B = e->cfg.n_streams, k = std::min<size_t>((size_t)n, cap);
+  const size_t k = std::min<size_t>((size_t)n, cap);
   if (out && k) {
     // long-term entries: the stream's row; the others [i][stream]: a strided 2D copy of its column
     std::vector<float> col(k);
@@ -458,7 +589,7 @@ extern "C" long fvad_engine_vadm_rolling(fvad_engine *e, int stream, int machine
     for (size_t i = 0; i < k; i++)
       // long-term entries never written since the machine started hold the
       // initial average, a double (RollingAverage.zig:16-32; lt_nw counts the written)
-      out[i] = (which == 0 && K.has_init && i >= st.lt_nw) ? K.init : (double)col[i];
+      out[i] = (which == 0 && has_init && i >= st.lt_nw) ? init : (double)col[i];
   }
   return n;
 }

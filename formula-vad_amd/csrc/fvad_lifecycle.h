@@ -7,7 +7,9 @@
 //   state  [s][st::kWords]            the rnnoise / re-block record
 //   ring   [s][c][ring_len]           denoised samples awaiting FFT B
 //   per machine m: VadmState [m][s], the long-term row [s][lt_pitch], the
-//   short-term and ratio columns [i][s], the segment row [m][s][seg_cap]
+//   short-term and ratio columns [i][s], the segment row [m][s][seg_cap],
+//   and with per-stream configs the constant table's row [m][s]
+//   (fvad_engine_set_stream_vadm: k_vadm_retarget; a blob does not carry it)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -78,9 +80,46 @@ struct ClearArgs {
 struct VClearArgs {
   VadmArgs vadm;
   int n_streams;
-  VadmState init[kMaxBandCfg];  // a machine's state after fvad_engine_reset
+  VadmState init[kMaxBandCfg];  // a machine's state after fvad_engine_reset (with vadm.tab: a fresh
+                                //   machine of the stream's own row instead, vadm_fresh)
   IdList ids;
 };
+
+// A freshly constructed machine of a row's config (fvad_vadm_derive's s0: the
+// long-term RollingAverage full of the initial average when there is one),
+// keeping what outlives the machine: the stream's window count, so window
+// sample indices continue, and the segments emitted so far.
+// (the row's has_init, n_lt and lt0 by value: a kernel reads them where the
+// row lies, in the table or in its argument block, and keeps no copy of it)
+__host__ __device__ inline VadmState vadm_fresh(int has_init, int n_lt, double lt0, unsigned long long windows_done,
+                                                unsigned n_segs) {
+  VadmState S{};
+  S.windows_done = windows_done;
+  S.n_segs = n_segs;
+  if (has_init) {
+    S.lt_count = (unsigned)n_lt;
+    S.lt_last = lt0;
+    S.lt_has = 1;
+    S.lt_pre_ok = 1;
+  }
+  return S;
+}
+
+// k_vadm_retarget (fvad_engine_set_stream_vadm): machine `machine` of the
+// listed streams becomes a fresh machine of row[i].  The rows travel in the
+// argument block like the stream lists above: kRetargetMax per launch.
+constexpr int kRetargetMax = 47;  // (48 rows of 80 bytes and their ids would be 4112 bytes)
+struct RetargetArgs {
+  VadmState *st;  // [m][stream]
+  float *buf;
+  VadmRow *tab;   // [m][stream]
+  int n_streams, machine, n;
+  int lt_pitch, n_st, n_r;  // the machine's room: what is cleared
+  long long lt_off, st_off, r_off;
+  int id[kRetargetMax];
+  VadmRow row[kRetargetMax];
+};
+static_assert(sizeof(RetargetArgs) <= 4096, "kernel argument block");
 struct XferArgs {
   float *state, *ring;
   int ring_len, n_streams;
@@ -92,6 +131,7 @@ struct XferArgs {
 
 hipError_t launch_stream_clear(const ClearArgs &a, hipStream_t stream);
 hipError_t launch_stream_vclear(const VClearArgs &a, hipStream_t stream);
+hipError_t launch_vadm_retarget(const RetargetArgs &a, hipStream_t stream);
 hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream);
 hipError_t launch_stream_scatter(const XferArgs &a, hipStream_t stream);
 

@@ -1,4 +1,5 @@
-// Per-stream lifecycle kernels: clear, gather and scatter over the engine's
+// Per-stream lifecycle kernels: clear, retarget (a stream's machine config),
+// gather and scatter over the engine's
 // per-stream layouts (fvad_lifecycle.h).  One workgroup per (listed stream,
 // part), float4 accesses where the layout is 16-byte aligned (the state
 // record, the long-term row, VadmState, the blob's sections); the re-block
@@ -65,10 +66,36 @@ __global__ void __launch_bounds__(kNT) k_stream_vclear(VClearArgs a) {
   const int s = a.ids.id[blockIdx.x], m = blockIdx.y, tid = threadIdx.x;
   const VadmConst &K = a.vadm.c[m];
   const size_t B = a.n_streams;
-  if (tid == 0) a.vadm.st[(size_t)m * B + s] = a.init[m];
+  // (per-stream configs: a fresh machine of the stream's own row, which stays;
+  // K's lengths are then the room's, the whole of what the stream may use)
+  if (tid == 0) {
+    if (a.vadm.tab) {
+      const VadmRow *r = a.vadm.tab + (size_t)m * B + s;
+      a.vadm.st[(size_t)m * B + s] = vadm_fresh(r->has_init, r->n_lt, r->lt0, 0, 0);
+    } else {
+      a.vadm.st[(size_t)m * B + s] = a.init[m];
+    }
+  }
   zero4(a.vadm.buf + K.lt_off + (size_t)s * K.lt_pitch, K.lt_pitch, tid);
   for (int i = tid; i < K.n_st; i += kNT) a.vadm.buf[K.st_off + (size_t)i * B + s] = 0.0f;
   for (int i = tid; i < K.n_r; i += kNT) a.vadm.buf[K.r_off + (size_t)i * B + s] = 0.0f;
+}
+
+// listed stream blockIdx.x: machine a.machine becomes a fresh machine of
+// a.row[blockIdx.x] -- the table row, the state (its window count and segment
+// count stay), and rolling buffers empty over the machine's room, whatever
+// the old and the new lengths are.  Runs on the side stream between two
+// machine passes, so nothing else touches the lane.
+__global__ void __launch_bounds__(kNT) k_vadm_retarget(RetargetArgs a) {
+  const int i = blockIdx.x, s = a.id[i], tid = threadIdx.x;
+  const size_t B = a.n_streams, idx = (size_t)a.machine * B + s;
+  if (tid == 0) {
+    a.tab[idx] = a.row[i];
+    a.st[idx] = vadm_fresh(a.row[i].has_init, a.row[i].n_lt, a.row[i].lt0, a.st[idx].windows_done, a.st[idx].n_segs);
+  }
+  zero4(a.buf + a.lt_off + (size_t)s * a.lt_pitch, a.lt_pitch, tid);
+  for (int k = tid; k < a.n_st; k += kNT) a.buf[a.st_off + (size_t)k * B + s] = 0.0f;
+  for (int k = tid; k < a.n_r; k += kNT) a.buf[a.r_off + (size_t)k * B + s] = 0.0f;
 }
 
 // stream slots[i] -> record recs[i].  part 0: state; 1 + c: channel c's
@@ -168,6 +195,13 @@ hipError_t launch_stream_vclear(const VClearArgs &a, hipStream_t stream) {
   if (a.ids.n < 1 || a.vadm.n < 1) return hipSuccess;
   (void)hipGetLastError();
   hipLaunchKernelGGL(k_stream_vclear, dim3((unsigned)a.ids.n, (unsigned)a.vadm.n), dim3(kNT), 0, stream, a);
+  return launched();
+}
+
+hipError_t launch_vadm_retarget(const RetargetArgs &a, hipStream_t stream) {
+  if (a.n < 1) return hipSuccess;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_vadm_retarget, dim3((unsigned)a.n), dim3(kNT), 0, stream, a);
   return launched();
 }
 

@@ -58,6 +58,35 @@ fvad::VadmDerived fvad::vadm_derive(const fvad_vadm_config &c, int sample_rate, 
   return d;
 }
 
+fvad::VadmRow fvad::vadm_row(const VadmDerived &d, int slot) {
+  const VadmConst &K = d.K;
+  VadmRow r{};
+  r.n_lt = K.n_lt;
+  r.n_st = K.n_st;
+  r.n_r = K.n_r;
+  r.slot = slot;
+  r.min_open = K.min_open;
+  r.max_gap = K.max_gap;
+  r.rec_pad = K.rec_pad;
+  r.init = K.init;
+  r.thr_factor = K.thr_factor;
+  r.ratio_thr = K.ratio_thr;
+  r.min_dur = K.min_dur;
+  r.sr = K.sr;
+  r.lt0 = d.s0.lt_last;
+  r.has_init = K.has_init;
+  return r;
+}
+
+extern "C" int fvad_vadm_lengths(const fvad_vadm_config *cfg, int sample_rate, int fft_size, int out[3]) {
+  if (!cfg || !out || sample_rate <= 0 || fft_size <= 0) return FVAD_EINVAL;
+  const fvad::VadmConst K = fvad::vadm_derive(*cfg, sample_rate, fft_size).K;
+  out[0] = K.n_lt;
+  out[1] = K.n_st;
+  out[2] = K.n_r;
+  return FVAD_OK;
+}
+
 int fvad::band_slot(const int *band_lo, const int *band_hi, int n_bands, int lo, int hi) {
   int slot = -1;
   for (int b = 0; b < n_bands; b++)

@@ -36,6 +36,11 @@ struct VadmDerived {
 };
 VadmDerived vadm_derive(const fvad_vadm_config &c, int sample_rate, int fft_size);
 
+// d as a row of the per-stream constant table (fvad_staged.h VadmRow: the
+// engines attached with fvad_engine_attach_vadm_ex); slot: the engine band
+// slot of d's speech band
+VadmRow vadm_row(const VadmDerived &d, int slot);
+
 // the slot b with band_lo[b] == lo and band_hi[b] == hi (the last, should the
 // bands repeat), or -1
 int band_slot(const int *band_lo, const int *band_hi, int n_bands, int lo, int hi);

@@ -59,6 +59,25 @@ struct VadmConst {
   int has_init;
   double init;
 };
+// Per-stream configs (fvad_engine_attach_vadm_ex): one row per (machine,
+// stream) of a device table [m][stream], the constants of VadmConst a config
+// decides -- a stream's own RollingAverage lengths, band slot, thresholds and
+// initial average -- under VadmConst's names, so the per-window code
+// (fvad_vadm_dev.h) takes either.  The buffer offsets and lt_pitch stay the
+// machine's (VadmArgs::c[m], sized by the attached room).  lt0: the long-term
+// average of a freshly constructed machine (RollingAverage.init's fold), what
+// k_vadm_retarget and k_stream_vclear start a machine from.  Five 16-byte
+// words: a lane fetches its row with five wide loads.
+struct alignas(16) VadmRow {
+  int n_lt, n_st, n_r, slot;
+  unsigned long long min_open, max_gap;
+  unsigned long long rec_pad;
+  double init;
+  float thr_factor, ratio_thr, min_dur, sr;
+  double lt0;
+  int has_init, pad;
+};
+static_assert(sizeof(VadmRow) == 80, "a table row is five 16-byte words");
 struct VadmState {
   unsigned long long speech_start, speech_end, windows_done;
   double lt_last, st_last, r_last, lt_pre;  // lt_pre: cached prefix (see ra_push_long)
@@ -129,6 +148,9 @@ struct VadmArgs {
   VadmEvRec *ev_stage;   // null (no event feed), or the pass's staging area [lane][ev_cap]
   unsigned *ev_count;    // [lane] records staged
   int ev_cap;            // records per lane: the windows a stream can complete in one push (one event each at most)
+  VadmRow *tab;          // null, or the per-stream constants [m][stream] (fvad_engine_attach_vadm_ex): the
+                         //   machine kernels are then k_vadm_hbm_ps / k_vadm_par_ps, and c[m] holds the
+                         //   room's lengths (the buffers' layout) and the machine's offsets
 };
 // the lazy long-term walk's counters (FVAD_DEBUG_VADM_COUNT): long-term tests
 // decided from an exact average, from the estimate, left open by the bound (an

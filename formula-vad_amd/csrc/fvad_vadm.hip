@@ -1,5 +1,6 @@
 // The device VADMachine over a push's window outputs (the engine's side
-// stream): k_vadm_hbm in steady state, k_vadm_par at sync points, and
+// stream): k_vadm_hbm in steady state, k_vadm_par at sync points (k_vadm_hbm_ps
+// and k_vadm_par_ps where every stream has its own config), and
 // k_vadm_events, which packs the speech events a pass staged.  At the end,
 // for its code's sake, the pitch front's k_select (see there).
 #pragma clang fp contract(off)
@@ -21,18 +22,45 @@ namespace fvad {
 // machine's per-window code is fvad_vadm_dev.h's (shared with the config
 // sweep, fvad_sweep.hip); here is where a push's windows come from.
 // ---------------------------------------------------------------------------
+// Where a machine's constants come from.  The uniform kernels (k_vadm_hbm,
+// k_vadm_par: engines attached with fvad_engine_attach_vadm) read machine m's
+// from the argument block; the per-stream kernels (k_vadm_hbm_ps,
+// k_vadm_par_ps: fvad_engine_attach_vadm_ex) read row [m][stream] of the
+// device table, once per machine.  The buffer offsets and lt_pitch are always
+// the machine's, a.vadm.c[m]: the layout does not depend on the rows.
+// kHbmBlock: k_vadm_hbm*'s long-term read-ahead (lt_range's block).  A lane
+// of k_vadm_hbm_ps holds its constants in VGPRs where k_vadm_hbm's are SGPRs;
+// with half the read-ahead (16 VGPRs less) it keeps k_vadm_hbm's 3 waves per
+// SIMD without scratch, and between sync points the folds it serves are rare
+// (the lazy walk, fvad_vadm_dev.h).
+template <bool kPS>
+struct VadmK {
+  using type = VadmConst;
+  static constexpr int kHbmBlock = FVAD_LT_BLOCK;
+  static __device__ __forceinline__ const VadmConst &of(const StagedArgs &a, int m, int) { return a.vadm.c[m]; }
+};
+template <>
+struct VadmK<true> {
+  using type = VadmRow;
+  static constexpr int kHbmBlock = FVAD_LT_BLOCK / 2;
+  // five 16-byte loads (the rows are 16-byte aligned)
+  static __device__ __forceinline__ VadmRow of(const StagedArgs &a, int m, int s) {
+    return a.vadm.tab[(size_t)m * a.n_streams + s];
+  }
+};
+
 // One machine over all completed windows of the push for one stream (the
-// serial walk, vadm_walk); `lt` points at entry 0 of the stream's long-term
-// buffer, `lts` is its stride.
-__device__ void vadm_stream(const StagedArgs &a, int m, int s, float *lt, size_t lts, bool final) {
+// serial walk, vadm_walk); K its constants, `lt` points at entry 0 of the
+// stream's long-term buffer, `lts` is its stride.
+template <int kL = FVAD_LT_BLOCK, class KT>
+__device__ void vadm_stream(const StagedArgs &a, int m, int s, const KT &K, float *lt, size_t lts, bool final) {
   const int B = a.n_streams, C = a.n_channels, nb = a.n_bands;
   const int nt = ticks_of(a, s);
-  const VadmConst &K = a.vadm.c[m];
   VadmState S = a.vadm.st[(size_t)m * B + s];
-  float *st = a.vadm.buf + K.st_off + s, *rb = a.vadm.buf + K.r_off + s;
+  float *st = a.vadm.buf + a.vadm.c[m].st_off + s, *rb = a.vadm.buf + a.vadm.c[m].r_off + s;
   VadmSeg *seg = a.vadm.seg + ((size_t)m * B + s) * a.vadm.seg_cap;
   const VadmEvLane ev = vadm_ev_lane(a.vadm, m, s);
-  vadm_walk(S, K, st, rb, B, lt, lts, seg, a.vadm.seg_cap, ev, (unsigned long long)a.plan->nfft_b,
+  vadm_walk<kL>(S, K, st, rb, B, lt, lts, seg, a.vadm.seg_cap, ev, (unsigned long long)a.plan->nfft_b,
             a.vadm.bound_scale, a.vadm.defer_max, a.vadm.count, final, [&](auto &&window) {
               // every window of the push in order: ticks, then a tick's slots
               // (several when fft_size < 480)
@@ -85,13 +113,18 @@ __device__ __forceinline__ double lt_fold(double acc, const float *lt, size_t lt
   if (i0 >= i1) return acc;
   return lt_range<FVAD_VP_BLOCK>(acc, lt, lts, i0, i1, nw, init, scalar);
 }
-__global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
+// (kPS: the four streams' table rows sit in LDS beside their states, Ks[],
+// read by the group's lanes where the uniform kernel reads the argument block)
+template <bool kPS>
+__device__ __forceinline__ void vadm_par_groups(const StagedArgs &a) {
+  using KT = typename VadmK<kPS>::type;
   __shared__ float wmin[kVpS][kVpMaxW], wvad[kVpS][kVpMaxW], wvr[kVpS][kVpMaxW];
   __shared__ float pv[kVpS][kVpMaxW];  // values pushed in this push, in push order (committed + the round's hypotheses)
   __shared__ double favg[kVpS][kVpG];
   __shared__ double rpre[kVpS];  // the cached prefix before the round's first push
   __shared__ int rnd[kVpS][4];  // round: first window, pushes committed so far, state (0 run, 1 done, 2 serial)
   __shared__ VadmState Ss[kVpS];
+  __shared__ VadmRow Ks[kVpS];  // (kPS only: the uniform kernel never names it, so it has none)
   const int B = a.n_streams, C = a.n_channels, nb = a.n_bands;
   const int g = threadIdx.x / kVpG, r = threadIdx.x % kVpG;
   const int s = blockIdx.x * kVpS + g;
@@ -100,8 +133,23 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
   const unsigned long long fft = (unsigned long long)a.plan->nfft_b;
   const int self = threadIdx.x;
   for (int m = 0; m < a.vadm.n; m++) {
-    const VadmConst &K = a.vadm.c[m];
-    float *lt = a.vadm.buf + K.lt_off + (size_t)(sok ? s : 0) * K.lt_pitch;  // the stream's row
+    const VadmConst &M = a.vadm.c[m];  // the layout
+    if constexpr (kPS) {
+      // the group's row, one 16-byte word per lane (Ks is free: the previous
+      // machine's last reads are behind the wave_sync that ends its turn)
+      static_assert(sizeof(VadmRow) / 16 <= kVpG, "one lane per word of the row");
+      if (r < (int)(sizeof(VadmRow) / 16))
+        reinterpret_cast<uint4 *>(&Ks[g])[r] =
+            reinterpret_cast<const uint4 *>(a.vadm.tab + (size_t)m * B + (s < B ? s : 0))[r];
+      wave_sync();
+    }
+    const KT &K = [&]() -> const KT & {
+      if constexpr (kPS)
+        return Ks[g];
+      else
+        return a.vadm.c[m];
+    }();
+    float *lt = a.vadm.buf + M.lt_off + (size_t)(sok ? s : 0) * M.lt_pitch;  // the stream's row
     const size_t lts = 1;
     // the push's windows in order -> LDS (16 ticks at a time, positions by a
     // prefix count over the group's lanes)
@@ -142,7 +190,7 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
       } else if (s < B) {
         VadmState S2 = a.vadm.st[(size_t)m * B + s];
         if (S2.lt_defer) {
-          lt_resolve(S2, K, a.vadm.buf + K.lt_off + (size_t)s * K.lt_pitch, 1);
+          lt_resolve(S2, K, a.vadm.buf + M.lt_off + (size_t)s * M.lt_pitch, 1);
           a.vadm.st[(size_t)m * B + s] = S2;
         }
       }
@@ -154,7 +202,7 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
       wave_sync();
     }
     VadmState &S = Ss[g];
-    float *st = a.vadm.buf + K.st_off + (sok ? s : 0), *rb = a.vadm.buf + K.r_off + (sok ? s : 0);
+    float *st = a.vadm.buf + M.st_off + (sok ? s : 0), *rb = a.vadm.buf + M.r_off + (sok ? s : 0);
     VadmSeg *seg = a.vadm.seg + ((size_t)m * B + (sok ? s : 0)) * a.vadm.seg_cap;
     const VadmEvLane ev = vadm_ev_lane(a.vadm, m, sok ? s : 0);
     // (n > kVpMaxW: a push wraps around the buffer at most once)
@@ -257,7 +305,7 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
         // engines whose machines can get here to k_vadm_hbm; the test hook
         // par_serial_every forces it): the serial walk on the leader lane,
         // from the untouched state in HBM
-        vadm_stream(a, m, s, lt, lts, true);
+        vadm_stream(a, m, s, K, lt, lts, true);
       } else {
         // the push's long-term values into the buffer (read above as the old entries)
         unsigned w = wbase;
@@ -272,47 +320,67 @@ __global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) {
     wave_sync();
   }
 }
+__global__ void __launch_bounds__(64) k_vadm_par(StagedArgs a) { vadm_par_groups<false>(a); }
+__global__ void __launch_bounds__(64) k_vadm_par_ps(StagedArgs a) { vadm_par_groups<true>(a); }
 
 // k_vadm_hbm: the same machine, long-term buffers walked in HBM, no LDS, one
 // wave (kVadmHbmLanes = 64 streams) per workgroup: a light kernel that co-runs
-// with the next push's pipeline on the engine's side stream.
+// with the next push's pipeline on the engine's side stream.  k_vadm_hbm_ps:
+// the same with each lane's constants its stream's own table row.
 #ifndef FVAD_VADM_LANES
 #define FVAD_VADM_LANES 64
 #endif
 constexpr int kVadmHbmLanes = FVAD_VADM_LANES;  // streams per workgroup (one wave); 16 / 32 / 64 measured within noise, 64 takes fewest wave slots
-__global__ void __launch_bounds__(64) k_vadm_hbm(StagedArgs a) {
+template <bool kPS>
+__device__ __forceinline__ void vadm_hbm_lanes(const StagedArgs &a) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= a.n_streams) return;
   const bool final = a.vadm.vfinal != 0;
+  constexpr int kL = VadmK<kPS>::kHbmBlock;
   if (ticks_of(a, s) <= 0) {  // no windows; at a sync point its owed fold is still due
     if (final)
       for (int m = 0; m < a.vadm.n; m++) {
         VadmState *p = a.vadm.st + (size_t)m * a.n_streams + s;
         if (p->lt_defer) {
           VadmState S = *p;
-          lt_resolve(S, a.vadm.c[m], a.vadm.buf + a.vadm.c[m].lt_off + (size_t)s * a.vadm.c[m].lt_pitch, 1);
+          lt_resolve<kL>(S, VadmK<kPS>::of(a, m, s), a.vadm.buf + a.vadm.c[m].lt_off + (size_t)s * a.vadm.c[m].lt_pitch,
+                         1);
           *p = S;
         }
       }
     return;
   }
   for (int m = 0; m < a.vadm.n; m++)
-    vadm_stream(a, m, s, a.vadm.buf + a.vadm.c[m].lt_off + (size_t)s * a.vadm.c[m].lt_pitch, 1, final);
+    vadm_stream<kL>(a, m, s, VadmK<kPS>::of(a, m, s),
+                    a.vadm.buf + a.vadm.c[m].lt_off + (size_t)s * a.vadm.c[m].lt_pitch, 1, final);
 }
+__global__ void __launch_bounds__(64) k_vadm_hbm(StagedArgs a) { vadm_hbm_lanes<false>(a); }
+__global__ void __launch_bounds__(64) k_vadm_hbm_ps(StagedArgs a) { vadm_hbm_lanes<true>(a); }
 
 hipError_t launch_vadm(const StagedArgs &a, hipStream_t stream, bool fast, bool *ran_par) {
   (void)hipGetLastError();
   // k_vadm_par's case: every machine's long-term buffer full from the start
   // (an initial average) and longer than a push's windows, at most kVpMaxW
-  // windows per push (wmax bounds them)
+  // windows per push (wmax bounds them).  With per-stream rows (a.vadm.tab)
+  // the caller has looked at the rows: it asks for `fast` only while every row
+  // has an initial average, and a stream whose buffer is no longer than a
+  // push's windows takes k_vadm_par_ps' in-kernel serial walk.
   bool par = fast && a.wmax <= kVpMaxW;
-  for (int m = 0; m < a.vadm.n; m++) par = par && a.vadm.c[m].has_init && a.vadm.c[m].n_lt > kVpMaxW;
+  if (!a.vadm.tab)
+    for (int m = 0; m < a.vadm.n; m++) par = par && a.vadm.c[m].has_init && a.vadm.c[m].n_lt > kVpMaxW;
   if (ran_par) *ran_par = par;
+  const dim3 hbm_grid((a.n_streams + kVadmHbmLanes - 1) / kVadmHbmLanes), par_grid((a.n_streams + kVpS - 1) / kVpS);
+  if (a.vadm.tab) {
+    if (!par)
+      FVAD_KERNEL_TRY(k_vadm_hbm_ps, hbm_grid, dim3(kVadmHbmLanes), 0, stream, a);
+    else
+      FVAD_KERNEL_TRY(k_vadm_par_ps, par_grid, dim3(kVpS * kVpG), 0, stream, a);
+    return hipSuccess;
+  }
   if (!par)
-    FVAD_KERNEL_TRY(k_vadm_hbm, dim3((a.n_streams + kVadmHbmLanes - 1) / kVadmHbmLanes), dim3(kVadmHbmLanes), 0,
-                    stream, a);
+    FVAD_KERNEL_TRY(k_vadm_hbm, hbm_grid, dim3(kVadmHbmLanes), 0, stream, a);
   else
-    FVAD_KERNEL_TRY(k_vadm_par, dim3((a.n_streams + kVpS - 1) / kVpS), dim3(kVpS * kVpG), 0, stream, a);
+    FVAD_KERNEL_TRY(k_vadm_par, par_grid, dim3(kVpS * kVpG), 0, stream, a);
   return hipSuccess;
 }
 

@@ -1,5 +1,5 @@
 // The device VADMachine's per-window code, shared by the engine's machine
-// kernels (fvad_vadm.hip: k_vadm_hbm, k_vadm_par) and the config sweep
+// kernels (fvad_vadm.hip: k_vadm_hbm, k_vadm_par and their _ps forms) and the config sweep
 // (fvad_sweep.hip: k_vadm_sweep), so every kernel runs the same expressions in
 // the same order: the rolling averages, the long-term folds, the speech-state
 // machine, and the serial walk over a run of windows (vadm_walk), which takes
@@ -142,6 +142,9 @@ __device__ __forceinline__ double lt_range(double acc, const float *buf, size_t 
 // (those entries have not changed) - the pass starts from that cached prefix.
 // Entries never written since the machine started hold the initial average
 // (a double, RollingAverage.zig init): entry i is a pushed f32 iff i < nw.
+// (kL, here and in lt_resolve / vadm_walk: lt_range's block, the entries read
+// ahead of the add chain -- registers, not results)
+template <int kL = FVAD_LT_BLOCK>
 __device__ __forceinline__ double ra_push_long(float *buf, size_t bs, int n, unsigned &widx, unsigned &count,
                                                unsigned &nw, double init, double &last, int &has, double &pre,
                                                int &pre_ok, float sample) {
@@ -156,12 +159,12 @@ __device__ __forceinline__ double ra_push_long(float *buf, size_t bs, int n, uns
   const unsigned save_at = widx;  // the next pass starts at the next write position
   double save = 0.0;              // (save_at == 0: it starts from 0.0)
   if (save_at > start && save_at < count) {
-    acc = lt_range(acc, buf, bs, start, save_at, nw, init, scalar);
+    acc = lt_range<kL>(acc, buf, bs, start, save_at, nw, init, scalar);
     save = acc;
-    acc = lt_range(acc, buf, bs, save_at, count, nw, init, scalar);
+    acc = lt_range<kL>(acc, buf, bs, save_at, count, nw, init, scalar);
   } else {
     if (save_at == start) save = acc;
-    acc = lt_range(acc, buf, bs, start, count, nw, init, scalar);
+    acc = lt_range<kL>(acc, buf, bs, start, count, nw, init, scalar);
   }
   pre = save;
   pre_ok = count == (unsigned)n;
@@ -175,7 +178,10 @@ __device__ __forceinline__ double ra_push_long(float *buf, size_t bs, int n, uns
 enum { kVmClosed = 0, kVmOpening = 1, kVmOpen = 2, kVmClosing = 3 };
 // short-term and channel-ratio averages (pushed every window); `met`: the
 // speech condition against the long-term average of the last long push
-__device__ __forceinline__ bool vadm_short(VadmState &S, const VadmConst &K, float *st, float *rb, int B, float min_v,
+// (KT, here and below: the machine's constants, VadmConst from the argument
+// block or a stream's own VadmRow -- the same names, the same expressions)
+template <class KT>
+__device__ __forceinline__ bool vadm_short(VadmState &S, const KT &K, float *st, float *rb, int B, float min_v,
                                            float vr) {
   const double st_avg = ra_push(st, B, K.n_st, S.st_widx, S.st_count, S.st_last, S.st_has, min_v);
   const double r_avg = ra_push(rb, B, K.n_r, S.r_widx, S.r_count, S.r_last, S.r_has, vr);
@@ -229,7 +235,8 @@ __device__ __forceinline__ void vadm_ev_put(const VadmEvLane &l, unsigned kind, 
 enum { kVeSpeechOpen = 1, kVeSegment = 2 };  // FVAD_EVENT_SPEECH_OPEN, FVAD_EVENT_SEGMENT (include/fvad.h)
 
 // the speech-state transition, segment output and tracking of one window
-__device__ __forceinline__ void vadm_fsm(VadmState &S, const VadmConst &K, unsigned long long index, bool met,
+template <class KT>
+__device__ __forceinline__ void vadm_fsm(VadmState &S, const KT &K, unsigned long long index, bool met,
                                          float vad, float vr, VadmSeg *seg, int seg_cap, const VadmEvLane &ev) {
   const int from = S.state;
   bool ended = false;
@@ -318,11 +325,12 @@ __device__ __forceinline__ void lt_neg_push(VadmState &S, unsigned n, float v) {
   if (S.lt_neg > 0) S.lt_neg--;
   if (!(v >= 0.0f)) S.lt_neg = (int)n;
 }
-__device__ __forceinline__ void lt_resolve(VadmState &S, const VadmConst &K, const float *lt, size_t lts) {
+template <int kL = FVAD_LT_BLOCK, class KT>
+__device__ __forceinline__ void lt_resolve(VadmState &S, const KT &K, const float *lt, size_t lts) {
   if (!S.lt_defer) return;
   const unsigned n = (unsigned)K.n_lt;
   double acc = S.lt_fpre;
-  if (S.lt_widx != 0) acc = lt_range(acc, lt, lts, S.lt_widx, n, S.lt_nw, K.init, 1.0 / (double)n);
+  if (S.lt_widx != 0) acc = lt_range<kL>(acc, lt, lts, S.lt_widx, n, S.lt_nw, K.init, 1.0 / (double)n);
   S.lt_last = acc;
   S.lt_defer = 0;
 }
@@ -357,8 +365,8 @@ __device__ __forceinline__ void lt_resolve(VadmState &S, const VadmConst &K, con
 // factor is nonnegative; otherwise each pushing window folds at once
 // (ra_push_long).  Whether the walk is lazy is decided once, at the start of
 // the run.
-template <class ForEachWindow>
-__device__ __forceinline__ void vadm_walk(VadmState &S, const VadmConst &K, float *st, float *rb, int B, float *lt,
+template <int kL = FVAD_LT_BLOCK, class KT, class ForEachWindow>
+__device__ __forceinline__ void vadm_walk(VadmState &S, const KT &K, float *st, float *rb, int B, float *lt,
                                           size_t lts, VadmSeg *seg, int seg_cap, const VadmEvLane &ev,
                                           unsigned long long fft, double bound_scale, unsigned defer_max,
                                           unsigned long long *cnt, bool final, ForEachWindow &&for_each_window) {
@@ -366,7 +374,7 @@ __device__ __forceinline__ void vadm_walk(VadmState &S, const VadmConst &K, floa
   const double f = (double)K.thr_factor, scalar = 1.0 / (double)n;
   const bool lazy = S.lt_count == n && S.lt_pre_ok && S.lt_has && n > 1 && f >= 0.0 &&
                     !(K.has_init && !(K.init >= 0.0)) && S.lt_neg == 0;
-  if (!lazy) lt_resolve(S, K, lt, lts);  // (a deferring machine is lazy; kept for safety)
+  if (!lazy) lt_resolve<kL>(S, K, lt, lts);  // (a deferring machine is lazy; kept for safety)
   // the bound's scale: the test hook's, +inf once a negative entry is pushed
   // (no bound holds then: every later test of the run folds)
   double bscale = bound_scale;
@@ -382,7 +390,7 @@ __device__ __forceinline__ void vadm_walk(VadmState &S, const VadmConst &K, floa
   // index (fpre) continued over the entries after it, C order
   auto fold = [&]() {
     double acc = fpre;
-    if (S.lt_widx != 0) acc = lt_range(acc, lt, lts, S.lt_widx, n, S.lt_nw, K.init, scalar);
+    if (S.lt_widx != 0) acc = lt_range<kL>(acc, lt, lts, S.lt_widx, n, S.lt_nw, K.init, scalar);
     S.lt_last = acc;
     approx = acc;
     amax = fabs(acc);
@@ -395,7 +403,7 @@ __device__ __forceinline__ void vadm_walk(VadmState &S, const VadmConst &K, floa
     if (!lazy) {
       met = vadm_short(S, K, st, rb, B, min_v, vr);
       if (!met) {
-        ra_push_long(lt, lts, K.n_lt, S.lt_widx, S.lt_count, S.lt_nw, K.init, S.lt_last, S.lt_has, S.lt_pre,
+        ra_push_long<kL>(lt, lts, K.n_lt, S.lt_widx, S.lt_count, S.lt_nw, K.init, S.lt_last, S.lt_has, S.lt_pre,
                      S.lt_pre_ok, min_v);
         lt_neg_push(S, n, min_v);
       }

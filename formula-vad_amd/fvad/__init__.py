@@ -229,6 +229,10 @@ SYMBOLS = [
     ("fvad_engine_kernel_name", C.c_char_p, [C.c_void_p, C.c_int]),
     ("fvad_engine_windows_per_tick", C.c_int, [C.c_void_p]),
     ("fvad_engine_attach_vadm", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("fvad_vadm_lengths", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("fvad_engine_attach_vadm_ex", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("fvad_engine_set_stream_vadm", C.c_int, [C.c_void_p, I32P, C.c_int, C.c_int, C.c_void_p]),
+    ("fvad_engine_stream_vadm_config", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("fvad_engine_segments", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     ("fvad_engine_segments_range", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]),
     ("fvad_engine_vadm_state", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64),
@@ -577,12 +581,40 @@ class Engine:
     def clear_times(self):
         _check(lib().fvad_engine_clear_times(self.h), "fvad_engine_clear_times")
 
-    def attach_vadm(self, cfgs=None, seg_capacity=256):
-        """Run VADMachines on the device after every push (default config if None)."""
+    def attach_vadm(self, cfgs=None, seg_capacity=256, room=None):
+        """Run VADMachines on the device after every push (default config if None).
+        room not None (a list of VadmConfig, [] allowed): a config per (machine, stream)
+        that set_stream_vadm can change later (fvad_engine_attach_vadm_ex); every stream
+        starts on cfgs[m], and the rolling buffers are sized for cfgs and room together."""
         cfgs = list(cfgs) if cfgs else [VadmConfig.default()]
         arr = (VadmConfig * len(cfgs))(*cfgs)
         self._vadm_keep = arr
-        _check(lib().fvad_engine_attach_vadm(self.h, arr, len(cfgs), seg_capacity), "fvad_engine_attach_vadm")
+        if room is None:
+            _check(lib().fvad_engine_attach_vadm(self.h, arr, len(cfgs), seg_capacity), "fvad_engine_attach_vadm")
+            return
+        room = list(room)
+        rarr = (VadmConfig * max(1, len(room)))(*room)
+        _check(lib().fvad_engine_attach_vadm_ex(self.h, arr, len(cfgs), seg_capacity, rarr if room else None,
+                                                len(room)), "fvad_engine_attach_vadm_ex")
+
+    def set_stream_vadm(self, ids, cfgs, machine=0):
+        """Machine `machine` of stream ids[i] becomes a fresh machine of cfgs[i], between the
+        pushes submitted before and after the call; never waits for the device
+        (fvad_engine_set_stream_vadm; the engine was attached with room=...)."""
+        a = _ids(ids)
+        cfgs = list(cfgs)
+        if len(cfgs) != a.size:
+            raise ValueError("cfgs: one config per listed stream")
+        arr = (VadmConfig * max(1, len(cfgs)))(*cfgs)
+        _check(lib().fvad_engine_set_stream_vadm(self.h, a.ctypes.data_as(I32P), a.size, machine, arr),
+               "fvad_engine_set_stream_vadm")
+
+    def stream_vadm_config(self, stream, machine=0):
+        """The VadmConfig (stream, machine) runs now (the host's mirror: no sync)."""
+        c = VadmConfig()
+        _check(lib().fvad_engine_stream_vadm_config(self.h, stream, machine, C.byref(c)),
+               "fvad_engine_stream_vadm_config")
+        return c
 
     def segments(self, stream, machine=0):
         n = lib().fvad_engine_segments(self.h, stream, machine, None, 0)
@@ -734,7 +766,9 @@ class EngineGroup:
     GPU unless asked (--groups).  Engine g owns streams
     [first[g], first[g] + sizes[g])."""
 
-    def __init__(self, model, n_streams, n_channels=2, groups=2, vadm=False, seg_capacity=256, **kw):
+    def __init__(self, model, n_streams, n_channels=2, groups=2, vadm=False, seg_capacity=256, vadm_room=None,
+                 **kw):
+        """vadm_room not None: per-stream configs (Engine.attach_vadm's room) on every engine."""
         if not 1 <= groups <= n_streams:
             raise ValueError("groups must be in [1, n_streams]")
         q, r = divmod(n_streams, groups)
@@ -747,7 +781,7 @@ class EngineGroup:
             # out hardware queues in creation order
             e = Engine(model, n, n_channels, **kw)
             if vadm:  # True: the default machine; or a list of VadmConfig
-                e.attach_vadm(None if vadm is True else vadm, seg_capacity)
+                e.attach_vadm(None if vadm is True else vadm, seg_capacity, room=vadm_room)
             if g and kw.get("mode", "staged") != "fused":  # the fused engine has no side streams
                 e.share_streams(self.engines[0], SHARE_PREP | (SHARE_SIDE if vadm else 0))
             self.engines.append(e)
@@ -833,6 +867,21 @@ class EngineGroup:
             if mine.size:
                 e.reset_streams(mine)
 
+    def set_stream_vadm(self, global_ids, cfgs, machine=0):
+        """Engine.set_stream_vadm over the group's stream numbering."""
+        ids = _ids(global_ids)
+        cfgs = list(cfgs)
+        if len(cfgs) != ids.size:
+            raise ValueError("cfgs: one config per listed stream")
+        if ids.size and (ids.min() < 0 or ids.max() >= self.B):
+            raise ValueError("stream index out of range")
+        if len(set(ids.tolist())) != ids.size:
+            raise ValueError("duplicate stream index")
+        for e, f, n in zip(self.engines, self.first, self.sizes):
+            pick = np.flatnonzero((ids >= f) & (ids < f + n))
+            if pick.size:
+                e.set_stream_vadm(ids[pick] - f, [cfgs[i] for i in pick], machine)
+
 class Denoiser:
     """src/Denoiser.zig over the rnnoise_* C ABI (GPU, batch of one)."""
 
@@ -886,6 +935,15 @@ def kiss_fftr(x):
     out = np.zeros(2 * (n // 2 + 1), np.float32)
     lib().kiss_fftr(cfg, fptr(x), out.ctypes.data_as(C.c_void_p))
     return out[0::2] + 1j * out[1::2]
+
+
+def vadm_lengths(cfg, sample_rate=48000, fft_size=2048):
+    """(long-term, short-term, volume ratio) RollingAverage lengths cfg needs (fvad_vadm_lengths):
+    what an Engine.attach_vadm room has to cover for set_stream_vadm to accept cfg."""
+    out = (C.c_int * 3)()
+    _check(lib().fvad_vadm_lengths(C.byref(cfg) if cfg is not None else None, sample_rate, fft_size, out),
+           "fvad_vadm_lengths")
+    return tuple(out)
 
 
 class VADMachine:
@@ -1174,6 +1232,16 @@ class Sweep:
             last = self.last_run()
             self.n_cfgs, self.kept_segments = last["n_cfgs"], last["kept_segments"]
         return self._scores(agg, one)
+
+    @staticmethod
+    def best_per_stream(single, field="f_score"):
+        """One config index per stream from the per-stream stats score / run_score return
+        with single=True (single[cfg][stream]): the argmax over configs of `field`, NaN
+        counting as minus infinity, ties going to the lowest index (int64 array)."""
+        v = np.array([[d[field] for d in row] for row in single], np.float64)
+        if v.ndim != 2 or v.shape[0] < 1:
+            raise ValueError("single: [cfg][stream] stats, at least one config")
+        return np.argmax(np.where(np.isnan(v), -np.inf, v), axis=0)
 
     def last_run(self):
         """The last run: its configs, whether its segments were kept, the bytes copied back from the device."""

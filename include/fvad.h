@@ -385,6 +385,52 @@ int fvad_vadm_state(const fvad_vadm *v, int *speech_state, uint64_t *speech_star
  * last collected push's windows are not in the machine state yet; every
  * reader above flushes them first.  A reset or destroy drops them. */
 int fvad_engine_attach_vadm(fvad_engine *e, const fvad_vadm_config *cfgs, int n, int seg_capacity);
+
+/* Per-stream configs: a machine config per (machine, stream) that can be
+ * changed between pushes without touching any other stream -- where a config
+ * sweep's winner per stream (fvad_sweep_run_score's single_out) goes.
+ *
+ * RollingAverage lengths a config needs at (sample_rate, fft_size): out[0] long-term,
+ * out[1] short-term, out[2] volume ratio.  Host only. */
+int fvad_vadm_lengths(const fvad_vadm_config *cfg, int sample_rate, int fft_size, int out[3]);
+/* fvad_engine_attach_vadm with a config per (machine, stream) that can be changed later.
+ * cfgs[n]: the config every stream starts with on machine m.  room[n_room] (nullable, n_room 0):
+ * configs that are never run and only size the rolling buffers -- each of a machine's three
+ * lengths is the maximum over cfgs[m] and every room config.  All or nothing, like
+ * fvad_engine_attach_vadm.  Such an engine runs k_vadm_hbm_ps / k_vadm_par_ps, which read a
+ * stream's constants from a device table (fvad_engine_kernel_name reports them in k_vadm_hbm's
+ * and k_vadm_par's places), also while every stream still runs cfgs[m]; results are those of
+ * fvad_engine_attach_vadm for the same configs.  Everything else -- readers, the event feed,
+ * clip capture, fvad_engine_share_streams, the test hooks -- works as on a plain engine, except:
+ * fvad_engine_save_streams and fvad_engine_restore_streams return FVAD_EINVAL (the v1 blob's
+ * record layout and config_hash assume one config per machine; a v2 record that carries its
+ * configs is a later change). */
+int fvad_engine_attach_vadm_ex(fvad_engine *e, const fvad_vadm_config *cfgs, int n, int seg_capacity,
+                               const fvad_vadm_config *room, int n_room);
+/* Machine `machine` of the n listed streams becomes a freshly constructed machine of cfgs[i].
+ * Takes effect between the pushes submitted before the call and those submitted after it, as
+ * fvad_engine_reset_streams does (a pending machine pass of the previous push is queued first
+ * and sees the old config), and never waits for the device: the rows reach it in the argument
+ * blocks of k_vadm_retarget launches on the side stream, 47 rows a launch, so no buffer of the
+ * caller's has to outlive the call.  The new machine's state is fvad_vadm_create's for cfgs[i]
+ * with its three rolling buffers empty, but its window count is kept (window sample indices
+ * continue where the stream is); a deferred long-term fold the old machine owed is dropped
+ * with it.  Segments already emitted stay in fvad_engine_segments' list, and n_segments and
+ * the feed's seq continue.  A speech in progress (opening, open or closing) is abandoned: it
+ * produces no segment and no SEGMENT event, so a SPEECH_OPEN event already delivered for it
+ * stays unmatched.  Pending clips of clip capture are untouched.
+ * Checked before any device work (FVAD_EINVAL, the engine exactly as it was): the engine was
+ * attached with fvad_engine_attach_vadm_ex; the streams are distinct and in range and
+ * machine < n; each config's speech band is one of the engine's bands (the band slot is per
+ * stream); each of its three lengths fits the attached room (the message names the stream,
+ * the length and the room); FVAD_DEBUG_VADM_LT_FULL is not set.  n == 0: FVAD_OK.
+ * fvad_engine_reset_streams and fvad_engine_reset give each stream a fresh machine of its
+ * current config: the configs survive a reset. */
+int fvad_engine_set_stream_vadm(fvad_engine *e, const int32_t *streams, int n, int machine,
+                                const fvad_vadm_config *cfgs);
+/* The config (stream, machine) runs now (host mirror, no sync). */
+int fvad_engine_stream_vadm_config(const fvad_engine *e, int stream, int machine, fvad_vadm_config *out);
+
 /* total segments of (stream, machine) so far; copies min(total, capacity, cap) */
 size_t fvad_engine_segments(fvad_engine *e, int stream, int machine, fvad_segment *out, size_t cap);
 /* the same from segment index `first` on (returns the total count) */
