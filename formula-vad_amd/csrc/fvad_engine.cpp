@@ -40,7 +40,10 @@ int fvad::set_error(int code, const std::string &msg) {
 }
 extern "C" const char *fvad_version(void) { return "fvad-mi355x 0.1 (gfx950)"; }
 
-void fvad_engine_set_raw_s16(fvad_engine *e, int raw) { e->raw_s16 = raw; }
+// (the rnnoise compat path is 48 kHz only: ignored on a resampling engine)
+void fvad_engine_set_raw_s16(fvad_engine *e, int raw) {
+  if (!e->rs) e->raw_s16 = raw;
+}
 
 extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams, int n_channels) {
   std::memset(c, 0, sizeof(*c));
@@ -56,6 +59,7 @@ extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams,
   c->band_hi[0] = 64;
   c->want_denoised = 0;
   c->use_denoiser = 1;
+  c->input_rate = 0;
 }
 
 namespace {
@@ -187,6 +191,9 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
   if (e->d_work) HIP_TRY(hipMemsetAsync(e->d_work.get(), 0, sizeof(unsigned) * fvad::kWorkCounters, e->stream.get()));
   HIP_TRY(hipMemsetAsync(e->d_ring.get(), 0,
                          sizeof(float) * (size_t)e->ring_len * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
+  if (e->rs)  // (their owner, the prep stream, is idle: synchronised above)
+    HIP_TRY(hipMemsetAsync(e->rs->tails.get(), 0,
+                           sizeof(float) * (size_t)(e->rs->d.K - 1) * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
   return FVAD_OK;
 }
@@ -232,6 +239,11 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   if (!cfg || !model || !out) return fail(FVAD_EINVAL, "null argument");
   const fvad_engine_config &c = *cfg;
   if (c.sample_rate != 48000) return fail(FVAD_ERATE, "only 48 kHz is supported (VAD.zig:101-104)");
+  // input_rate: 0 or 48000 for none, or a rate k_resample brings to 48 kHz
+  const bool resample = c.input_rate != 0 && c.input_rate != 48000;
+  fvad::rs::Desc rd{};
+  if (resample && !fvad::rs::describe(c.input_rate, rd))
+    return fail(FVAD_ERATE, "input_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
   if (c.n_streams < 1 || c.n_channels < 1 || c.n_channels > FVAD_MAX_CHANNELS)
     return fail(FVAD_EINVAL, "n_streams >= 1 and 1 <= n_channels <= 8 required");
   // FFT.zig:29-31: any even, non-zero size.  fft_size < 480 completes several
@@ -267,6 +279,7 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
 
   fvad_engine *e = new fvad_engine();
   e->cfg = c;
+  if (!resample) e->cfg.input_rate = 0;
   // the staged path writes every tick of a push before FFT B reads its
   // windows, so the ring holds one window plus a whole push
   // the re-block ring holds a window plus a push; a multiple of 4 so a
@@ -379,6 +392,11 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
           1, std::min<long long>({units, 2LL * e->grid_frames, (1LL << 30) / per}));
       if ((rc = make_dev(e->d_fbwork, (size_t)e->fb_work_blocks * e->fb_work_stride))) return bail(rc);
     }
+  }
+  if (resample) {
+    e->rs.reset(new Resample());
+    e->rs->d = rd;
+    if ((rc = resample_make(e))) return bail(rc);
   }
   if ((rc = fvad_engine_reset(e))) return bail(rc);
   *out = e;
@@ -636,6 +654,13 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
 
 int fvad::eng::launch(fvad_engine *e, int n_ticks, bool use_ticks, bool timed, bool use_tail) {
   if (!e->cfg.use_denoiser) timed = false;  // the no-denoiser pipeline records no kernel events
+  if (e->rs) {
+    // the push's first kernel: the raw input to 48 kHz, on the stream that
+    // owns the tails, behind the copies of the input and of ticks_valid
+    const int *tv = !use_ticks ? nullptr
+                    : e->cfg.mode != FVAD_MODE_FUSED ? e->d_ticks_b[e->next_buf].get() : e->d_ticks;
+    if (const int rr = resample_push(e, n_ticks, tv)) return rr;
+  }
   const int rc = e->cfg.mode == FVAD_MODE_FUSED ? run_fused(e, n_ticks, use_ticks, timed)
                                                  : run_staged(e, n_ticks, use_ticks, use_tail, timed);
   if (!rc && timed) e->slot_pending[e->ev_slot] = true;
@@ -709,7 +734,7 @@ extern "C" int fvad_engine_push_ex(fvad_engine *e, const float *pcm, int n_ticks
   std::vector<int32_t> tt;
   if ((rc = tail_ticks(e, ticks_valid, last_tick_samples, n_ticks, tt))) return rc;
   HIP_TRY(hipSetDevice(c.device));
-  const size_t bytes = (size_t)n_ticks * c.n_streams * c.n_channels * fvad::kFrame * sizeof(float);
+  const size_t bytes = (size_t)n_ticks * c.n_streams * c.n_channels * input_frame(e) * sizeof(float);
   // staged: the inputs go through the prep stream (ticks buffer b is free
   // once push k-2 finished)
   hipStream_t cs = e->stream.get();
@@ -721,7 +746,8 @@ extern "C" int fvad_engine_push_ex(fvad_engine *e, const float *pcm, int n_ticks
     dticks = e->d_ticks_b[b].get();
   }
   if ((rc = input_buffer(e, cs))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->d_pcm, pcm, bytes, hipMemcpyHostToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(input_target(e), pcm, bytes, hipMemcpyHostToDevice, cs));
+  if (e->rs) e->rs->in16 = false;
   if (!tt.empty()) {  // ticks and tails, [2 * B] (synchronous copy: tt is a local)
     HIP_TRY(hipMemcpyAsync(dticks, tt.data(), sizeof(int32_t) * tt.size(), hipMemcpyHostToDevice, cs));
     HIP_TRY(hipStreamSynchronize(cs));
@@ -746,6 +772,7 @@ extern "C" int fvad_engine_load_synthetic(fvad_engine *e, int n_ticks, uint32_t 
 // block.
 extern "C" int fvad_engine_load_synthetic_ex(fvad_engine *e, int n_ticks, int n_pushes, uint32_t base) {
   if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (e->rs) return fail(FVAD_EINVAL, "the synthetic generator is 48 kHz: not available on a resampling engine");
   const fvad_engine_config &c = e->cfg;
   if (n_ticks < 1 || n_ticks > c.max_ticks) return fail(FVAD_EINVAL, "n_ticks out of range");
   if (n_pushes < 1 || (long long)n_ticks * n_pushes > (1LL << 30))
@@ -793,6 +820,7 @@ extern "C" int fvad_engine_resident_seek(fvad_engine *e, int push) {
 
 extern "C" int fvad_engine_run_resident(fvad_engine *e, int n_ticks) {
   if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (e->rs) return fail(FVAD_EINVAL, "no resident input on a resampling engine");
   if (n_ticks < 1 || n_ticks > e->resident_ticks) return fail(FVAD_EINVAL, "n_ticks exceeds resident input");
   HIP_TRY(hipSetDevice(e->cfg.device));
   // the set this push will record into was used two pushes ago: read it (it
@@ -872,6 +900,10 @@ extern "C" int fvad_engine_clear_times(fvad_engine *e) {
   }
   e->et_ms_sum = 0;
   e->et_timed = 0;
+  if (e->rs) {
+    e->rs->ms_sum = 0;
+    e->rs->n_timed = 0;
+  }
   if (e->cap)
     for (int k = 0; k < 2; k++) {
       e->cap->ms_sum[k] = 0;

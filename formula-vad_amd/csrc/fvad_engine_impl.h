@@ -19,6 +19,7 @@
 #include "fvad_kernels.h"
 #include "fvad_lifecycle.h"
 #include "fvad_machine.h"
+#include "fvad_resample.h"
 #include "fvad_staged.h"
 
 #define HIP_TRY(expr)                                                                                             \
@@ -113,6 +114,24 @@ struct Capture {
   EventTimer at[2], pt[2];  // k_hist_append (by push parity) and the pass (by vadm_slot)
   double ms_sum[2] = {};
   int n_timed[2] = {};
+};
+
+// Input resampling (fvad_engine_config.input_rate; DESIGN.md section 7, "Input
+// resampling"): everything it owns, made by fvad_engine_create; an engine of
+// 48 kHz input has none of it.
+struct Resample {
+  rs::Desc d{};
+  dev_ptr<float> taps;    // [L][K]
+  dev_ptr<float> tails;   // [s][c][K - 1], the prep stream's (fused: the engine stream's)
+  // the push as the host sent it, float or int16: the parity of d_pcm_b,
+  // released by the same ev_in_free (recorded behind the reader of d_pcm,
+  // which is behind k_resample)
+  dev_ptr<float> raw[2];  // max_ticks * B * C * n_in words each
+  bool in16 = false;      // the push being launched holds int16 samples
+  EventTimer tm[2];       // the resample launches of a push, alternately
+  int slot = 0;
+  double ms_sum = 0;
+  int n_timed = 0;
 };
 }  // namespace eng
 }  // namespace fvad
@@ -342,6 +361,8 @@ struct fvad_engine {
   int rt_next = 0;
   double rt_ms[3] = {};
   int rt_n[3] = {};
+  // input resampling (input_rate set): null on an engine of 48 kHz input
+  std::unique_ptr<fvad::eng::Resample> rs;
   // clip capture, last: released before everything it refers to
   std::unique_ptr<fvad::eng::Capture> cap;
 };
@@ -361,6 +382,13 @@ int release_input(fvad_engine *e);
 int check_ticks(const fvad_engine *e, const int32_t *ticks_valid, int n_ticks);
 int tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, const int32_t *last, int n_ticks,
                std::vector<int32_t> &tt);
+// input resampling: samples per tick and channel of a push, where its H2D
+// copy goes, the stream that owns the tails, and the push's resample launches
+int input_frame(const fvad_engine *e);
+void *input_target(const fvad_engine *e);
+hipStream_t resample_stream(const fvad_engine *e);
+int resample_make(fvad_engine *e);
+int resample_push(fvad_engine *e, int n_ticks, const int *d_ticks);
 // fvad_engine_vadm.cpp
 int vadm_reset(fvad_engine *e);
 int vadm_flush(fvad_engine *e, bool fast = true);

@@ -34,6 +34,87 @@ int fvad::eng::release_input(fvad_engine *e) {
   return FVAD_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Input resampling (input_rate set; fvad_resample.h): the host's copies go to
+// the raw buffer of d_pcm's parity, k_resample writes d_pcm from it
+// ---------------------------------------------------------------------------
+int fvad::eng::input_frame(const fvad_engine *e) { return e->rs ? e->rs->d.n_in : fvad::kFrame; }
+
+// where the H2D copy of the push about to launch goes (after input_buffer)
+void *fvad::eng::input_target(const fvad_engine *e) {
+  return e->rs ? static_cast<void *>(e->rs->raw[e->in_next].get()) : static_cast<void *>(e->d_pcm);
+}
+
+// the tails' owner: k_resample runs there, ahead of the push's first reader
+// of d_pcm (staged: the prep stream, with and without the denoiser)
+hipStream_t fvad::eng::resample_stream(const fvad_engine *e) {
+  return e->cfg.mode != FVAD_MODE_FUSED ? e->pstream : e->stream.get();
+}
+
+// fvad_engine_create's part: the table, the tails (zeroed by the reset that
+// follows) and the raw staging
+int fvad::eng::resample_make(fvad_engine *e) {
+  Resample &r = *e->rs;
+  const fvad_engine_config &c = e->cfg;
+  const std::vector<float> &taps = fvad::resample_table(r.d);
+  const size_t rows = (size_t)c.n_streams * c.n_channels;
+  int rc;
+  if ((rc = fvad::make_dev(r.taps, taps.size())) || (rc = fvad::make_dev(r.tails, rows * (r.d.K - 1))) ||
+      (rc = fvad::make_dev(r.raw[0], (size_t)c.max_ticks * rows * r.d.n_in)) ||
+      (rc = fvad::make_dev(r.raw[1], (size_t)c.max_ticks * rows * r.d.n_in)) || (rc = r.tm[0].create()) ||
+      (rc = r.tm[1].create()))
+    return rc;
+  HIP_TRY(hipMemcpy(r.taps.get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+  return FVAD_OK;
+}
+
+// the resample launches of the push about to launch, timed without waiting
+// (a sample still running when its timer comes round again is dropped)
+int fvad::eng::resample_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
+  Resample &r = *e->rs;
+  fvad::ResampleArgs a{};
+  a.raw = r.raw[e->in_next].get();
+  a.taps = r.taps.get();
+  a.tails = r.tails.get();
+  a.ticks_valid = d_ticks;
+  a.out = e->d_pcm;
+  a.n_streams = e->cfg.n_streams;
+  a.n_channels = e->cfg.n_channels;
+  a.n_ticks = n_ticks;
+  a.in16 = r.in16;
+  a.d = r.d;
+  hipStream_t st = resample_stream(e);
+  EventTimer &tm = r.tm[r.slot ^= 1];
+  int rc;
+  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
+  HIP_TRY(fvad::launch_resample(a, st));
+  return tm.end(st);
+}
+
+extern "C" int fvad_engine_input_frame(const fvad_engine *e) { return e ? input_frame(e) : FVAD_EINVAL; }
+
+extern "C" int fvad_engine_fetch_input(fvad_engine *e, int n_ticks, float *pcm48) {
+  if (!e || !pcm48) return fail(FVAD_EINVAL, "null argument");
+  if (!e->rs) return fail(FVAD_EINVAL, "fvad_engine_fetch_input reads a resampling engine (input_rate)");
+  if (n_ticks < 1 || n_ticks > e->cfg.max_ticks) return fail(FVAD_EINVAL, "n_ticks out of range");
+  if (const int rc = fvad_engine_sync(e)) return rc;
+  HIP_TRY(hipMemcpy(pcm48, e->d_pcm, (size_t)n_ticks * e->cfg.n_streams * e->cfg.n_channels * fvad::kFrame * sizeof(float),
+                    hipMemcpyDeviceToHost));
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs) {
+  if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
+  if (!e->rs) return fail(FVAD_EINVAL, "fvad_engine_resample_times reads a resampling engine (input_rate)");
+  if (const int rc = fvad_engine_sync(e)) return rc;
+  Resample &r = *e->rs;
+  for (EventTimer &tm : r.tm)
+    if (const int rc = tm.collect(r.ms_sum, r.n_timed)) return rc;
+  *ms_avg = r.n_timed ? r.ms_sum / r.n_timed : 0.0;
+  if (n_runs) *n_runs = r.n_timed;
+  return FVAD_OK;
+}
+
 int fvad::eng::check_ticks(const fvad_engine *e, const int32_t *ticks_valid, int n_ticks) {
   if (ticks_valid)
     for (int s = 0; s < e->cfg.n_streams; s++)
@@ -50,6 +131,11 @@ int fvad::eng::tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, cons
   tt.clear();
   if (!last) return FVAD_OK;
   const int B = e->cfg.n_streams;
+  if (e->rs) {  // whole ticks only: the resampler's phase restarts with every tick
+    for (int s = 0; s < B; s++)
+      if (last[s] != e->rs->d.n_in) return fail(FVAD_EINVAL, "a resampling engine consumes whole ticks only");
+    return FVAD_OK;
+  }
   bool partial = false;
   for (int s = 0; s < B; s++) {
     if (last[s] < 1 || last[s] > fvad::kFrame) return fail(FVAD_EINVAL, "last_tick_samples out of range [1, 480]");
@@ -120,7 +206,7 @@ int ensure_slots(fvad_engine *e, int i) {
   // what an earlier, partly failed call allocated is kept and reused
   auto host = [](auto &p, size_t count) { return p ? FVAD_OK : fvad::make_pinned(p, count); };
   int rc;
-  if ((rc = host(sl.in, frames)) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
+  if ((rc = host(sl.in, TB * C * input_frame(e))) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
       (rc = host(sl.ratio, TB)) || (rc = host(sl.wflag, TB)) || (rc = host(sl.wratio, TBW)) ||
       (rc = host(sl.wvad, TBW)) || (rc = host(sl.band, TBW * C * c.n_bands)) ||
       (c.want_denoised && (rc = host(sl.den, frames))))
@@ -130,12 +216,14 @@ int ensure_slots(fvad_engine *e, int i) {
 }
 
 // slot i's pinned 16-bit input and the device staging buffer, on first use
+// (a resampling engine has its raw buffers instead of the staging buffer)
 int ensure_slots16(fvad_engine *e, int i) {
   const fvad_engine_config &c = e->cfg;
-  const size_t n = (size_t)c.max_ticks * c.n_streams * c.n_channels * fvad::kFrame;
+  const size_t n = (size_t)c.max_ticks * c.n_streams * c.n_channels * input_frame(e);
   auto &sl = e->slots[i];
   int rc;
-  if ((!sl.in16 && (rc = fvad::make_pinned(sl.in16, n))) || (!e->d_pcm16 && (rc = fvad::make_dev(e->d_pcm16, n))))
+  if ((!sl.in16 && (rc = fvad::make_pinned(sl.in16, n))) ||
+      (!e->rs && !e->d_pcm16 && (rc = fvad::make_dev(e->d_pcm16, n))))
     return rc;
   return FVAD_OK;
 }
@@ -188,7 +276,8 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   auto &sl = e->slots[si];
   if (sl.pending) return fail(FVAD_EINVAL, "FVAD_MAX_IN_FLIGHT pushes in flight: collect the oldest one first");
   const size_t B = c.n_streams, TB = (size_t)n_ticks * B, TBW = TB * e->wpt;
-  const size_t n_samples = TB * c.n_channels * fvad::kFrame, bytes = n_samples * sizeof(float);
+  // (n_samples: the input's, at the engine's input rate; bytes: the denoised output's)
+  const size_t n_samples = TB * c.n_channels * input_frame(e), bytes = TB * c.n_channels * fvad::kFrame * sizeof(float);
   Sample *slot_in;
   if constexpr (k16)
     slot_in = sl.in16.get();
@@ -212,8 +301,13 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   // staged with the denoiser: k_prep3 reads the 16-bit samples straight from
   // the input buffer (half its input bytes; the copy stream carries only the
   // H2D copy, and no conversion kernel takes a slot beside the pushes)
-  const bool direct16 = k16 && staged && c.use_denoiser && !e->raw_s16;
-  if constexpr (k16) {
+  const bool direct16 = k16 && staged && c.use_denoiser && !e->raw_s16 && !e->rs;
+  if (e->rs) {
+    // a resampling engine: the samples as they are into the raw buffer;
+    // k_resample (launch) converts and writes d_pcm as f32
+    HIP_TRY(hipMemcpyAsync(input_target(e), slot_in, n_samples * sizeof(Sample), hipMemcpyHostToDevice, cs));
+    e->rs->in16 = k16;
+  } else if constexpr (k16) {
     if (direct16) {
       HIP_TRY(hipMemcpyAsync(e->d_pcm, sl.in16.get(), n_samples * sizeof(int16_t), hipMemcpyHostToDevice, cs));
     } else {
@@ -223,7 +317,7 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
       HIP_TRY(fvad::launch_pcm16(e->d_pcm16.get(), e->d_pcm, n_samples, cs));
     }
   } else {
-    HIP_TRY(hipMemcpyAsync(e->d_pcm, sl.in.get(), bytes, hipMemcpyHostToDevice, cs));
+    HIP_TRY(hipMemcpyAsync(e->d_pcm, sl.in.get(), n_samples * sizeof(float), hipMemcpyHostToDevice, cs));
   }
   if (use_ticks) {
     int *dticks = e->d_ticks;

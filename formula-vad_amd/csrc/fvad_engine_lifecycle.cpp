@@ -40,11 +40,14 @@ uint64_t config_hash_of(const fvad_engine *e) {
                     m.min_vad_duration_sec})
       h = fnv_add(h, v);
   }
+  // a resampling engine's rate; an engine of 48 kHz input hashes what it always did
+  if (e->rs) h = fnv_add(h, e->rs->d.rate);
   return h;
 }
 
 fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
-  return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap);
+  return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap,
+                           e->rs ? e->rs->d.K - 1 : 0);
 }
 
 fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
@@ -66,6 +69,7 @@ fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   h.config_hash = config_hash_of(e);
   h.model_hash = e->model_hash;
   h.sample_rate = (uint32_t)e->cfg.sample_rate;
+  h.reserved[0] = e->rs ? (uint32_t)e->rs->d.rate : 0u;
   return h;
 }
 
@@ -103,6 +107,7 @@ fvad::XferArgs xfer_args(const fvad_engine *e, const fvad::BlobLayout &lay) {
   a.vadm = e->vadm;
   a.lay = lay;
   a.blob = e->d_blob.get();
+  a.rs_tails = e->rs ? e->rs->tails.get() : nullptr;
   return a;
 }
 
@@ -203,6 +208,13 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
       va.ids = ca.ids;
       HIP_TRY(fvad::launch_stream_vclear(va, e->side));
     }
+    if (e->rs) {  // the resampler's tails, on the stream k_resample runs on
+      fvad::ResampleClearArgs ra{};
+      ra.tails = e->rs->tails.get();
+      ra.row_words = e->cfg.n_channels * (e->rs->d.K - 1);
+      ra.ids = ca.ids;
+      HIP_TRY(fvad::launch_resample_clear(ra, resample_stream(e)));
+    }
   }
   // clip capture: the streams' positions restart behind the appends already
   // queued, their pending clips go behind the passes already queued
@@ -280,6 +292,7 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
       h.use_denoiser != mine.use_denoiser || h.n_bands != mine.n_bands || h.n_machines != mine.n_machines ||
       h.state_words != mine.state_words || h.sample_rate != mine.sample_rate)
     return fail(FVAD_EFORMAT, "stream blob from an engine with another mode, channels, fft_size, bands or machines");
+  if (h.reserved[0] != mine.reserved[0]) return fail(FVAD_EFORMAT, "stream blob from an engine with another input_rate");
   if (h.config_hash != mine.config_hash) return fail(FVAD_EFORMAT, "stream blob from another engine configuration");
   if (h.model_hash != mine.model_hash) return fail(FVAD_EFORMAT, "stream blob from another model");
   if ((h.n_machines > 0) != (h.seg_capacity > 0) || h.seg_capacity > 0x7fffffffu / 32)

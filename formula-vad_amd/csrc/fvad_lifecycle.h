@@ -42,12 +42,15 @@ static_assert(st::kWords % 64 == 0 && st::kPitch == 0 && kPitchBuf % 4 == 0 && s
 //   o_mach[m]                   machine m: VadmState | long-term row [lt_pitch] |
 //                               short-term [pad4(n_st)] | ratio [pad4(n_r)] |
 //                               segments [pad4(6 * seg_cap)] (min(n_segs, seg_cap) stored, zeros after)
+//   o_rs + c * rs_pad           a resampling engine only (rs_tail = K - 1 > 0): channel c's resampler
+//                               tail, its last rs_tail input samples, zeros after
 struct BlobLayout {
-  int n_channels, n_mach, seg_cap, fft_size, use_denoiser;
-  long long pend_pad, o_ring, o_mach[kMaxBandCfg], words;
+  int n_channels, n_mach, seg_cap, fft_size, use_denoiser, rs_tail;
+  long long pend_pad, o_ring, o_mach[kMaxBandCfg], rs_pad, o_rs, words;
 };
 constexpr long long pad4(long long x) { return (x + 3) & ~3LL; }
-inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, const VadmArgs &v, int seg_cap) {
+inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, const VadmArgs &v, int seg_cap,
+                              int rs_tail = 0) {
   BlobLayout L{};
   L.n_channels = n_channels;
   L.n_mach = v.n;
@@ -62,6 +65,10 @@ inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, co
     o += kVadmStateWords + pad4(v.c[m].lt_pitch) + pad4(v.c[m].n_st) + pad4(v.c[m].n_r) +
          pad4((long long)kVadmSegWords * seg_cap);
   }
+  L.rs_tail = rs_tail;
+  L.rs_pad = pad4(rs_tail);
+  L.o_rs = o;
+  o += (long long)n_channels * L.rs_pad;
   L.words = o;
   return L;
 }
@@ -126,6 +133,7 @@ struct XferArgs {
   VadmArgs vadm;
   BlobLayout lay;
   float *blob;        // device staging: records of lay.words each
+  float *rs_tails;    // [s][c][lay.rs_tail], a resampling engine's (fvad_resample.h)
   IdList slots, recs;  // stream slots[i] <-> record recs[i]
 };
 

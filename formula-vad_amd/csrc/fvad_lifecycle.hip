@@ -99,7 +99,8 @@ __global__ void __launch_bounds__(kNT) k_vadm_retarget(RetargetArgs a) {
 }
 
 // stream slots[i] -> record recs[i].  part 0: state; 1 + c: channel c's
-// pending window part; 1 + C + m: machine m
+// pending window part; 1 + C + m: machine m; 1 + C + n_mach (a resampling
+// engine): the channels' resampler tails
 __global__ void __launch_bounds__(kNT) k_stream_gather(XferArgs a) {
   const int s = a.slots.id[blockIdx.x], part = blockIdx.y, tid = threadIdx.x;
   const BlobLayout &L = a.lay;
@@ -108,6 +109,11 @@ __global__ void __launch_bounds__(kNT) k_stream_gather(XferArgs a) {
   const float *stp = a.state + (size_t)s * st::kWords;
   if (part == 0) {
     copy4(rec, stp, st::kWords, tid);
+  } else if (part == 1 + C + L.n_mach) {
+    const float *tails = a.rs_tails + (size_t)s * C * L.rs_tail;
+    for (int c = 0; c < C; c++)
+      for (int j = tid; j < (int)L.rs_pad; j += kNT)
+        rec[L.o_rs + (size_t)c * L.rs_pad + j] = j < L.rs_tail ? tails[(size_t)c * L.rs_tail + j] : 0.0f;
   } else if (part <= C) {
     const int c = part - 1;
     const unsigned long long total = record_samples(stp, L.use_denoiser);
@@ -149,6 +155,10 @@ __global__ void __launch_bounds__(kNT) k_stream_scatter(XferArgs a) {
   const float *rec = a.blob + (size_t)a.recs.id[blockIdx.x] * L.words;
   if (part == 0) {
     copy4(a.state + (size_t)s * st::kWords, rec, st::kWords, tid);
+  } else if (part == 1 + C + L.n_mach) {
+    float *tails = a.rs_tails + (size_t)s * C * L.rs_tail;
+    for (int c = 0; c < C; c++)
+      for (int j = tid; j < L.rs_tail; j += kNT) tails[(size_t)c * L.rs_tail + j] = rec[L.o_rs + (size_t)c * L.rs_pad + j];
   } else if (part <= C) {
     const int c = part - 1;
     const unsigned long long total = record_samples(rec, L.use_denoiser);
@@ -208,7 +218,7 @@ hipError_t launch_vadm_retarget(const RetargetArgs &a, hipStream_t stream) {
 hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream) {
   if (a.slots.n < 1) return hipSuccess;
   (void)hipGetLastError();
-  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach;
+  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach + (a.lay.rs_tail > 0 ? 1u : 0u);
   hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)a.slots.n, parts), dim3(kNT), 0, stream, a);
   return launched();
 }
@@ -216,7 +226,7 @@ hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream) {
 hipError_t launch_stream_scatter(const XferArgs &a, hipStream_t stream) {
   if (a.slots.n < 1) return hipSuccess;
   (void)hipGetLastError();
-  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach;
+  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach + (a.lay.rs_tail > 0 ? 1u : 0u);
   hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)a.slots.n, parts), dim3(kNT), 0, stream, a);
   return launched();
 }

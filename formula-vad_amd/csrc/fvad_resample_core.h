@@ -1,0 +1,74 @@
+// Input resampling to 48 kHz (fvad_engine_config.input_rate; DESIGN.md section
+// 7, "Input resampling"): the index arithmetic and the accumulate loop, for
+// host and device.  k_resample (fvad_resample.hip) and fvad_resample_host
+// (fvad_resample.cpp) both run this code, so they agree by the bits.
+//
+// A tick is 10 ms: n_in = rate / 100 input samples give 480 output samples.
+// With g = gcd(48000, rate), L = 48000 / g and M = rate / g, output r of a
+// tick reads the K inputs ending at i = floor(r M / L) through phase
+// p = r M mod L of a polyphase FIR of L x K taps; 480 M / L = n_in, so every
+// tick starts at phase 0 and the arithmetic never needs an absolute index.
+#pragma once
+#pragma clang fp contract(off)
+#include "fvad_exact.h"  // FVAD_HD
+
+namespace fvad {
+namespace rs {
+
+constexpr int kOut = 480;      // output samples per tick
+constexpr int kRates = 6;      // the closed list of input rates
+constexpr int kMaxTaps = 160 * 48;  // L * K at 44.1 kHz, the largest table
+constexpr int kMaxTail = 95;   // K - 1 at 96 kHz, the longest history
+
+struct Desc {
+  int rate, L, M, K, n_in;
+};
+
+FVAD_HD inline int gcd(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+// false off the list
+FVAD_HD inline bool describe(int rate, Desc &d) {
+  if (rate != 8000 && rate != 16000 && rate != 24000 && rate != 32000 && rate != 44100 && rate != 96000) return false;
+  const int g = gcd(48000, rate);
+  d.rate = rate;
+  d.L = 48000 / g;
+  d.M = rate / g;
+  d.K = 48 * ((d.M + d.L - 1) / d.L);  // 48 max(1, ceil(M / L))
+  d.n_in = rate / 100;
+  return true;
+}
+
+// output r of a tick: the newest input it reads (relative to the tick's first
+// sample) and its phase.  r M <= 479 * 147.
+FVAD_HD inline void position(int r, int L, int M, int &i, int &p) {
+  const int rm = r * M;
+  i = rm / L;
+  p = rm - i * L;
+}
+
+// 16-bit input k: k_pcm16's conversion, exact in f32
+FVAD_HD inline float sample(float v) { return v; }
+FVAD_HD inline float sample(short v) { return (float)v * (1.0f / 32768.0f); }
+
+// N outputs of one phase: acc[n] = sum over k ascending of tap(k) * x(n, k),
+// x(n, k) the input k samples before output n's newest.  The product is
+// rounded to f32, then the sum; nothing fused (the pragma above, and the
+// host's -ffp-contract=off), nothing re-associated.
+template <int N, typename Tap, typename X>
+FVAD_HD inline void accumulate(int K, Tap tap, X x, float (&acc)[N]) {
+  for (int n = 0; n < N; n++) acc[n] = 0.0f;
+  for (int k = 0; k < K; k++) {
+    const float t = tap(k);
+    for (int n = 0; n < N; n++) acc[n] = acc[n] + t * x(n, k);
+  }
+}
+
+}  // namespace rs
+}  // namespace fvad

@@ -38,7 +38,13 @@ class EngineConfig(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_channels", C.c_int), ("device", C.c_int), ("sample_rate", C.c_int),
                 ("fft_size", C.c_int), ("max_ticks", C.c_int), ("n_bands", C.c_int),
                 ("band_lo", C.c_int * MAX_BANDS), ("band_hi", C.c_int * MAX_BANDS), ("want_denoised", C.c_int),
-                ("mode", C.c_int), ("use_denoiser", C.c_int)]
+                ("mode", C.c_int), ("use_denoiser", C.c_int), ("input_rate", C.c_int)]
+
+
+class ResampleDesc(C.Structure):
+    """fvad_resample_desc (include/fvad.h)."""
+    _fields_ = [("input_rate", C.c_int), ("L", C.c_int), ("M", C.c_int), ("taps_per_phase", C.c_int),
+                ("frame_in", C.c_int), ("delay", C.c_double)]
 
 
 MODE_STAGED, MODE_FUSED, MODE_FP16, MODE_FP16_FUSED, MODE_F32_FAST = 0, 1, 2, 3, 4
@@ -255,6 +261,12 @@ SYMBOLS = [
     ("fvad_engine_output_log_read", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     ("fvad_engine_clear_times", C.c_int, [C.c_void_p]),
     ("fvad_engine_fetch", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("fvad_resample_info", C.c_int, [C.c_int, C.c_void_p]),
+    ("fvad_resample_taps", C.c_size_t, [C.c_int, F32P, C.c_size_t]),
+    ("fvad_resample_host", C.c_int, [C.c_int, F32P, C.c_size_t, F32P, F32P]),
+    ("fvad_engine_input_frame", C.c_int, [C.c_void_p]),
+    ("fvad_engine_fetch_input", C.c_int, [C.c_void_p, C.c_int, F32P]),
+    ("fvad_engine_resample_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("fvad_vadm_config_default", None, [C.c_void_p]),
     ("fvad_vadm_create", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fvad_vadm_destroy", None, [C.c_void_p]),
@@ -407,11 +419,45 @@ def synth_cache_clear():
     lib().fvad_synth_cache_clear()
 
 
+def resample_info(input_rate):
+    """fvad_resample_info: the resampler of an input rate as a dict -- L, M,
+    taps_per_phase, frame_in and the delay in 48 kHz samples (host only)."""
+    d = ResampleDesc()
+    _check(lib().fvad_resample_info(input_rate, C.byref(d)), "fvad_resample_info")
+    return {n: getattr(d, n) for n, _ in d._fields_}
+
+
+def resample_taps(input_rate):
+    """fvad_resample_taps: the [L][taps_per_phase] float32 tap table (host only)."""
+    d = resample_info(input_rate)
+    out = np.zeros((d["L"], d["taps_per_phase"]), np.float32)
+    n = lib().fvad_resample_taps(input_rate, fptr(out), out.size)
+    assert n == out.size, (n, out.shape)
+    return out
+
+
+def resample_host(input_rate, x, tail=None):
+    """fvad_resample_host: one channel's whole ticks x ([n_ticks * frame_in]
+    float32) at 48 kHz ([n_ticks * 480]), the arithmetic of the engine's
+    k_resample.  tail (float32 [taps_per_phase - 1], updated in place): the
+    samples before x[0]; None: zeros, nothing kept."""
+    d = resample_info(input_rate)
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    assert x.size % d["frame_in"] == 0, (x.size, d["frame_in"])
+    n_ticks = x.size // d["frame_in"]
+    if tail is not None:
+        assert tail.dtype == np.float32 and tail.flags.c_contiguous and tail.size == d["taps_per_phase"] - 1
+    out = np.zeros(n_ticks * FRAME, np.float32)
+    _check(lib().fvad_resample_host(input_rate, fptr(x), n_ticks, fptr(tail) if tail is not None else None,
+                                    fptr(out)), "fvad_resample_host")
+    return out
+
+
 class Engine:
     """Batched hot path for a partition of streams on one GPU."""
 
     def __init__(self, model, n_streams, n_channels=2, device=0, max_ticks=100, fft_size=2048, bands=((4, 64),),
-                 want_denoised=False, mode="staged", use_denoiser=True):
+                 want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000):
         cfg = EngineConfig()
         lib().fvad_engine_config_default(C.byref(cfg), n_streams, n_channels)
         cfg.device = device
@@ -425,6 +471,8 @@ class Engine:
         cfg.mode = {"staged": MODE_STAGED, "fused": MODE_FUSED, "fp16": MODE_FP16, "fp16_fused": MODE_FP16_FUSED,
                     "f32_fast": MODE_F32_FAST}[mode]
         cfg.use_denoiser = int(use_denoiser)
+        # 8000 .. 96000: the pushes are at that rate, resampled to 48 kHz on the device
+        cfg.input_rate = 0 if input_rate in (0, 48000) else input_rate
         self.cfg = cfg
         self.model = model
         h = C.c_void_p()
@@ -435,6 +483,8 @@ class Engine:
         # window slots per (tick, stream): 1 for fft_size >= 480, else several
         # (VAD.zig:307-347); with W > 1 the window outputs get a slot axis
         self.wpt = lib().fvad_engine_windows_per_tick(h)
+        # input samples per tick and channel: input_rate / 100 (480 at 48 kHz)
+        self.frame_in = lib().fvad_engine_input_frame(h)
 
     def _alloc_out(self, n_ticks, denoised):
         T, B, Ch, nb, W = n_ticks, self.B, self.C, self.nb, self.wpt
@@ -449,11 +499,11 @@ class Engine:
         return o, s
 
     def push(self, pcm, ticks_valid=None, denoised=False, last_tick_samples=None):
-        """pcm: [ticks][streams][channels][480] normalised f32; last_tick_samples
+        """pcm: [ticks][streams][channels][frame_in] normalised f32; last_tick_samples
         (no-denoiser engines): real samples in each stream's last valid tick."""
         pcm = np.ascontiguousarray(pcm, np.float32)
         T = pcm.shape[0]
-        assert pcm.shape[1:] == (self.B, self.C, FRAME), pcm.shape
+        assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
         o, s = self._alloc_out(T, denoised)
         tv = None
         if ticks_valid is not None:
@@ -466,19 +516,19 @@ class Engine:
 
     def input_slot(self):
         """The engine's pinned input slot for the next submit, as a
-        [max_ticks][streams][channels][480] float32 view (fill it in place
+        [max_ticks][streams][channels][frame_in] float32 view (fill it in place
         and pass it to submit: no host copy)."""
         p = lib().fvad_engine_input_slot(self.h)
         if not p:
             raise FvadError("fvad_engine_input_slot: %s" % last_error())
-        n = self.max_ticks * self.B * self.C * FRAME
+        n = self.max_ticks * self.B * self.C * self.frame_in
         arr = np.ctypeslib.as_array(C.cast(p, F32P), shape=(n,))
-        return arr.reshape(self.max_ticks, self.B, self.C, FRAME)
+        return arr.reshape(self.max_ticks, self.B, self.C, self.frame_in)
 
     def submit(self, pcm, ticks_valid=None):
         """Asynchronous push (fvad_engine_submit): returns once queued."""
         pcm = np.ascontiguousarray(pcm, np.float32)
-        assert pcm.shape[1:] == (self.B, self.C, FRAME), pcm.shape
+        assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
         tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
         self._sub_keep = tv
         _check(lib().fvad_engine_submit(self.h, fptr(pcm), pcm.shape[0],
@@ -486,19 +536,19 @@ class Engine:
 
     def input_slot_i16(self):
         """The pinned 16-bit input slot for the next submit_i16, as a
-        [max_ticks][streams][channels][480] int16 view."""
+        [max_ticks][streams][channels][frame_in] int16 view."""
         p = lib().fvad_engine_input_slot_i16(self.h)
         if not p:
             raise FvadError("fvad_engine_input_slot_i16: %s" % last_error())
-        n = self.max_ticks * self.B * self.C * FRAME
+        n = self.max_ticks * self.B * self.C * self.frame_in
         arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(n,))
-        return arr.reshape(self.max_ticks, self.B, self.C, FRAME)
+        return arr.reshape(self.max_ticks, self.B, self.C, self.frame_in)
 
     def submit_i16(self, pcm, ticks_valid=None, last_tick_samples=None):
         """Asynchronous push of 16-bit samples k (fvad_engine_submit_i16): the
         same outputs as submit() of k / 32768.0f, half the PCIe bytes."""
         pcm = np.ascontiguousarray(pcm, np.int16)
-        assert pcm.shape[1:] == (self.B, self.C, FRAME), pcm.shape
+        assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
         tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
         lt = np.ascontiguousarray(last_tick_samples, np.int32) if last_tick_samples is not None else None
         self._sub_keep = (tv, lt)
@@ -738,6 +788,19 @@ class Engine:
         n = C.c_int()
         _check(lib().fvad_engine_output_log_read(self.h, push, C.byref(s), C.byref(n)), "fvad_engine_output_log_read")
         return {k: v[: n.value] for k, v in o.items()}
+
+    def fetch_input(self, n_ticks):
+        """fvad_engine_fetch_input: the 48 kHz device input of the last push of a
+        resampling engine, [n_ticks][streams][channels][480] (a sync point)."""
+        out = np.zeros((n_ticks, self.B, self.C, FRAME), np.float32)
+        _check(lib().fvad_engine_fetch_input(self.h, n_ticks, fptr(out)), "fvad_engine_fetch_input")
+        return out
+
+    def resample_times(self):
+        """(ms average of a push's resample launches, pushes measured); a sync point."""
+        ms, n = C.c_double(), C.c_int()
+        _check(lib().fvad_engine_resample_times(self.h, C.byref(ms), C.byref(n)), "fvad_engine_resample_times")
+        return ms.value, n.value
 
     def fetch(self, n_ticks, denoised=False):
         o, s = self._alloc_out(n_ticks, denoised)

@@ -119,6 +119,10 @@ typedef struct {
                          * the window ratio is preAnalyzeSegment's over the frame, window vad -1 */
   /* ABI note (r5): the trailing `unsigned cu_mask[8]` of earlier builds was removed; a binding
    * compiled against them must drop it (fvad_engine_config_default fills every field) */
+  int input_rate;       /* the rate of the pushed samples: 0 or 48000 (default 0) for 48 kHz input, or 8000,
+                         * 16000, 24000, 32000, 44100, 96000 for an engine that resamples every push to
+                         * 48 kHz on the device (section 2b below); FVAD_ERATE otherwise.  sample_rate, the
+                         * pipeline's rate, stays 48000 */
 } fvad_engine_config;
 
 /* staged: time-parallel frame kernels + a thin per-stream recurrence kernel;
@@ -225,7 +229,10 @@ typedef struct {
                            *     n_bands, the band ranges, n_machines and every machine config field */
   uint64_t model_hash;    /*  64 FNV-1a 64 of fvad_model_blob's bytes */
   uint32_t sample_rate;   /*  72 */
-  uint32_t reserved[13];  /*  76 zero */
+  uint32_t reserved[13];  /*  76 [0]: the saving engine's input_rate when it resamples (its records then end
+                           *     with the resampler's tails, per channel (taps_per_phase + 2) & ~3 words, and
+                           *     config_hash covers the rate), 0 otherwise; a blob restores only into an
+                           *     engine of the same input_rate.  [1..12]: zero */
 } fvad_stream_blob_header;
 int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams, int n);
 /* bytes a save of n streams needs (0 for a NULL engine or n < 0) */
@@ -333,6 +340,69 @@ const char *fvad_engine_kernel_name(const fvad_engine *e, int i);
 int fvad_engine_clear_times(fvad_engine *e);
 /* copy outputs of the last resident run to host */
 int fvad_engine_fetch(fvad_engine *e, int n_ticks, fvad_outputs *out);
+
+/* ------------------------------------------------------------------ */
+/* 2b. Input resampling (fvad_engine_config.input_rate)                 */
+/* ------------------------------------------------------------------ */
+/* An engine created with input_rate R in {8000, 16000, 24000, 32000, 44100,
+ * 96000} takes its pushes at R and resamples them to 48 kHz on the device
+ * (k_resample, the first kernel of the push) in front of the unchanged
+ * pipeline.  A tick stays 10 ms: frame_in = R / 100 samples per channel in,
+ * 480 out.  Every input shape of section 2 becomes
+ * [ticks][streams][channels][frame_in] -- fvad_engine_push[_ex],
+ * fvad_engine_submit[_ex], fvad_engine_submit_i16 and both input slots;
+ * the outputs keep their shapes (denoised is the 48 kHz signal).
+ *
+ * The resampler, to the bit: g = gcd(48000, R), L = 48000 / g, M = R / g,
+ * K = 48 max(1, ceil(M / L)) taps per phase; the prototype of N = L K taps at
+ * the rate Fp = L R is a Kaiser-windowed sinc, designed in f64: A = 80,
+ * beta = 0.1102 (A - 8.7), df = (A - 8) / (2.285 (N - 1)) Fp / (2 pi),
+ * f_stop = min(R, 48000) / 2, fc = f_stop - df / 2,
+ * proto[j] = sinc(2 fc / Fp (j - (N - 1) / 2)) I0(beta sqrt(1 - (2 j / (N - 1) - 1)^2)) / I0(beta),
+ * scaled to sum L; taps[p][k] = (float)proto[k L + p].  Output r (0..479) of
+ * tick t: i = floor(r M / L), p = r M mod L, acc = 0.0f, then for k = 0 .. K - 1
+ * acc = acc + taps[p][k] * x[t frame_in + i - k], product and sum each rounded
+ * to f32, nothing fused.  x before a stream's first sample is 0; across pushes
+ * it continues from the stream's last K - 1 input samples (kept on the device;
+ * reset, saved and restored with the stream).  16-bit input k is
+ * (float)k / 32768 first.  Only a stream's ticks_valid ticks are consumed.
+ *
+ * Every sample index the engine reports -- segments, events, clips -- counts
+ * 48 kHz samples of the resampled signal.  The position in the source is
+ * index * R / 48000 - delay * R / 48000 source samples, delay =
+ * (N - 1) / (2 M) in 48 kHz samples (fvad_resample_info).
+ *
+ * Not available on a resampling engine (FVAD_EINVAL, the engine unchanged): a
+ * partial last tick (last_tick_samples other than frame_in),
+ * fvad_engine_load_synthetic[_ex] and fvad_engine_run_resident (the generator
+ * is 48 kHz).  The rnnoise compat path, fvad_pipeline_*, fvad_multi_*, the
+ * simulator and fvad_sweep_* stay 48 kHz only (FVAD_ERATE). */
+typedef struct {
+  int input_rate;
+  int L, M;            /* 48000 / g and input_rate / g */
+  int taps_per_phase;  /* K */
+  int frame_in;        /* input samples per tick and channel */
+  double delay;        /* the filter's group delay in 48 kHz samples, (L K - 1) / (2 M) */
+} fvad_resample_desc;
+/* host only (no GPU).  FVAD_ERATE for a rate off the list (0 and 48000 too) */
+int fvad_resample_info(int input_rate, fvad_resample_desc *out);
+/* the [L][K] tap table; copies min(count, cap) floats (out may be NULL) and
+ * returns the count, 0 for a rate off the list */
+size_t fvad_resample_taps(int input_rate, float *out, size_t cap);
+/* One channel on the host, the arithmetic above (the kernel's mirror): in is
+ * n_ticks * frame_in samples, out n_ticks * 480.  tail: the K - 1 samples
+ * before in[0], read and replaced by the last K - 1 of this call's input
+ * (carry it to continue a stream); NULL: zeros, nothing kept. */
+int fvad_resample_host(int input_rate, const float *in, size_t n_ticks, float *tail, float *out);
+/* input samples per tick and channel: frame_in, 480 on a plain engine */
+int fvad_engine_input_frame(const fvad_engine *e);
+/* The 48 kHz device input of the last push, [ticks][streams][channels][480]:
+ * what k_resample wrote (zeros in the ticks past a stream's ticks_valid).  A
+ * sync point.  Resampling engines only (FVAD_EINVAL otherwise). */
+int fvad_engine_fetch_input(fvad_engine *e, int n_ticks, float *pcm48);
+/* average event time (ms) of a push's resample launches (k_resample and the
+ * tail update behind it) and the pushes measured; a sync point */
+int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs);
 
 /* ------------------------------------------------------------------ */
 /* 3. Host mirror of the reference API (C++ above this ABI)             */
