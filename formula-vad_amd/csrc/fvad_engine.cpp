@@ -60,6 +60,9 @@ extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams,
   c->want_denoised = 0;
   c->use_denoiser = 1;
   c->input_rate = 0;
+  c->want_spectrum = 0;
+  c->spec_lo = 0;
+  c->spec_hi = 1024;
 }
 
 namespace {
@@ -273,6 +276,11 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
     return fail(FVAD_EINVAL, "reported bins must span <= 256");
   if (c.mode != FVAD_MODE_STAGED && c.mode != FVAD_MODE_FUSED && !fp16_mode(c.mode) && c.mode != FVAD_MODE_F32_FAST)
     return fail(FVAD_EINVAL, "unknown engine mode");
+  if (c.want_spectrum) {
+    if (c.mode == FVAD_MODE_FUSED) return fail(FVAD_EINVAL, "want_spectrum runs on the staged engines (k_frame has no tap)");
+    if (c.spec_lo < 0 || c.spec_hi < c.spec_lo || c.spec_hi > c.fft_size / 2)
+      return fail(FVAD_EINVAL, "invalid spectrum range: 0 <= spec_lo <= spec_hi <= fft_size / 2 required");
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FVAD_EDEVICE, "no HIP device available");
   if (c.device < 0 || c.device >= ndev) return fail(FVAD_EDEVICE, "device ordinal out of range");
@@ -296,6 +304,12 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
     e->kernels = fvad::staged_kernels({c.mode == FVAD_MODE_F32_FAST && c.use_denoiser, fp16_mode(c.mode),
                                        c.mode == FVAD_MODE_FP16_FUSED, olafb});
     e->n_kernels = e->kernels.n;
+    if (c.want_spectrum && c.fft_size == 2048)  // the tap twins' names in the FFT-B slot (fvad_wave.hip)
+      for (int i = 0; i < e->kernels.n; i++) {
+        fvad::StagedKernel &k = e->kernels.k[i];
+        if (k.stage == fvad::kStageOla && olafb) k.name = "k_olafb_spec";
+        if (k.stage == fvad::kStageFftB) k.name = "k_fftbw_spec";
+      }
   }
   e->n_events = c.mode != FVAD_MODE_FUSED ? fvad::kStagedEvents : 3;
   e->last_event = c.mode != FVAD_MODE_FUSED ? fvad::kStagedLast : 2;
@@ -392,6 +406,10 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
           1, std::min<long long>({units, 2LL * e->grid_frames, (1LL << 30) / per}));
       if ((rc = make_dev(e->d_fbwork, (size_t)e->fb_work_blocks * e->fb_work_stride))) return bail(rc);
     }
+  }
+  if (c.want_spectrum) {
+    e->n_spec = c.spec_hi - c.spec_lo + 1;
+    if ((rc = make_dev(e->d_spec, T * B * e->wpt * C * (size_t)e->n_spec))) return bail(rc);
   }
   if (resample) {
     e->rs.reset(new Resample());
@@ -557,6 +575,9 @@ fvad::StagedArgs staged_fixed(const fvad_engine *e) {
   a.raw_s16 = e->raw_s16;
   a.vadm = e->vadm;
   a.stamps = e->d_stamps.get();
+  a.spec = e->d_spec.get();
+  a.spec_lo = c.spec_lo;
+  a.spec_hi = c.spec_hi;
   return a;
 }
 
@@ -588,6 +609,12 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
   a.out_win_vad = e->d_wvad;
   a.out_band = e->d_band;
   a.out_win_flag = e->d_wflag;
+  // window spectra: the push's slots read 0 wherever FFT B writes no window
+  // (behind the previous push's FFT B on the engine stream, ahead of this one's)
+  if (e->d_spec)
+    HIP_TRY(hipMemsetAsync(e->d_spec.get(), 0,
+                           sizeof(float) * (size_t)n_ticks * c.n_streams * e->wpt * c.n_channels * e->n_spec,
+                           e->stream.get()));
   if (c.use_denoiser) {
     HIP_TRY(fvad::launch_prep(a, e->pstream, timed ? e->ev : nullptr));
     // clip capture: the push's input into the history ring, by the stream that
@@ -664,6 +691,7 @@ int fvad::eng::launch(fvad_engine *e, int n_ticks, bool use_ticks, bool timed, b
   const int rc = e->cfg.mode == FVAD_MODE_FUSED ? run_fused(e, n_ticks, use_ticks, timed)
                                                  : run_staged(e, n_ticks, use_ticks, use_tail, timed);
   if (!rc && timed) e->slot_pending[e->ev_slot] = true;
+  if (!rc) e->last_ticks = n_ticks;
   return rc;
 }
 
@@ -919,6 +947,27 @@ extern "C" int fvad_engine_fetch(fvad_engine *e, int n_ticks, fvad_outputs *out)
   if (n_ticks < 1 || n_ticks > e->cfg.max_ticks) return fail(FVAD_EINVAL, "n_ticks out of range");
   HIP_TRY(hipSetDevice(e->cfg.device));
   return fetch(e, n_ticks, out);
+}
+
+extern "C" int fvad_engine_spectrum_bins(const fvad_engine *e, int *lo, int *hi) {
+  if (!e || !e->d_spec) return 0;
+  if (lo) *lo = e->cfg.spec_lo;
+  if (hi) *hi = e->cfg.spec_hi;
+  return e->n_spec;
+}
+
+extern "C" int fvad_engine_fetch_spectrum(fvad_engine *e, int n_ticks, float *out) {
+  if (!e || !out) return fail(FVAD_EINVAL, "null argument");
+  if (!e->d_spec) return fail(FVAD_EINVAL, "engine created without want_spectrum");
+  for (const fvad_engine::Slot &sl : e->slots)
+    if (sl.pending) return fail(FVAD_EINVAL, "a submitted push is uncollected: the spectra are the last launched push's");
+  if (n_ticks < 1 || n_ticks > e->last_ticks)
+    return fail(FVAD_EINVAL, "n_ticks out of range [1, the last push's ticks]");
+  if (const int rc = fvad_engine_sync(e)) return rc;
+  const fvad_engine_config &c = e->cfg;
+  HIP_TRY(hipMemcpy(out, e->d_spec.get(), sizeof(float) * (size_t)n_ticks * c.n_streams * e->wpt * c.n_channels * e->n_spec,
+                    hipMemcpyDeviceToHost));
+  return FVAD_OK;
 }
 
 extern "C" int fvad_engine_windows_per_tick(const fvad_engine *e) { return e ? e->wpt : FVAD_EINVAL; }

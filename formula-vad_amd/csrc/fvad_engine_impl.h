@@ -293,6 +293,12 @@ struct fvad_engine {
   fvad::dev_ptr<float2> d_fbwork;
   int fb_work_blocks = 0;
   long long fb_work_stride = 0;
+  // Window spectra (fvad_engine_config.want_spectrum; DESIGN.md section 7,
+  // "Window spectra and band sweeps"): the last launched push's,
+  // [max_ticks][streams][wpt][channels][n_spec]; null without the tap.
+  // last_ticks: that push's ticks (what fvad_engine_fetch_spectrum may read)
+  fvad::dev_ptr<float> d_spec;
+  int n_spec = 0, last_ticks = 0;
   int resident_ticks = 0;
   int n_kernels = 0;
   fvad::StagedKernels kernels{};  // not fused: the kernels of a push and their timing events (n_kernels of them)

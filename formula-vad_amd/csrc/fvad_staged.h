@@ -220,6 +220,11 @@ struct StagedArgs {
   VadmArgs vadm;
   unsigned *work;          // [kWorkCounters] dynamic group counters of the persistent kernels
   unsigned long long *stamps;  // diagnostic build only (FVAD_STAMPS): per-phase cycles of k_rnn3
+  // window spectra (fvad_engine_config.want_spectrum): null, or [t][s][wpt][c][spec_hi - spec_lo + 1], the
+  // magnitudes of a completed window's bins spec_lo..spec_hi, written by the tap variants of the FFT-B
+  // kernels (last, so every other field keeps its offset)
+  float *spec;
+  int spec_lo, spec_hi;
 };
 
 // true when launch_staged runs k_olafb in place of k_ola, k_winmeta, k_fftbw

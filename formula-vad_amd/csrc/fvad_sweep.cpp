@@ -5,17 +5,25 @@
 // and the scores (fvad_sweep_score: the host evaluator, fvad_eval.cpp;
 // fvad_sweep_run_score: the shared core, fvad_eval_core.h).  Everything but
 // fvad_sweep_run and fvad_sweep_run_score on a device sweep is host code.
+//
+// A spectral sweep (fvad_sweep_create_spectral) records magnitude spectra in
+// the band sums' place: Windows::band then holds [window][channel][n_spec],
+// a run lists its configs' distinct bands, and each chunk's band minima come
+// from k_sweep_bandmin (the host path: fvad_bandsum_core.h) instead of
+// k_sweep_min; the machines run unchanged with n_bands = the chunk's bands.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <string>
 #include <thread>
 #include <utility>
 #include <vector>
 
 #include "../../include/fvad.h"
+#include "fvad_bandsum_core.h"
 #include "fvad_eval_core.h"
 #include "fvad_hip_own.h"
 #include "fvad_internal.h"
@@ -33,7 +41,7 @@ using fvad::set_error;
 namespace {
 constexpr size_t kSweepBudget = (size_t)4 << 30;  // device bytes of one chunk's machines
 
-struct Windows {  // one stream's recorded sequence
+struct Windows {  // one stream's recorded sequence (band: a spectral sweep's magnitudes)
   std::vector<float> band, vad, vr;
   size_t n() const { return vr.size(); }
 };
@@ -106,10 +114,39 @@ struct Chunk {
            lanes() * seg_cap * sizeof(fvad::VadmSeg) + n_cfgs() * sizeof(fvad::VadmConst);
   }
 };
+
+// A spectral run's bands: the distinct (lo, hi) of its configs in order of
+// first appearance, and each config's index among them.
+struct Bands {
+  std::vector<int2> list;
+  std::vector<int> of;  // [config]
+  std::map<std::pair<int, int>, int> index;
+};
+// The distinct bands of the configs [c0, c0 + n) in order of first appearance
+// (local), and for each band of the run its slot among them or -1 (slot_of)
+struct ChunkBands {
+  std::vector<int2> local;
+  std::vector<int> slot_of;
+  explicit ChunkBands(const Bands &b) : slot_of(b.list.size(), -1) {}
+  void add(const Bands &b, size_t m) {
+    int &sl = slot_of[(size_t)b.of[m]];
+    if (sl < 0) {
+      sl = (int)local.size();
+      local.push_back(b.list[(size_t)b.of[m]]);
+    }
+  }
+  bool has(const Bands &b, size_t m) const { return slot_of[(size_t)b.of[m]] >= 0; }
+};
 }  // namespace
 
 struct fvad_sweep {
   fvad_sweep_config cfg{};
+  // spectral sweep: the windows hold the magnitudes of the bins spec_lo..spec_hi
+  bool spectral = false;
+  int spec_lo = 0, spec_hi = 0;
+  int n_spec() const { return spec_hi - spec_lo + 1; }
+  // floats of a recorded window's row in Windows::band
+  size_t per() const { return (size_t)cfg.n_channels * (spectral ? (size_t)n_spec() : (size_t)cfg.n_bands); }
   std::vector<Windows> win;
   bool dirty = true;  // the device copy of the windows is stale
   size_t n_cfgs = 0;
@@ -128,6 +165,10 @@ struct fvad_sweep {
   DevBuf<float> d_band, d_wmin, d_wvad, d_wvr, d_lt, d_sbuf, d_rbuf;
   DevBuf<long long> d_off;
   DevBuf<int> d_nwin;
+  DevBuf<int2> d_bands;  // spectral: the chunk's distinct bands
+  // k_sweep_bandmin's event time over the last device run's chunks (fvad_sweep_bandmin_ms)
+  fvad::event_ptr ev_bandmin[2];
+  double bandmin_ms = 0;
   DevBuf<fvad::VadmConst> d_K;
   DevBuf<fvad::VadmState> d_st;
   DevBuf<fvad::VadmSeg> d_seg;
@@ -158,14 +199,28 @@ int check_config(const fvad_sweep_config &c) {
 
 // every config's constants, initial state and band slot; FVAD_EINVAL naming
 // the first config whose speech band is none of the sweep's
-int prepare(const fvad_sweep_config &c, const fvad_vadm_config *cfgs, size_t n, std::vector<fvad::VadmConst> *K,
-            std::vector<fvad::VadmState> *s0) {
+// (sw: null for fvad_sweep_bytes, a plain sweep's).  A spectral sweep accepts
+// every band inside its range: *bands lists the distinct ones, and the slot
+// (the band's index there) is set again for each chunk.
+int prepare(const fvad_sweep_config &c, const fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n,
+            std::vector<fvad::VadmConst> *K, std::vector<fvad::VadmState> *s0, Bands *bands) {
   K->resize(n);
   s0->resize(n);
   for (size_t m = 0; m < n; m++) {
     const fvad::VadmDerived d = fvad::vadm_derive(cfgs[m], c.sample_rate, c.fft_size);
     (*K)[m] = d.K;
     (*s0)[m] = d.s0;
+    if (sw && sw->spectral) {
+      if (d.lo < sw->spec_lo || d.hi > sw->spec_hi || d.hi < d.lo)
+        return set_error(FVAD_EINVAL, "config " + std::to_string(m) + ": its speech band (bins " + std::to_string(d.lo) +
+                                          ".." + std::to_string(d.hi) + ") lies outside the sweep's spectrum range (" +
+                                          std::to_string(sw->spec_lo) + ".." + std::to_string(sw->spec_hi) + ")");
+      const auto at = bands->index.emplace(std::make_pair(d.lo, d.hi), (int)bands->list.size());
+      if (at.second) bands->list.push_back(make_int2(d.lo, d.hi));
+      bands->of.push_back(at.first->second);
+      (*K)[m].slot = at.first->second;
+      continue;
+    }
     (*K)[m].slot = fvad::band_slot(c.band_lo, c.band_hi, c.n_bands, d.lo, d.hi);
     if ((*K)[m].slot < 0)
       return set_error(FVAD_EINVAL, "config " + std::to_string(m) + ": its speech band (bins " + std::to_string(d.lo) +
@@ -202,7 +257,7 @@ int aggregate_configs(size_t B, size_t n, F &&single_of, fvad_aggregate_stats *a
 
 int upload_windows(fvad_sweep *sw) {
   const fvad_sweep_config &c = sw->cfg;
-  const size_t B = (size_t)c.n_streams, per = (size_t)c.n_channels * c.n_bands;
+  const size_t B = (size_t)c.n_streams, per = sw->per();
   std::vector<long long> off(B);
   std::vector<int> nwin(B);
   size_t total = 0;
@@ -211,38 +266,51 @@ int upload_windows(fvad_sweep *sw) {
     nwin[s] = (int)sw->win[s].n();
     total += sw->win[s].n();
   }
-  std::vector<float> band(total * per), vad(total), vr(total);
+  // (a spectral sweep's rows go up stream by stream: no second host copy of the spectra)
+  std::vector<float> band(sw->spectral ? 0 : total * per), vad(total), vr(total);
   for (size_t s = 0; s < B; s++) {
     const Windows &w = sw->win[s];
-    std::copy(w.band.begin(), w.band.end(), band.begin() + (size_t)off[s] * per);
+    if (!sw->spectral) std::copy(w.band.begin(), w.band.end(), band.begin() + (size_t)off[s] * per);
     std::copy(w.vad.begin(), w.vad.end(), vad.begin() + off[s]);
     std::copy(w.vr.begin(), w.vr.end(), vr.begin() + off[s]);
   }
   int rc;
-  if ((rc = sw->d_band.grow(band.size())) || (rc = sw->d_wvad.grow(total)) || (rc = sw->d_wvr.grow(total)) ||
-      (rc = sw->d_wmin.grow(total * c.n_bands)) || (rc = sw->d_off.grow(B)) || (rc = sw->d_nwin.grow(B)))
+  if ((rc = sw->d_band.grow(total * per)) || (rc = sw->d_wvad.grow(total)) || (rc = sw->d_wvr.grow(total)) ||
+      (rc = sw->d_off.grow(B)) || (rc = sw->d_nwin.grow(B)))
     return rc;
-  HIP_TRY(sw->d_band.put(band.data(), band.size()));
+  if (!sw->spectral && (rc = sw->d_wmin.grow(total * c.n_bands))) return rc;  // (spectral: per chunk, run_device)
+  if (sw->spectral) {
+    for (size_t s = 0; s < B; s++)
+      if (!sw->win[s].band.empty())
+        HIP_TRY(hipMemcpy(sw->d_band.get() + (size_t)off[s] * per, sw->win[s].band.data(),
+                          sw->win[s].band.size() * sizeof(float), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(sw->d_band.put(band.data(), band.size()));
+  }
   HIP_TRY(sw->d_wvad.put(vad.data(), total));
   HIP_TRY(sw->d_wvr.put(vr.data(), total));
   HIP_TRY(sw->d_off.put(off.data(), B));
   HIP_TRY(sw->d_nwin.put(nwin.data(), B));
   sw->n_windows = (long long)total;
-  fvad::SweepArgs a{};
-  a.n_channels = c.n_channels;
-  a.n_bands = c.n_bands;
-  a.n_windows = sw->n_windows;
-  a.band = sw->d_band.get();
-  a.wmin = sw->d_wmin.get();
-  HIP_TRY(fvad::launch_sweep_min(a, sw->stream.get()));
-  HIP_TRY(hipStreamSynchronize(sw->stream.get()));
+  if (!sw->spectral) {
+    fvad::SweepArgs a{};
+    a.n_channels = c.n_channels;
+    a.n_bands = c.n_bands;
+    a.n_windows = sw->n_windows;
+    a.band = sw->d_band.get();
+    a.wmin = sw->d_wmin.get();
+    HIP_TRY(fvad::launch_sweep_min(a, sw->stream.get()));
+    HIP_TRY(hipStreamSynchronize(sw->stream.get()));
+  }
   sw->dirty = false;
   return FVAD_OK;
 }
 
 // sc: null (the segments come back), or the lanes are scored on the device and
 // their statistics and status words come back instead
-int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vector<fvad::VadmState> &s0, Score *sc) {
+// bands: a spectral run's (empty otherwise)
+int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vector<fvad::VadmState> &s0,
+               const Bands &bands, Score *sc) {
   const fvad_sweep_config &c = sw->cfg;
   const size_t B = (size_t)c.n_streams, n = K.size();
   const hipStream_t stream = sw->stream.get();
@@ -262,6 +330,10 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     HIP_TRY(sw->d_lab_off.put_async(sc->off.data(), sc->off.size(), stream));
     HIP_TRY(sw->d_stat.put_async(sc->stat, sc->n_stat, stream));
   }
+  if (sw->spectral)
+    for (fvad::event_ptr &ev : sw->ev_bandmin)
+      if (!ev && (rc = fvad::make_event(ev, true))) return rc;
+  double bandmin_ms = 0;
   std::vector<Lane> lanes(B * n);
   std::vector<fvad::VadmState> st;
   std::vector<fvad_segment> seg;  // (a VadmSeg is an fvad_segment: fvad_machine.h)
@@ -270,13 +342,43 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
   size_t bytes_back = 0;
   for (size_t c0 = 0; c0 < n;) {
     // the chunk: configs [c0, c1), by the test hook or as many as the budget holds (one at least)
+    // (spectral: the chunk's band minima, windows x its distinct bands, count too)
     size_t c1 = c0 + 1;
-    if (sw->chunk)
+    ChunkBands cb(bands);
+    const size_t wmin_per_band = (size_t)sw->n_windows * sizeof(float);
+    if (sw->spectral) cb.add(bands, c0);
+    if (sw->chunk) {
       c1 = std::min(n, c0 + sw->chunk);
-    else
-      while (c1 < n && Chunk(c, K, c0, c1 + 1).bytes() <= kSweepBudget) c1++;
+      if (sw->spectral)
+        for (size_t m = c0 + 1; m < c1; m++) cb.add(bands, m);
+    } else {
+      while (c1 < n) {
+        const size_t D1 = sw->spectral ? cb.local.size() + (cb.has(bands, c1) ? 0 : 1) : 0;
+        if (Chunk(c, K, c0, c1 + 1).bytes() + D1 * wmin_per_band > kSweepBudget) break;
+        if (sw->spectral) cb.add(bands, c1);
+        c1++;
+      }
+    }
     const Chunk ch(c, K, c0, c1);
     const size_t nc = ch.n_cfgs(), nl = ch.lanes();
+    const int D = sw->spectral ? (int)cb.local.size() : c.n_bands;
+    if (sw->spectral) {
+      for (size_t m = c0; m < c1; m++) K[m].slot = cb.slot_of[(size_t)bands.of[m]];
+      if ((rc = sw->d_bands.grow((size_t)D)) || (rc = sw->d_wmin.grow((size_t)sw->n_windows * D))) return rc;
+      HIP_TRY(sw->d_bands.put_async(cb.local.data(), (size_t)D, stream));
+      fvad::BandMinArgs b{};
+      b.n_channels = c.n_channels;
+      b.n_spec = sw->n_spec();
+      b.spec_lo = sw->spec_lo;
+      b.n_bands = D;
+      b.n_windows = sw->n_windows;
+      b.spec = sw->d_band.get();
+      b.bands = sw->d_bands.get();
+      b.wmin = sw->d_wmin.get();
+      HIP_TRY(hipEventRecord(sw->ev_bandmin[0].get(), stream));
+      HIP_TRY(fvad::launch_sweep_bandmin(b, stream));
+      HIP_TRY(hipEventRecord(sw->ev_bandmin[1].get(), stream));
+    }
     if ((rc = sw->d_K.grow(nc)) || (rc = sw->d_st.grow(nl)) || (rc = sw->d_lt.grow(ch.lt)) ||
         (rc = sw->d_sbuf.grow(ch.max_st * nl)) || (rc = sw->d_rbuf.grow(ch.max_r * nl)) ||
         (rc = sw->d_seg.grow(nl * ch.seg_cap)))
@@ -295,7 +397,7 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
     a.n_streams = c.n_streams;
     a.n_cfgs = (int)nc;
     a.n_channels = c.n_channels;
-    a.n_bands = c.n_bands;
+    a.n_bands = D;
     a.seg_cap = c.seg_capacity;
     a.K = sw->d_K.get();
     a.st = sw->d_st.get();
@@ -331,6 +433,11 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
       HIP_TRY(fvad::launch_sweep_score(b, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
+    if (sw->spectral) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, sw->ev_bandmin[0].get(), sw->ev_bandmin[1].get()));
+      bandmin_ms += ms;
+    }
     HIP_TRY(sw->d_st.fetch(st.data(), nl, &bytes_back));
     if (sc) {
       single.resize(nl);
@@ -361,40 +468,64 @@ int run_device(fvad_sweep *sw, std::vector<fvad::VadmConst> &K, const std::vecto
   sw->n_cfgs = n;
   sw->kept = !sc;
   sw->bytes_back = bytes_back;
+  sw->bandmin_ms = bandmin_ms;
   return FVAD_OK;
 }
 
 // sc: null (the segments are kept), or each lane is scored by the shared core
 // as k_sweep_score does it and keeps no segments
-int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fvad::VadmConst> &K, Score *sc) {
+// A spectral sweep (bands: the run's) works by (stream, band): the band's sums
+// over the stream's windows once (fvad_bandsum_core.h: k_sweep_bandmin's
+// chains), then every config of that band over them.
+int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fvad::VadmConst> &K, const Bands &bands,
+             Score *sc) {
   const fvad_sweep_config &c = sw->cfg;
   const size_t B = (size_t)c.n_streams, n = K.size(), nl = B * n;
   std::vector<Lane> lanes(nl);
-  auto work = [&](size_t t, size_t nt) {
-    for (size_t l = t; l < nl; l += nt) {
-      const size_t s = l / n, m = l % n;
-      const Windows &w = sw->win[s];
-      fvad::host_vadm_lane(cfgs[m], c.sample_rate, c.fft_size, c.n_channels, c.n_bands, K[m].slot, w.n(),
-                           w.band.data(), w.vad.data(), w.vr.data(), &lanes[l].snap, &lanes[l].segs);
-      if (sc) {
-        const std::vector<fvad_segment> &g = lanes[l].segs;
-        if (g.size() > (size_t)c.seg_capacity)
-          sc->status[l] = fvad::kEvalOverCapacity;
-        else
-          sc->status[l] = fvad::eval_lane(
-              [&](size_t i, float *from, float *to) {
-                *from = (float)g[i].sample_from / 48000.0f;
-                *to = (float)g[i].sample_to / 48000.0f;
-              },
-              g.size(), sc->lab.data() + 2 * sc->off[s], (size_t)(sc->off[s + 1] - sc->off[s]),
-              sc->stat[sc->n_stat == 1 ? 0 : m], &sc->single[l]);
-        lanes[l].segs = {};
-      } else if (lanes[l].segs.size() > (size_t)c.seg_capacity) {
-        lanes[l].segs.resize((size_t)c.seg_capacity);
-      }
+  // one lane over `band` [window][channel][n_bands], reading slot `slot`
+  auto lane = [&](size_t l, const float *band, int n_bands, int slot) {
+    const size_t s = l / n, m = l % n;
+    const Windows &w = sw->win[s];
+    fvad::host_vadm_lane(cfgs[m], c.sample_rate, c.fft_size, c.n_channels, n_bands, slot, w.n(), band, w.vad.data(),
+                         w.vr.data(), &lanes[l].snap, &lanes[l].segs);
+    if (sc) {
+      const std::vector<fvad_segment> &g = lanes[l].segs;
+      if (g.size() > (size_t)c.seg_capacity)
+        sc->status[l] = fvad::kEvalOverCapacity;
+      else
+        sc->status[l] = fvad::eval_lane(
+            [&](size_t i, float *from, float *to) {
+              *from = (float)g[i].sample_from / 48000.0f;
+              *to = (float)g[i].sample_to / 48000.0f;
+            },
+            g.size(), sc->lab.data() + 2 * sc->off[s], (size_t)(sc->off[s + 1] - sc->off[s]),
+            sc->stat[sc->n_stat == 1 ? 0 : m], &sc->single[l]);
+      lanes[l].segs = {};
+    } else if (lanes[l].segs.size() > (size_t)c.seg_capacity) {
+      lanes[l].segs.resize((size_t)c.seg_capacity);
     }
   };
-  const size_t nt = std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)std::thread::hardware_concurrency(), nl}));
+  std::vector<std::vector<size_t>> cfgs_of(bands.list.size());  // spectral: the configs of each band
+  for (size_t m = 0; m < bands.of.size(); m++) cfgs_of[(size_t)bands.of[m]].push_back(m);
+  const size_t units = sw->spectral ? B * bands.list.size() : nl;
+  auto work = [&](size_t t, size_t nt) {
+    std::vector<float> sums;
+    for (size_t u = t; u < units; u += nt) {
+      if (!sw->spectral) {
+        lane(u, sw->win[u / n].band.data(), c.n_bands, K[u % n].slot);
+        continue;
+      }
+      const size_t s = u / bands.list.size(), g = u % bands.list.size(), C = (size_t)c.n_channels, per = sw->per();
+      const Windows &w = sw->win[s];
+      sums.resize(w.n() * C);
+      for (size_t i = 0; i < w.n() * C; i++)
+        sums[i] = fvad::band_chain(w.band.data() + (i / C) * per + (i % C) * (size_t)sw->n_spec(), sw->spec_lo,
+                                   bands.list[g].x, bands.list[g].y);
+      for (const size_t m : cfgs_of[g]) lane(s * n + m, sums.data(), 1, 0);
+    }
+  };
+  const size_t nt =
+      std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)std::thread::hardware_concurrency(), units}));
   std::vector<std::thread> th;
   for (size_t t = 1; t < nt; t++) th.emplace_back(work, t, nt);
   work(0, nt);
@@ -404,6 +535,7 @@ int run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, const std::vector<fva
   sw->have_counts = false;
   sw->kept = !sc;
   sw->bytes_back = 0;
+  sw->bandmin_ms = 0;
   return FVAD_OK;
 }
 
@@ -413,9 +545,10 @@ int run(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs, bool force_
   if (const int rc = check_run(sw, cfgs, n_cfgs)) return rc;
   std::vector<fvad::VadmConst> K;
   std::vector<fvad::VadmState> s0;
-  if (const int rc = prepare(sw->cfg, cfgs, n_cfgs, &K, &s0)) return rc;
-  if (force_host || sw->cfg.device == -1) return run_host(sw, cfgs, K, sc);
-  return run_device(sw, K, s0, sc);
+  Bands bands;
+  if (const int rc = prepare(sw->cfg, sw, cfgs, n_cfgs, &K, &s0, &bands)) return rc;
+  if (force_host || sw->cfg.device == -1) return run_host(sw, cfgs, K, bands, sc);
+  return run_device(sw, K, s0, bands, sc);
 }
 
 const Lane *lane_of(const fvad_sweep *sw, int stream, size_t cfg) {
@@ -424,8 +557,8 @@ const Lane *lane_of(const fvad_sweep *sw, int stream, size_t cfg) {
 }
 }  // namespace
 
-extern "C" int fvad_sweep_create(const fvad_sweep_config *cfg, fvad_sweep **out) {
-  if (!cfg || !out) return set_error(FVAD_EINVAL, "null argument");
+namespace {
+int create(const fvad_sweep_config *cfg, fvad_sweep **out) {
   if (const int rc = check_config(*cfg)) return rc;
   fvad::stream_ptr stream;
   if (cfg->device != -1) {
@@ -445,6 +578,27 @@ extern "C" int fvad_sweep_create(const fvad_sweep_config *cfg, fvad_sweep **out)
   *out = sw;
   return FVAD_OK;
 }
+}  // namespace
+
+extern "C" int fvad_sweep_create(const fvad_sweep_config *cfg, fvad_sweep **out) {
+  if (!cfg || !out) return set_error(FVAD_EINVAL, "null argument");
+  return create(cfg, out);
+}
+
+extern "C" int fvad_sweep_create_spectral(const fvad_sweep_config *cfg, int spec_lo, int spec_hi, fvad_sweep **out) {
+  if (!cfg || !out) return set_error(FVAD_EINVAL, "null argument");
+  fvad_sweep_config c = *cfg;  // n_bands and the bands are ignored: one band, the range, for check_config
+  c.n_bands = 1;
+  c.band_lo[0] = spec_lo;
+  c.band_hi[0] = spec_hi;
+  if (c.fft_size >= 2 && (spec_lo < 0 || spec_hi < spec_lo || spec_hi > c.fft_size / 2))
+    return set_error(FVAD_EINVAL, "invalid spectrum range: 0 <= spec_lo <= spec_hi <= fft_size / 2 required");
+  if (const int rc = create(&c, out)) return rc;
+  (*out)->spectral = true;
+  (*out)->spec_lo = spec_lo;
+  (*out)->spec_hi = spec_hi;
+  return FVAD_OK;
+}
 
 extern "C" void fvad_sweep_destroy(fvad_sweep *sw) {
   if (!sw) return;
@@ -452,14 +606,23 @@ extern "C" void fvad_sweep_destroy(fvad_sweep *sw) {
   delete sw;
 }
 
-extern "C" int fvad_sweep_set_windows(fvad_sweep *sw, int stream, size_t n_windows, const float *band,
-                                      const float *vad, const float *vol_ratio) {
-  if (!sw) return set_error(FVAD_EINVAL, "null sweep");
+namespace {
+// the setters' kinds: band sums go to a plain sweep, spectra to a spectral one
+int check_kind(const fvad_sweep *sw, bool spectral) {
+  if (sw->spectral == spectral) return FVAD_OK;
+  return set_error(FVAD_EINVAL, spectral ? "not a spectral sweep (fvad_sweep_create_spectral): it records band sums"
+                                         : "a spectral sweep records spectra (fvad_sweep_set_spectra, _append_spectra)");
+}
+
+// fvad_sweep_set_windows / _set_spectra: band holds sw->per() floats per window
+int set_rows(fvad_sweep *sw, int stream, size_t n_windows, const float *band, const float *vad,
+             const float *vol_ratio) {
   if (stream < 0 || stream >= sw->cfg.n_streams) return set_error(FVAD_EINVAL, "stream index out of range");
-  if (n_windows > 0 && (!band || !vol_ratio)) return set_error(FVAD_EINVAL, "null band or vol_ratio");
+  if (n_windows > 0 && (!band || !vol_ratio))
+    return set_error(FVAD_EINVAL, sw->spectral ? "null spectrum or vol_ratio" : "null band or vol_ratio");
   if (n_windows > (size_t)0x7fffffff) return set_error(FVAD_EINVAL, "n_windows above 2^31 - 1");
   Windows &w = sw->win[(size_t)stream];
-  const size_t per = (size_t)sw->cfg.n_channels * sw->cfg.n_bands;
+  const size_t per = sw->per();
   w.band.assign(band, band + n_windows * per);
   w.vr.assign(vol_ratio, vol_ratio + n_windows);
   if (vad && sw->cfg.use_denoiser)
@@ -470,15 +633,11 @@ extern "C" int fvad_sweep_set_windows(fvad_sweep *sw, int stream, size_t n_windo
   return FVAD_OK;
 }
 
-extern "C" int fvad_sweep_append_outputs(fvad_sweep *sw, const fvad_outputs *out, int n_ticks,
-                                         const int32_t *ticks_valid) {
-  if (!sw || !out) return set_error(FVAD_EINVAL, "null argument");
-  if (!out->win_flag || !out->win_ratio || !out->win_vad || !out->band)
-    return set_error(FVAD_EINVAL, "win_flag, win_ratio, win_vad and band are required");
+// fvad_sweep_append_outputs / _append_spectra: rows [tick][stream][slot] of sw->per() floats
+int append_rows(fvad_sweep *sw, const fvad_outputs *out, const float *rows, int n_ticks, const int32_t *ticks_valid) {
   if (n_ticks < 0) return set_error(FVAD_EINVAL, "n_ticks < 0");
   const fvad_sweep_config &c = sw->cfg;
-  const size_t B = (size_t)c.n_streams, W = (size_t)fvad::windows_per_tick(c.fft_size),
-               per = (size_t)c.n_channels * c.n_bands;
+  const size_t B = (size_t)c.n_streams, W = (size_t)fvad::windows_per_tick(c.fft_size), per = sw->per();
   // validate everything first: a bad value leaves the sweep as it was
   for (size_t s = 0; s < B; s++) {
     if (ticks_valid && (ticks_valid[s] < 0 || ticks_valid[s] > n_ticks))
@@ -498,13 +657,46 @@ extern "C" int fvad_sweep_append_outputs(fvad_sweep *sw, const fvad_outputs *out
     for (int t = 0; t < nt; t++)
       for (int32_t k = 0, f = out->win_flag[(size_t)t * B + s]; k < f; k++) {
         const size_t o = ((size_t)t * B + s) * W + (size_t)k;
-        w.band.insert(w.band.end(), out->band + o * per, out->band + (o + 1) * per);
+        w.band.insert(w.band.end(), rows + o * per, rows + (o + 1) * per);
         w.vad.push_back(c.use_denoiser ? out->win_vad[o] : 0.0f);
         w.vr.push_back(out->win_ratio[o]);
       }
   }
   sw->dirty = true;
   return FVAD_OK;
+}
+}  // namespace
+
+extern "C" int fvad_sweep_set_windows(fvad_sweep *sw, int stream, size_t n_windows, const float *band,
+                                      const float *vad, const float *vol_ratio) {
+  if (!sw) return set_error(FVAD_EINVAL, "null sweep");
+  if (const int rc = check_kind(sw, false)) return rc;
+  return set_rows(sw, stream, n_windows, band, vad, vol_ratio);
+}
+
+extern "C" int fvad_sweep_set_spectra(fvad_sweep *sw, int stream, size_t n_windows, const float *spectrum,
+                                      const float *vad, const float *vol_ratio) {
+  if (!sw) return set_error(FVAD_EINVAL, "null sweep");
+  if (const int rc = check_kind(sw, true)) return rc;
+  return set_rows(sw, stream, n_windows, spectrum, vad, vol_ratio);
+}
+
+extern "C" int fvad_sweep_append_outputs(fvad_sweep *sw, const fvad_outputs *out, int n_ticks,
+                                         const int32_t *ticks_valid) {
+  if (!sw || !out) return set_error(FVAD_EINVAL, "null argument");
+  if (const int rc = check_kind(sw, false)) return rc;
+  if (!out->win_flag || !out->win_ratio || !out->win_vad || !out->band)
+    return set_error(FVAD_EINVAL, "win_flag, win_ratio, win_vad and band are required");
+  return append_rows(sw, out, out->band, n_ticks, ticks_valid);
+}
+
+extern "C" int fvad_sweep_append_spectra(fvad_sweep *sw, const fvad_outputs *out, const float *spectrum, int n_ticks,
+                                         const int32_t *ticks_valid) {
+  if (!sw || !out) return set_error(FVAD_EINVAL, "null argument");
+  if (const int rc = check_kind(sw, true)) return rc;
+  if (!out->win_flag || !out->win_ratio || !out->win_vad || !spectrum)
+    return set_error(FVAD_EINVAL, "win_flag, win_ratio, win_vad and spectrum are required");
+  return append_rows(sw, out, spectrum, n_ticks, ticks_valid);
 }
 
 extern "C" int fvad_sweep_run_host(fvad_sweep *sw, const fvad_vadm_config *cfgs, size_t n_cfgs) {
@@ -575,6 +767,13 @@ extern "C" int fvad_sweep_last_run(const fvad_sweep *sw, size_t *n_cfgs, int *ke
   return FVAD_OK;
 }
 
+extern "C" int fvad_sweep_bandmin_ms(const fvad_sweep *sw, double *ms) {
+  if (!sw || !ms) return set_error(FVAD_EINVAL, "null argument");
+  if (!sw->spectral) return set_error(FVAD_EINVAL, "not a spectral sweep");
+  *ms = sw->bandmin_ms;
+  return FVAD_OK;
+}
+
 extern "C" size_t fvad_sweep_segments(const fvad_sweep *sw, int stream, size_t cfg, fvad_segment *out, size_t cap) {
   const Lane *l = lane_of(sw, stream, cfg);
   if (!l) return 0;
@@ -630,7 +829,8 @@ extern "C" size_t fvad_sweep_bytes(const fvad_sweep_config *cfg, const fvad_vadm
   if (!cfg || !cfgs || n_cfgs < 1 || check_config(*cfg)) return 0;
   std::vector<fvad::VadmConst> K;
   std::vector<fvad::VadmState> s0;
-  if (prepare(*cfg, cfgs, n_cfgs, &K, &s0)) return 0;
+  Bands none;
+  if (prepare(*cfg, nullptr, cfgs, n_cfgs, &K, &s0, &none)) return 0;
   return Chunk(*cfg, K, 0, n_cfgs).bytes();
 }
 

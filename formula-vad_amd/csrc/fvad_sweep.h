@@ -33,6 +33,22 @@ constexpr int kSweepBlock = 64;  // windows per walk: a lane re-decides lazy / n
 hipError_t launch_sweep_min(const SweepArgs &a, hipStream_t stream);
 hipError_t launch_vadm_sweep(const SweepArgs &a, hipStream_t stream);
 
+// k_sweep_bandmin's arguments (spectral sweeps, fvad_sweep_create_spectral):
+// the recorded spectra in, the chunk's wmin out -- what k_sweep_min makes of
+// recorded band sums, for the chunk's D distinct bands.
+struct BandMinArgs {
+  int n_channels, n_spec, spec_lo;  // a window's magnitudes: [channel][n_spec], bin spec_lo first
+  int n_bands;                      // D
+  long long n_windows;              // all streams'
+  const float *spec;                // [window][channel][n_spec]
+  const int2 *bands;                // [D] inclusive bins (lo, hi) inside [spec_lo, spec_lo + n_spec)
+  float *wmin;                      // [window][D]
+};
+// floats of a window k_sweep_bandmin stages in LDS: 8 channels of fft_size
+// 2048's 1 025 bins; a larger window is read from HBM by every thread
+constexpr int kBandMinStage = FVAD_MAX_CHANNELS * 1025;
+hipError_t launch_sweep_bandmin(const BandMinArgs &a, hipStream_t stream);
+
 // k_sweep_score's arguments (fvad_sweep_score.hip): a chunk's lanes as
 // SweepArgs', scored where k_vadm_sweep left them.
 struct ScoreArgs {

@@ -5,6 +5,12 @@
 //                                         sums (from 999, strict <: vadm_stream's
 //                                         reduction, exact in f32), once per
 //                                         (window, band slot) instead of per lane
+//   k_sweep_bandmin  workgroup/window     spectral sweeps: the window's magnitudes
+//                                         (staged in LDS once) into the minimum
+//                                         over channels of every distinct band's
+//                                         sum, a thread per band walking its f32
+//                                         chain in bin order (fvad_bandsum_core.h:
+//                                         FFT B's band sums, k_sweep_min's minimum)
 //   k_vadm_sweep   lane/(stream, config)  the device VADMachine (fvad_vadm_dev.h:
 //                                         the code k_vadm_hbm runs) over the
 //                                         stream's whole sequence
@@ -24,6 +30,9 @@
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
+#include "fvad_bandsum_core.h"
 #include "fvad_sweep.h"
 #include "fvad_vadm_dev.h"
 
@@ -40,6 +49,27 @@ __global__ void __launch_bounds__(256) k_sweep_min(SweepArgs a) {
     if (v < min_v) min_v = v;
   }
   a.wmin[i] = min_v;
+}
+
+// kStage: the window's n_channels * n_spec <= kBandMinStage magnitudes go
+// through LDS (32 800 bytes), read from HBM once, coalesced; otherwise every
+// thread reads its bands' bins from HBM.  wmin's stores run along the bands.
+template <bool kStage>
+__global__ void __launch_bounds__(256) k_sweep_bandmin(BandMinArgs a) {
+  __shared__ float mag[kStage ? kBandMinStage : 1];
+  const int per = a.n_channels * a.n_spec;
+  for (long long w = blockIdx.x; w < a.n_windows; w += gridDim.x) {
+    const float *row = a.spec + (size_t)w * per;
+    if constexpr (kStage) {
+      for (int i = threadIdx.x; i < per; i += 256) mag[i] = row[i];
+      __syncthreads();
+    }
+    for (int d = threadIdx.x; d < a.n_bands; d += 256) {
+      const int2 b = a.bands[d];
+      a.wmin[(size_t)w * a.n_bands + d] = band_min(kStage ? mag : row, a.n_channels, a.n_spec, a.spec_lo, b.x, b.y);
+    }
+    if constexpr (kStage) __syncthreads();  // the next window's magnitudes replace these
+  }
 }
 
 __global__ void __launch_bounds__(64) k_vadm_sweep(SweepArgs a) {
@@ -68,6 +98,16 @@ hipError_t launch_sweep_min(const SweepArgs &a, hipStream_t stream) {
   const long long n = a.n_windows * a.n_bands;
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_sweep_min, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sweep_bandmin(const BandMinArgs &a, hipStream_t stream) {
+  if (a.n_windows <= 0 || a.n_bands <= 0) return hipSuccess;
+  const dim3 grid((unsigned)std::min<long long>(a.n_windows, 1 << 20));
+  if (a.n_channels * (long long)a.n_spec <= kBandMinStage)
+    hipLaunchKernelGGL(k_sweep_bandmin<true>, grid, dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL(k_sweep_bandmin<false>, grid, dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -193,7 +193,37 @@ __device__ __forceinline__ size_t win_out(const StagedArgs &a, int s, int slot) 
   return ((size_t)t * a.n_streams + s) * a.wpt + (slot - t * a.wpt);
 }
 
-template <int NT, bool kLds>
+// kiss_fftr's split for bin k (0..nc) of the nc-point transform in W, and the
+// bin's magnitude
+__device__ __forceinline__ float fftr_mag(const float2 *W, const float2 *__restrict__ sup, int k, int nc, float norm) {
+  float re, imv;
+  if (k == 0) {
+    re = W[0].x + W[0].y;
+    imv = 0;
+  } else if (k == nc) {
+    re = W[0].x - W[0].y;
+    imv = 0;
+  } else {
+    const int kk = (2 * k < nc) ? k : nc - k;
+    const float2 fpk = W[kk];
+    const float2 fpnk = make_float2(W[nc - kk].x, -W[nc - kk].y);
+    const float2 f1k = cadd(fpk, fpnk), f2k = csub(fpk, fpnk);
+    const float2 tw2 = cmul(f2k, sup[kk - 1]);
+    if (2 * k < nc) {
+      re = (f1k.x + tw2.x) * ((float).5);
+      imv = (f1k.y + tw2.y) * ((float).5);
+    } else {
+      re = (f1k.x - tw2.x) * ((float).5);
+      imv = (tw2.y - f1k.y) * ((float).5);
+    }
+  }
+  const float r2 = re * re, i2 = imv * imv;
+  return sqrtf(r2 + i2) * norm;
+}
+
+// kTap (want_spectrum): the magnitudes of the bins a.spec_lo..a.spec_hi also go
+// to the window's row of a.spec, a thread per bin (coalesced stores).
+template <int NT, bool kLds, bool kTap>
 __global__ void __launch_bounds__(NT) k_fftb(StagedArgs a) {
   // W[nc] (+ S[nc] with a radix > 5), then the magnitudes of the reported bins
   extern __shared__ __attribute__((aligned(16))) float2 Wl[];
@@ -225,30 +255,10 @@ __global__ void __launch_bounds__(NT) k_fftb(StagedArgs a) {
       __syncthreads();
       kiss_stages(W, S, P->fac_b, P->nfac_b, nc, twb, tid, NT);
       const int lo = a.bin_lo_all, hi = a.bin_hi_all;
-      for (int k = lo + tid; k <= hi; k += NT) {
-        float re, imv;
-        if (k == 0) {
-          re = W[0].x + W[0].y;
-          imv = 0;
-        } else if (k == nc) {
-          re = W[0].x - W[0].y;
-          imv = 0;
-        } else {
-          const int kk = (2 * k < nc) ? k : nc - k;
-          const float2 fpk = W[kk];
-          const float2 fpnk = make_float2(W[nc - kk].x, -W[nc - kk].y);
-          const float2 f1k = cadd(fpk, fpnk), f2k = csub(fpk, fpnk);
-          const float2 tw2 = cmul(f2k, sup[kk - 1]);
-          if (2 * k < nc) {
-            re = (f1k.x + tw2.x) * ((float).5);
-            imv = (f1k.y + tw2.y) * ((float).5);
-          } else {
-            re = (f1k.x - tw2.x) * ((float).5);
-            imv = (tw2.y - f1k.y) * ((float).5);
-          }
-        }
-        const float r2 = re * re, i2 = imv * imv;
-        mag[k - lo] = sqrtf(r2 + i2) * P->norm_b;
+      for (int k = lo + tid; k <= hi; k += NT) mag[k - lo] = fftr_mag(W, sup, k, nc, P->norm_b);
+      if constexpr (kTap) {
+        float *spec = a.spec + (o * C + c) * (size_t)(a.spec_hi - a.spec_lo + 1);
+        for (int k = a.spec_lo + tid; k <= a.spec_hi; k += NT) spec[k - a.spec_lo] = fftr_mag(W, sup, k, nc, P->norm_b);
       }
       __syncthreads();
       if (tid < a.n_bands) {
@@ -279,12 +289,12 @@ long long fftb_work_stride(int nfft_b, int bin_lo_all, int bin_hi_all, int gener
   return (nc * (generic ? 2 : 1) + (bins + 1) / 2 + 1) & ~1LL;  // float2 units, 16-byte aligned slices
 }
 
-hipError_t launch_fftb(const StagedArgs &a, int n_cu, hipStream_t stream) {
-  if (a.nfft_b == 2048) return launch_wave(kWaveFftB, a, n_cu, stream);
+template <bool kTap>
+static hipError_t launch_fftb_block(const StagedArgs &a, hipStream_t stream) {
   static const bool attr = [] {
     bool ok = true;
-    for (const void *k : {reinterpret_cast<const void *>(&k_fftb<256, true>),
-                          reinterpret_cast<const void *>(&k_fftb<64, true>)})
+    for (const void *k : {reinterpret_cast<const void *>(&k_fftb<256, true, kTap>),
+                          reinterpret_cast<const void *>(&k_fftb<64, true, kTap>)})
       ok &= hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
     return ok;
   }();
@@ -292,7 +302,7 @@ hipError_t launch_fftb(const StagedArgs &a, int n_cu, hipStream_t stream) {
   const long long units = (long long)a.n_streams * a.wmax;
   if (a.fb_work) {
     const unsigned grid = (unsigned)std::min<long long>(units, a.fb_work_blocks);
-    FVAD_KERNEL_TRY((k_fftb<256, false>), dim3(grid), dim3(256), 0, stream, a);
+    FVAD_KERNEL_TRY((k_fftb<256, false, kTap>), dim3(grid), dim3(256), 0, stream, a);
     return hipSuccess;
   }
   const int nc = a.nfft_b / 2;
@@ -300,10 +310,16 @@ hipError_t launch_fftb(const StagedArgs &a, int n_cu, hipStream_t stream) {
                      sizeof(float) * (size_t)(a.bin_hi_all - a.bin_lo_all + 1);
   const unsigned grid = (unsigned)std::min<long long>(units, 1 << 16);
   if (nc <= 64)  // fft_size <= 128: a wave per window
-    FVAD_KERNEL_TRY((k_fftb<64, true>), dim3(grid), dim3(64), lds, stream, a);
+    FVAD_KERNEL_TRY((k_fftb<64, true, kTap>), dim3(grid), dim3(64), lds, stream, a);
   else
-    FVAD_KERNEL_TRY((k_fftb<256, true>), dim3(grid), dim3(256), lds, stream, a);
+    FVAD_KERNEL_TRY((k_fftb<256, true, kTap>), dim3(grid), dim3(256), lds, stream, a);
   return hipSuccess;
+}
+
+hipError_t launch_fftb(const StagedArgs &a, int n_cu, hipStream_t stream) {
+  if (a.nfft_b == 2048) return launch_wave(kWaveFftB, a, n_cu, stream);
+  // want_spectrum (a.spec): the tap instantiations
+  return a.spec ? launch_fftb_block<true>(a, stream) : launch_fftb_block<false>(a, stream);
 }
 
 // ---------------------------------------------------------------------------

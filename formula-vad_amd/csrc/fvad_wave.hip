@@ -485,13 +485,45 @@ __device__ __forceinline__ void fftb_tw_load(FbTw &w, const Plan *__restrict__ P
   w.tw0 = twb[0];
 }
 
+// kiss_fftr's split for bin k (0..1024) of the 1024-point transform held in
+// natural order in R, and the bin's magnitude
+__device__ __forceinline__ float fftb_mag(const float2 *R, const float2 *__restrict__ sup, int k, float norm) {
+  const int nc = 1024;
+  float re, imv;
+  if (k == 0) {
+    re = R[0].x + R[0].y;
+    imv = 0;
+  } else if (k == nc) {
+    re = R[0].x - R[0].y;
+    imv = 0;
+  } else {
+    const int kk = (k < nc / 2) ? k : nc - k;
+    const float2 fpk = R[kk];
+    const float2 fpnk = make_float2(R[nc - kk].x, -R[nc - kk].y);
+    const float2 f1k = cadd(fpk, fpnk), f2k = csub(fpk, fpnk);
+    const float2 tw2 = cmul(f2k, sup[kk - 1]);
+    if (k < nc / 2) {
+      re = (f1k.x + tw2.x) * ((float).5);
+      imv = (f1k.y + tw2.y) * ((float).5);
+    } else {
+      re = (f1k.x - tw2.x) * ((float).5);
+      imv = (tw2.y - f1k.y) * ((float).5);
+    }
+  }
+  const float r2 = re * re, i2 = imv * imv;
+  return sqrtf(r2 + i2) * norm;
+}
+
 // FFT B of one windowed 2048-sample frame given in layout X (register r of
 // lane l = packed input k = l + 64 r), then kiss_fftr's split for the
 // reported bins, magnitudes and the band sums in bin order; lane b < n_bands
 // returns band b's sum.  R: the wave's exchange region (kFbSlots float2; the
 // caller's input may live there until v is loaded); mag: kFbMag floats.
+// kTap: the magnitudes of the bins a.spec_lo..a.spec_hi also go to spec (the
+// window's row of a.spec for this channel; coalesced along the bin index).
+template <bool kTap>
 __device__ __forceinline__ float fftb_bands(float2 (&v)[16], float2 *R, float *mag, const FbTabs &tb,
-                                            const StagedArgs &a, int lane) {
+                                            const StagedArgs &a, int lane, float *spec = nullptr) {
   const Plan *__restrict__ P = a.plan;
   FbTw w;
   fftb_tw_load(w, P, lane);
@@ -568,32 +600,10 @@ __device__ __forceinline__ float fftb_bands(float2 (&v)[16], float2 *R, float *m
 #pragma unroll
   for (int r = 0; r < 16; r++) R[64 * r + lane] = v[r];
   wfft::wsync();
-  const int nc = 1024;
-  for (int k = lo + lane; k <= hi; k += 64) {
-    float re, imv;
-    if (k == 0) {
-      re = R[0].x + R[0].y;
-      imv = 0;
-    } else if (k == nc) {
-      re = R[0].x - R[0].y;
-      imv = 0;
-    } else {
-      const int kk = (k < nc / 2) ? k : nc - k;
-      const float2 fpk = R[kk];
-      const float2 fpnk = make_float2(R[nc - kk].x, -R[nc - kk].y);
-      const float2 f1k = cadd(fpk, fpnk), f2k = csub(fpk, fpnk);
-      const float2 tw2 = cmul(f2k, sup[kk - 1]);
-      if (k < nc / 2) {
-        re = (f1k.x + tw2.x) * ((float).5);
-        imv = (f1k.y + tw2.y) * ((float).5);
-      } else {
-        re = (f1k.x - tw2.x) * ((float).5);
-        imv = (tw2.y - f1k.y) * ((float).5);
-      }
-    }
-    const float r2 = re * re, i2 = imv * imv;
-    mag[k - lo] = sqrtf(r2 + i2) * P->norm_b;
-  }
+  for (int k = lo + lane; k <= hi; k += 64) mag[k - lo] = fftb_mag(R, sup, k, P->norm_b);
+  // the window's spectrum (want_spectrum): the same values for the tap's bins, a lane per bin
+  if constexpr (kTap)
+    for (int k = a.spec_lo + lane; k <= a.spec_hi; k += 64) spec[k - a.spec_lo] = fftb_mag(R, sup, k, P->norm_b);
   wfft::wsync();
   float acc = 0.0f;
   if (lane < nb)
@@ -602,7 +612,9 @@ __device__ __forceinline__ float fftb_bands(float2 (&v)[16], float2 *R, float *m
   return acc;
 }
 
-__global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftbw(StagedArgs a) {
+// (kTap: k_fftbw_spec, the want_spectrum twin, which also writes a.spec)
+template <bool kTap>
+__device__ __forceinline__ void fftbw_run(StagedArgs a) {
   __shared__ __attribute__((aligned(16))) float2 Rg[kWNW][kFbSlots];
   __shared__ float mg[kWNW][kFbMag];
   __shared__ FbTabs tb;
@@ -641,8 +653,10 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftbw(StagedArgs a) {
       const float t1 = ring[i1] * P->hannb[2 * k + 1];
       v[r] = make_float2(t0, t1);
     }
-    const float band = fftb_bands(v, R, mag, tb, a, lane);
-    if (lane < nb) a.out_band[(((size_t)t * a.n_streams + s) * C + c) * nb + lane] = band;
+    const size_t ow = ((size_t)t * a.n_streams + s) * C + c;
+    const float band =
+        fftb_bands<kTap>(v, R, mag, tb, a, lane, kTap ? a.spec + ow * (size_t)(a.spec_hi - a.spec_lo + 1) : nullptr);
+    if (lane < nb) a.out_band[ow * nb + lane] = band;
   }
 }
 
@@ -661,8 +675,10 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftbw(StagedArgs a) {
 // instead of every sample written and read back).  The window bookkeeping of
 // k_winmeta (completion, share-weighted volume ratio, window vad) runs on
 // every wave of the stream identically; channel 0 writes it.
+// k_olafb_spec: the want_spectrum twin (kTap), which also writes a.spec.
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
+template <bool kTap>
+__device__ __forceinline__ void olafb_run(StagedArgs a) {
   __shared__ __attribute__((aligned(16))) float2 Rg[kWNW][kFbSlots];  // window samples, then the FFT exchanges
   __shared__ float mg[kWNW][kFbMag];
   __shared__ float ovg[kWNW][kFrame];  // a completing tick's samples past the window
@@ -811,7 +827,8 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
             const float2 x = *reinterpret_cast<const float2 *>(W + 2 * k);
             v[rr] = make_float2(x.x * P->hannb[2 * k], x.y * P->hannb[2 * k + 1]);
           }
-          const float band = fftb_bands(v, R, mag, tb, a, lane);
+          const float band = fftb_bands<kTap>(
+              v, R, mag, tb, a, lane, kTap ? a.spec + (ot * C + c) * (size_t)(a.spec_hi - a.spec_lo + 1) : nullptr);
           if (lane < nb) a.out_band[(ot * C + c) * nb + lane] = band;
           // they start the next window
           for (int i = lane; i < off + kFrame - FB; i += 64) W[i] = ov[i];
@@ -857,6 +874,11 @@ __global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) {
   }
 }
 
+__global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftbw(StagedArgs a) { fftbw_run<false>(a); }
+__global__ void __launch_bounds__(64 * kWNW, kWOcc) k_fftbw_spec(StagedArgs a) { fftbw_run<true>(a); }
+__global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb(StagedArgs a) { olafb_run<false>(a); }
+__global__ void __launch_bounds__(64 * kWNW, kWOcc) k_olafb_spec(StagedArgs a) { olafb_run<true>(a); }
+
 // n_cu: the CUs the engine's stream may use (all, or its CU mask's)
 hipError_t launch_wave(WaveKernel which, const StagedArgs &a, int n_cu, hipStream_t stream) {
   static const int p_fftA = resident_per_cu(k_fftAw, 64 * kWNW), p_pspec = resident_per_cu(k_pspecw, 64 * kPNW),
@@ -870,6 +892,22 @@ hipError_t launch_wave(WaveKernel which, const StagedArgs &a, int n_cu, hipStrea
   // measured with the timed pushes' dispatch race gone, §8 r5)
   const int g_fftA = p_fftA * n_cu, g_pspec = p_pspec * n_cu, g_synth = p_synth * n_cu, g_fftb = p_fftb * n_cu,
             g_olafb = std::min(p_olafb, 2) * n_cu;
+  // want_spectrum (a.spec): the _spec twins, with their own residency
+  if (which == kWaveOlaFb && a.spec) {
+    static const int p_spec = resident_per_cu(k_olafb_spec, 64 * kWNW);
+    const int G = kWNW / a.n_channels;
+    hipLaunchKernelGGL(k_olafb_spec, dim3((unsigned)std::min<long long>((a.n_streams + G - 1) / G, std::min(p_spec, 2) * n_cu)),
+                       dim3(64 * kWNW), 0, stream, a);
+    return hipGetLastError();
+  }
+  if (which == kWaveFftB && a.spec) {
+    static const int p_spec = resident_per_cu(k_fftbw_spec, 64 * kWNW);
+    const long long items = (long long)a.n_streams * a.wmax * a.n_channels;
+    hipLaunchKernelGGL(k_fftbw_spec,
+                       dim3((unsigned)std::min<long long>(std::max<long long>((items + kWNW - 1) / kWNW, 1), p_spec * n_cu)),
+                       dim3(64 * kWNW), 0, stream, a);
+    return hipGetLastError();
+  }
   if (which == kWaveOlaFb) {
     const int G = kWNW / a.n_channels;
     hipLaunchKernelGGL(k_olafb, dim3((unsigned)std::min<long long>((a.n_streams + G - 1) / G, g_olafb)), dim3(64 * kWNW),

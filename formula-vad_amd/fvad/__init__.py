@@ -38,7 +38,8 @@ class EngineConfig(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("n_channels", C.c_int), ("device", C.c_int), ("sample_rate", C.c_int),
                 ("fft_size", C.c_int), ("max_ticks", C.c_int), ("n_bands", C.c_int),
                 ("band_lo", C.c_int * MAX_BANDS), ("band_hi", C.c_int * MAX_BANDS), ("want_denoised", C.c_int),
-                ("mode", C.c_int), ("use_denoiser", C.c_int), ("input_rate", C.c_int)]
+                ("mode", C.c_int), ("use_denoiser", C.c_int),
+                ("want_spectrum", C.c_int), ("spec_lo", C.c_int), ("spec_hi", C.c_int), ("input_rate", C.c_int)]
 
 
 class ResampleDesc(C.Structure):
@@ -267,6 +268,8 @@ SYMBOLS = [
     ("fvad_engine_input_frame", C.c_int, [C.c_void_p]),
     ("fvad_engine_fetch_input", C.c_int, [C.c_void_p, C.c_int, F32P]),
     ("fvad_engine_resample_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("fvad_engine_spectrum_bins", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("fvad_engine_fetch_spectrum", C.c_int, [C.c_void_p, C.c_int, F32P]),
     ("fvad_vadm_config_default", None, [C.c_void_p]),
     ("fvad_vadm_create", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fvad_vadm_destroy", None, [C.c_void_p]),
@@ -311,6 +314,10 @@ SYMBOLS = [
     ("fvad_sweep_last_run", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                       C.POINTER(C.c_size_t)]),
     ("fvad_sweep_bytes", C.c_size_t, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("fvad_sweep_create_spectral", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fvad_sweep_set_spectra", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, F32P, F32P, F32P]),
+    ("fvad_sweep_append_spectra", C.c_int, [C.c_void_p, C.c_void_p, F32P, C.c_int, I32P]),
+    ("fvad_sweep_bandmin_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("fvad_sweep_set_debug", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("fvad_sweep_debug_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("fvad_synth_stream", C.c_long, [C.c_uint32, C.c_size_t, C.c_int, F32P, F32P, C.c_size_t]),
@@ -457,7 +464,7 @@ class Engine:
     """Batched hot path for a partition of streams on one GPU."""
 
     def __init__(self, model, n_streams, n_channels=2, device=0, max_ticks=100, fft_size=2048, bands=((4, 64),),
-                 want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000):
+                 want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000, spectrum=None):
         cfg = EngineConfig()
         lib().fvad_engine_config_default(C.byref(cfg), n_streams, n_channels)
         cfg.device = device
@@ -473,6 +480,10 @@ class Engine:
         cfg.use_denoiser = int(use_denoiser)
         # 8000 .. 96000: the pushes are at that rate, resampled to 48 kHz on the device
         cfg.input_rate = 0 if input_rate in (0, 48000) else input_rate
+        # spectrum=(lo, hi): every completed window's magnitudes of the FFT-B bins lo..hi
+        # are kept for fetch_spectrum, and push returns them as out["spectrum"]
+        if spectrum is not None:
+            cfg.want_spectrum, (cfg.spec_lo, cfg.spec_hi) = 1, spectrum
         self.cfg = cfg
         self.model = model
         h = C.c_void_p()
@@ -485,6 +496,7 @@ class Engine:
         self.wpt = lib().fvad_engine_windows_per_tick(h)
         # input samples per tick and channel: input_rate / 100 (480 at 48 kHz)
         self.frame_in = lib().fvad_engine_input_frame(h)
+        self.n_spec = lib().fvad_engine_spectrum_bins(h, None, None)  # 0: no tap
 
     def _alloc_out(self, n_ticks, denoised):
         T, B, Ch, nb, W = n_ticks, self.B, self.C, self.nb, self.wpt
@@ -512,6 +524,8 @@ class Engine:
         _check(lib().fvad_engine_push_ex(self.h, fptr(pcm), T, tv.ctypes.data_as(I32P) if tv is not None else None,
                                          lt.ctypes.data_as(I32P) if lt is not None else None, C.byref(s)),
                "fvad_engine_push_ex")
+        if self.n_spec:
+            o["spectrum"] = self.fetch_spectrum(T)
         return o
 
     def input_slot(self):
@@ -794,6 +808,14 @@ class Engine:
         resampling engine, [n_ticks][streams][channels][480] (a sync point)."""
         out = np.zeros((n_ticks, self.B, self.C, FRAME), np.float32)
         _check(lib().fvad_engine_fetch_input(self.h, n_ticks, fptr(out)), "fvad_engine_fetch_input")
+        return out
+
+    def fetch_spectrum(self, n_ticks):
+        """fvad_engine_fetch_spectrum: the window spectra of the last launched push,
+        [n_ticks][streams]([W])[channels][n_spec] like out["band"] (a sync point)."""
+        ws = (n_ticks, self.B) if self.wpt == 1 else (n_ticks, self.B, self.wpt)
+        out = np.zeros(ws + (self.C, max(1, self.n_spec)), np.float32)
+        _check(lib().fvad_engine_fetch_spectrum(self.h, n_ticks, fptr(out)), "fvad_engine_fetch_spectrum")
         return out
 
     def resample_times(self):
@@ -1183,7 +1205,10 @@ class Sweep:
     one GPU lane per (stream, config), or the host VADMachine with device=-1."""
 
     def __init__(self, n_streams, n_channels=2, device=0, fft_size=2048, bands=((4, 64),), use_denoiser=True,
-                 seg_capacity=256, sample_rate=48000):
+                 seg_capacity=256, sample_rate=48000, spectrum=None):
+        """spectrum=(lo, hi): a spectral sweep (fvad_sweep_create_spectral) -- it records
+        window spectra of the bins lo..hi (set_spectra, append_spectra) and runs configs
+        of any speech band inside them; bands is then ignored."""
         cfg = SweepConfig()
         cfg.n_streams, cfg.n_channels, cfg.sample_rate, cfg.fft_size = n_streams, n_channels, sample_rate, fft_size
         cfg.n_bands = len(bands)
@@ -1194,8 +1219,13 @@ class Sweep:
         self.cfg = cfg
         self.h = None
         h = C.c_void_p()
-        _check(lib().fvad_sweep_create(C.byref(cfg), C.byref(h)), "fvad_sweep_create")
+        if spectrum is None:
+            _check(lib().fvad_sweep_create(C.byref(cfg), C.byref(h)), "fvad_sweep_create")
+        else:
+            _check(lib().fvad_sweep_create_spectral(C.byref(cfg), spectrum[0], spectrum[1], C.byref(h)),
+                   "fvad_sweep_create_spectral")
         self.h = h
+        self.n_spec = 0 if spectrum is None else spectrum[1] - spectrum[0] + 1
         self.B, self.C, self.nb, self.n_cfgs = n_streams, n_channels, len(bands), 0
         self.kept_segments = True  # the last run kept its segments (run_score does not)
 
@@ -1222,6 +1252,34 @@ class Sweep:
         tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
         _check(lib().fvad_sweep_append_outputs(self.h, C.byref(s), T, tv.ctypes.data_as(I32P) if tv is not None
                                                else None), "fvad_sweep_append_outputs")
+
+    def set_spectra(self, stream, spectrum, vol_ratio, vad=None):
+        """spectrum [windows][channels][n_spec], vol_ratio [windows], vad [windows] or None (0)."""
+        r = np.ascontiguousarray(vol_ratio, np.float32).reshape(-1)
+        b = np.ascontiguousarray(spectrum, np.float32)
+        if self.n_spec:  # (a plain sweep: the library refuses the call)
+            b = b.reshape(len(r), self.C, self.n_spec)
+        v = np.ascontiguousarray(vad, np.float32).reshape(len(r)) if vad is not None else None
+        _check(lib().fvad_sweep_set_spectra(self.h, stream, len(r), fptr(b), fptr(v) if v is not None else None,
+                                            fptr(r)), "fvad_sweep_set_spectra")
+
+    def append_spectra(self, out, spectrum=None, ticks_valid=None):
+        """The completed windows of one push appended to every stream, with their spectra:
+        out is Engine.push's dict, spectrum its out["spectrum"] unless given."""
+        T = out["win_flag"].shape[0]
+        a = {k: np.ascontiguousarray(out[k], np.int32 if k == "win_flag" else np.float32)
+             for k in ("win_flag", "win_ratio", "win_vad")}
+        sp = np.ascontiguousarray(out["spectrum"] if spectrum is None else spectrum, np.float32)
+        s = Outputs(None, None, a["win_flag"].ctypes.data_as(I32P), fptr(a["win_ratio"]), fptr(a["win_vad"]), None, None)
+        tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
+        _check(lib().fvad_sweep_append_spectra(self.h, C.byref(s), fptr(sp), T, tv.ctypes.data_as(I32P)
+                                               if tv is not None else None), "fvad_sweep_append_spectra")
+
+    def bandmin_ms(self):
+        """k_sweep_bandmin's event time in the last run of a spectral sweep, all chunks (ms)."""
+        ms = C.c_double()
+        _check(lib().fvad_sweep_bandmin_ms(self.h, C.byref(ms)), "fvad_sweep_bandmin_ms")
+        return ms.value
 
     def run(self, cfgs):
         arr, n = self._cfgs(cfgs)

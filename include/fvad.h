@@ -117,6 +117,12 @@ typedef struct {
   int use_denoiser;     /* VAD.Config.use_denoiser (default 1).  0: fft_size frames of raw input go
                          * straight to FFT B (VAD.zig:206-212,239-249); per-tick vad / ratio are -1,
                          * the window ratio is preAnalyzeSegment's over the frame, window vad -1 */
+  int want_spectrum;    /* 1: FFT B also writes every completed window's magnitudes of the bins
+                         * spec_lo..spec_hi (section 2c below; default 0: nothing of it exists) */
+  int spec_lo, spec_hi; /* inclusive FFT-B bin range, 0 <= spec_lo <= spec_hi <= fft_size / 2 (default 0, 1024);
+                         * read only with want_spectrum */
+  /* ABI note: want_spectrum, spec_lo and spec_hi stand in front of input_rate, which stays the struct's
+   * last field; a binding that declares the struct itself must insert them here */
   /* ABI note (r5): the trailing `unsigned cu_mask[8]` of earlier builds was removed; a binding
    * compiled against them must drop it (fvad_engine_config_default fills every field) */
   int input_rate;       /* the rate of the pushed samples: 0 or 48000 (default 0) for 48 kHz input, or 8000,
@@ -403,6 +409,37 @@ int fvad_engine_fetch_input(fvad_engine *e, int n_ticks, float *pcm48);
 /* average event time (ms) of a push's resample launches (k_resample and the
  * tail update behind it) and the pushes measured; a sync point */
 int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs);
+
+/* ------------------------------------------------------------------ */
+/* 2c. Window spectra (fvad_engine_config.want_spectrum)                */
+/* ------------------------------------------------------------------ */
+/* An engine created with want_spectrum keeps, beside the band sums, the
+ * magnitude spectrum of every completed window: n_spec = spec_hi - spec_lo + 1
+ * f32 per channel, bin k = sqrtf(re * re + im * im) * norm of kiss_fftr's
+ * output over the Hann-windowed fft_size samples -- the reference's
+ * Spectrogram.compute at hop_size == fft_size (Spectrogram.zig:30-94), and the
+ * very values FFT B sums into the bands: a band sum is
+ * acc = 0.0f; for k = lo .. hi: acc += spectrum[k], in f32, to the bit.
+ * Every staged-family mode, with or without the denoiser or input_rate;
+ * FVAD_MODE_FUSED with want_spectrum is FVAD_EINVAL, as is a bad range.  The
+ * tap has no per-stream state and changes no other output; an engine without
+ * it allocates and launches what it always did.
+ *
+ * The device holds the spectra of one push, [ticks][streams][W][channels]
+ * [n_spec] (fvad_outputs.band's layout with n_spec for n_bands, W =
+ * fvad_engine_windows_per_tick): slot w < win_flag of a valid tick is the
+ * tick's w-th completed window, every other slot reads 0.  The next launched
+ * push overwrites them: fvad_outputs, the pinned output slots and the output
+ * log carry no spectra.
+ *
+ * fvad_engine_spectrum_bins: n_spec and (nullable) the range; 0 when the tap
+ * is off.  fvad_engine_fetch_spectrum: a sync point; the first n_ticks ticks
+ * of the last launched push's spectra -- of fvad_engine_push[_ex], of
+ * fvad_engine_run_resident, or of the only outstanding submit once collected.
+ * FVAD_EINVAL while a submitted push is uncollected, without the tap, and for
+ * n_ticks < 1 or above that push's ticks. */
+int fvad_engine_spectrum_bins(const fvad_engine *e, int *lo, int *hi);
+int fvad_engine_fetch_spectrum(fvad_engine *e, int n_ticks, float *out);
 
 /* ------------------------------------------------------------------ */
 /* 3. Host mirror of the reference API (C++ above this ABI)             */
@@ -893,6 +930,40 @@ int fvad_sweep_last_run(const fvad_sweep *sw, size_t *n_cfgs, int *kept_segments
  * (buffers, states, segments, constants; the recorded windows come on top:
  * (n_channels * n_bands + n_bands + 2) floats each); 0 on invalid arguments. */
 size_t fvad_sweep_bytes(const fvad_sweep_config *cfg, const fvad_vadm_config *cfgs, size_t n_cfgs);
+/* Spectral sweeps: any speech band per config.  A band sum cannot be rebuilt
+ * from other band sums (it is one f32 chain in bin order), so a spectral sweep
+ * records each window's magnitudes of the bins spec_lo..spec_hi (section 2c:
+ * what an engine with want_spectrum and the same range fetches) instead of
+ * band sums.  cfg->n_bands and band_lo / band_hi are ignored; the range check
+ * is the engine's (FVAD_EINVAL); device = -1 makes a host-only spectral sweep.
+ *
+ * fvad_sweep_set_spectra and fvad_sweep_append_spectra are fvad_sweep_set_windows
+ * and fvad_sweep_append_outputs with spectrum [n_windows][n_channels][n_spec],
+ * or fvad_engine_fetch_spectrum's layout beside the push's outputs (win_flag,
+ * win_ratio, win_vad required), in band's place: the same window order and
+ * ticks_valid rules.  The band-sum setters on a spectral sweep and the
+ * spectral setters on a plain sweep are FVAD_EINVAL.
+ *
+ * fvad_sweep_run, _run_host and _run_score accept every config whose speech
+ * band [lo, hi] lies inside [spec_lo, spec_hi] (FVAD_EINVAL naming the first
+ * config otherwise, nothing run).  The distinct bands of a chunk of configs,
+ * in order of first appearance, get a slot each; k_sweep_bandmin turns the
+ * recorded spectra into the windows' band minima of those D bands -- per
+ * channel acc = 0.0f; for k = lo .. hi: acc += spectrum[k], then the minimum
+ * over channels from 999 with strict < -- and the machines run unchanged over
+ * them.  The host path runs the same sums (fvad_bandsum_core.h).  A chunk's
+ * minima (windows * D floats) count against the chunk budget;
+ * fvad_sweep_bytes does not include them, nor the spectra
+ * (n_channels * n_spec + 2 floats per window). */
+int fvad_sweep_create_spectral(const fvad_sweep_config *cfg, int spec_lo, int spec_hi, fvad_sweep **out);
+int fvad_sweep_set_spectra(fvad_sweep *sw, int stream, size_t n_windows, const float *spectrum, const float *vad,
+                           const float *vol_ratio);
+int fvad_sweep_append_spectra(fvad_sweep *sw, const fvad_outputs *out, const float *spectrum, int n_ticks,
+                              const int32_t *ticks_valid);
+/* k_sweep_bandmin's time in the last run of a spectral sweep, by HIP events round
+ * its launches, summed over the chunks (0 after a host run); FVAD_EINVAL on a
+ * plain sweep */
+int fvad_sweep_bandmin_ms(const fvad_sweep *sw, double *ms);
 /* Test hooks (results are identical for every setting), for the next runs:
  *   FVAD_SWEEP_DEBUG_BOUND_SCALE  the lazy long-term test's bound times value (-1: infinite, 0: default)
  *   FVAD_SWEEP_DEBUG_DEFER_MAX    settle an owed fold once value long pushes are owed (0: default)
