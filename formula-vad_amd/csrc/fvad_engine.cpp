@@ -59,6 +59,7 @@ extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams,
   c->band_hi[0] = 64;
   c->want_denoised = 0;
   c->use_denoiser = 1;
+  c->denoised_rate = 0;
   c->input_rate = 0;
   c->want_spectrum = 0;
   c->spec_lo = 0;
@@ -197,6 +198,9 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
   if (e->rs)  // (their owner, the prep stream, is idle: synchronised above)
     HIP_TRY(hipMemsetAsync(e->rs->tails.get(), 0,
                            sizeof(float) * (size_t)(e->rs->d.K - 1) * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
+  if (e->ro)
+    HIP_TRY(hipMemsetAsync(e->ro->tails.get(), 0,
+                           sizeof(float) * (size_t)(e->ro->d.K - 1) * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
   return FVAD_OK;
 }
@@ -247,6 +251,13 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   fvad::rs::Desc rd{};
   if (resample && !fvad::rs::describe(c.input_rate, rd))
     return fail(FVAD_ERATE, "input_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
+  // denoised_rate: 0 or 48000 for the 48 kHz signal, or a rate k_resample_out brings it to
+  const bool resample_out = c.denoised_rate != 0 && c.denoised_rate != 48000;
+  fvad::rs::DescOut od{};
+  if (resample_out && !fvad::rs::describe_out(c.denoised_rate, od))
+    return fail(FVAD_ERATE, "denoised_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
+  if (resample_out && (!c.want_denoised || !c.use_denoiser))
+    return fail(FVAD_EINVAL, "denoised_rate needs want_denoised = 1 and use_denoiser = 1");
   if (c.n_streams < 1 || c.n_channels < 1 || c.n_channels > FVAD_MAX_CHANNELS)
     return fail(FVAD_EINVAL, "n_streams >= 1 and 1 <= n_channels <= 8 required");
   // FFT.zig:29-31: any even, non-zero size.  fft_size < 480 completes several
@@ -288,6 +299,7 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   fvad_engine *e = new fvad_engine();
   e->cfg = c;
   if (!resample) e->cfg.input_rate = 0;
+  if (!resample_out) e->cfg.denoised_rate = 0;
   // the staged path writes every tick of a push before FFT B reads its
   // windows, so the ring holds one window plus a whole push
   // the re-block ring holds a window plus a push; a multiple of 4 so a
@@ -416,6 +428,11 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
     e->rs->d = rd;
     if ((rc = resample_make(e))) return bail(rc);
   }
+  if (resample_out) {
+    e->ro.reset(new ResampleOut());
+    e->ro->d = od;
+    if ((rc = resample_out_make(e))) return bail(rc);
+  }
   if ((rc = fvad_engine_reset(e))) return bail(rc);
   *out = e;
   return FVAD_OK;
@@ -501,6 +518,9 @@ int run_fused(fvad_engine *e, int n_ticks, bool use_ticks, bool timed) {
   if (timed) HIP_TRY(hipEventRecord(e->ev[1], e->stream.get()));
   HIP_TRY(fvad::launch_frame(fa, e->stream.get()));
   if (timed) HIP_TRY(hipEventRecord(e->ev[2], e->stream.get()));
+  // the denoised rows at denoised_rate, behind k_frame, their writer
+  if (e->ro)
+    if (const int rr = resample_out_push(e, n_ticks, pa.ticks_valid)) return rr;
   return FVAD_OK;
 }
 
@@ -670,6 +690,10 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
       HIP_TRY(hipMemcpyAsync(L + off[i], src[i], n[i] * 4, hipMemcpyDeviceToDevice, e->stream.get()));
     e->log_ticks[e->log_n++] = n_ticks;
   }
+  // the denoised rows at denoised_rate, behind the tail kernels, the push's
+  // last writers of d_den (it reads ticks buffer b: ahead of ev_buf_free)
+  if (e->ro)
+    if (const int rr = resample_out_push(e, n_ticks, a.ticks_valid)) return rr;
   // every reader of buffer b (incl. the copy of ticks for k_vadm_hbm) is queued
   HIP_TRY(hipEventRecord(e->ev_buf_free[b].get(), e->stream.get()));
   e->buf_busy[b] = true;
@@ -740,7 +764,7 @@ int fvad::eng::fetch(fvad_engine *e, int n_ticks, fvad_outputs *o) {
     return rc;
   if (o->denoised) {
     if (!e->d_den) return fail(FVAD_EINVAL, "engine created without want_denoised");
-    if ((rc = cp(o->denoised, e->d_den.get(), TB * c.n_channels * fvad::kFrame * 4))) return rc;
+    if ((rc = cp(o->denoised, denoised_source(e), TB * c.n_channels * denoised_frame(e) * 4))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
   return FVAD_OK;
@@ -931,6 +955,10 @@ extern "C" int fvad_engine_clear_times(fvad_engine *e) {
   if (e->rs) {
     e->rs->ms_sum = 0;
     e->rs->n_timed = 0;
+  }
+  if (e->ro) {
+    e->ro->ms_sum = 0;
+    e->ro->n_timed = 0;
   }
   if (e->cap)
     for (int k = 0; k < 2; k++) {

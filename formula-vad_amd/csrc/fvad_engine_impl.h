@@ -20,6 +20,7 @@
 #include "fvad_lifecycle.h"
 #include "fvad_machine.h"
 #include "fvad_resample.h"
+#include "fvad_resample_out.h"
 #include "fvad_staged.h"
 
 #define HIP_TRY(expr)                                                                                             \
@@ -129,6 +130,21 @@ struct Resample {
   dev_ptr<float> raw[2];  // max_ticks * B * C * n_in words each
   bool in16 = false;      // the push being launched holds int16 samples
   EventTimer tm[2];       // the resample launches of a push, alternately
+  int slot = 0;
+  double ms_sum = 0;
+  int n_timed = 0;
+};
+
+// The denoised PCM at another rate (fvad_engine_config.denoised_rate;
+// DESIGN.md section 7, "Output rate of the denoised PCM"): everything it owns,
+// made by fvad_engine_create; an engine that returns the 48 kHz signal has
+// none of it.  All of it is the engine stream's.
+struct ResampleOut {
+  rs::DescOut d{};
+  dev_ptr<float> taps;   // [L][K]
+  dev_ptr<float> tails;  // [s][c][K - 1]
+  dev_ptr<float> out;    // d_den_out: [tick][s][c][n_out], max_ticks ticks
+  EventTimer tm[4];      // the two launches of a push, in turn (three pushes in flight and their copies)
   int slot = 0;
   double ms_sum = 0;
   int n_timed = 0;
@@ -369,6 +385,8 @@ struct fvad_engine {
   int rt_n[3] = {};
   // input resampling (input_rate set): null on an engine of 48 kHz input
   std::unique_ptr<fvad::eng::Resample> rs;
+  // the denoised PCM at another rate (denoised_rate set): null otherwise
+  std::unique_ptr<fvad::eng::ResampleOut> ro;
   // clip capture, last: released before everything it refers to
   std::unique_ptr<fvad::eng::Capture> cap;
 };
@@ -395,6 +413,13 @@ void *input_target(const fvad_engine *e);
 hipStream_t resample_stream(const fvad_engine *e);
 int resample_make(fvad_engine *e);
 int resample_push(fvad_engine *e, int n_ticks, const int *d_ticks);
+// the denoised PCM at another rate: samples per tick and channel of the
+// denoised rows the host receives, the device rows they are copied from, and
+// the push's two launches on the engine stream (behind its last writer of d_den)
+int denoised_frame(const fvad_engine *e);
+const float *denoised_source(const fvad_engine *e);
+int resample_out_make(fvad_engine *e);
+int resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks);
 // fvad_engine_vadm.cpp
 int vadm_reset(fvad_engine *e);
 int vadm_flush(fvad_engine *e, bool fast = true);

@@ -115,6 +115,68 @@ extern "C" int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n
   return FVAD_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The denoised PCM at another rate (denoised_rate set; fvad_resample_out.h):
+// k_resample_out writes d_den_out from d_den on the engine stream, and every
+// copy of denoised rows to the host reads d_den_out
+// ---------------------------------------------------------------------------
+int fvad::eng::denoised_frame(const fvad_engine *e) { return e->ro ? e->ro->d.n_out : fvad::kFrame; }
+
+const float *fvad::eng::denoised_source(const fvad_engine *e) { return e->ro ? e->ro->out.get() : e->d_den.get(); }
+
+// fvad_engine_create's part: the table, the tails (zeroed by the reset that
+// follows) and the output rows
+int fvad::eng::resample_out_make(fvad_engine *e) {
+  ResampleOut &r = *e->ro;
+  const fvad_engine_config &c = e->cfg;
+  const std::vector<float> &taps = fvad::resample_out_table(r.d);
+  const size_t rows = (size_t)c.n_streams * c.n_channels;
+  int rc;
+  if ((rc = fvad::make_dev(r.taps, taps.size())) || (rc = fvad::make_dev(r.tails, rows * (r.d.K - 1))) ||
+      (rc = fvad::make_dev(r.out, (size_t)c.max_ticks * rows * r.d.n_out)))
+    return rc;
+  for (EventTimer &tm : r.tm)
+    if ((rc = tm.create())) return rc;
+  HIP_TRY(hipMemcpy(r.taps.get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+  return FVAD_OK;
+}
+
+// the two launches of the push being launched, on the engine stream behind
+// its last writer of d_den, timed without waiting (as resample_push)
+int fvad::eng::resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
+  ResampleOut &r = *e->ro;
+  fvad::ResampleOutArgs a{};
+  a.den = e->d_den.get();
+  a.taps = r.taps.get();
+  a.tails = r.tails.get();
+  a.ticks_valid = d_ticks;
+  a.out = r.out.get();
+  a.n_streams = e->cfg.n_streams;
+  a.n_channels = e->cfg.n_channels;
+  a.n_ticks = n_ticks;
+  a.d = r.d;
+  hipStream_t st = e->stream.get();
+  EventTimer &tm = r.tm[r.slot = (r.slot + 1) % 4];
+  int rc;
+  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
+  HIP_TRY(fvad::launch_resample_out(a, st));
+  return tm.end(st);
+}
+
+extern "C" int fvad_engine_denoised_frame(const fvad_engine *e) { return e ? denoised_frame(e) : FVAD_EINVAL; }
+
+extern "C" int fvad_engine_resample_out_times(fvad_engine *e, double *ms_avg, int *n_runs) {
+  if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
+  if (!e->ro) return fail(FVAD_EINVAL, "fvad_engine_resample_out_times reads an engine with denoised_rate set");
+  if (const int rc = fvad_engine_sync(e)) return rc;
+  ResampleOut &r = *e->ro;
+  for (EventTimer &tm : r.tm)
+    if (const int rc = tm.collect(r.ms_sum, r.n_timed)) return rc;
+  *ms_avg = r.n_timed ? r.ms_sum / r.n_timed : 0.0;
+  if (n_runs) *n_runs = r.n_timed;
+  return FVAD_OK;
+}
+
 int fvad::eng::check_ticks(const fvad_engine *e, const int32_t *ticks_valid, int n_ticks) {
   if (ticks_valid)
     for (int s = 0; s < e->cfg.n_streams; s++)
@@ -184,7 +246,8 @@ int ensure_slots(fvad_engine *e, int i) {
     // windows_per_tick (up to 240 at fft_size 2): refuse configurations whose
     // slot would not be a sane pinned allocation (the streaming API only:
     // resident and push-from-host engines never allocate a slot)
-    const double slot = 4.0 * ((double)frames * (c.want_denoised ? 2 : 1) + 3.0 * TB + 2.0 * TBW +
+    const double slot = 4.0 * ((double)frames + (c.want_denoised ? (double)TB * C * denoised_frame(e) : 0.0) + 3.0 * TB +
+                               2.0 * TBW +
                                (double)TBW * C * c.n_bands);
     if (slot > 16.0 * (1ull << 30))
       return fail(FVAD_ENOMEM, "a push of max_ticks x n_streams needs > 16 GiB of pinned slot memory "
@@ -209,7 +272,7 @@ int ensure_slots(fvad_engine *e, int i) {
   if ((rc = host(sl.in, TB * C * input_frame(e))) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
       (rc = host(sl.ratio, TB)) || (rc = host(sl.wflag, TB)) || (rc = host(sl.wratio, TBW)) ||
       (rc = host(sl.wvad, TBW)) || (rc = host(sl.band, TBW * C * c.n_bands)) ||
-      (c.want_denoised && (rc = host(sl.den, frames))))
+      (c.want_denoised && (rc = host(sl.den, TB * C * denoised_frame(e)))))
     return rc;
   if ((!sl.h2d && (rc = fvad::make_event(sl.h2d))) || (rc = fvad::make_event(sl.done))) return rc;
   return FVAD_OK;
@@ -277,7 +340,7 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   if (sl.pending) return fail(FVAD_EINVAL, "FVAD_MAX_IN_FLIGHT pushes in flight: collect the oldest one first");
   const size_t B = c.n_streams, TB = (size_t)n_ticks * B, TBW = TB * e->wpt;
   // (n_samples: the input's, at the engine's input rate; bytes: the denoised output's)
-  const size_t n_samples = TB * c.n_channels * input_frame(e), bytes = TB * c.n_channels * fvad::kFrame * sizeof(float);
+  const size_t n_samples = TB * c.n_channels * input_frame(e), bytes = TB * c.n_channels * denoised_frame(e) * sizeof(float);
   Sample *slot_in;
   if constexpr (k16)
     slot_in = sl.in16.get();
@@ -345,7 +408,7 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   if ((rc = d2h(sl.vad.get(), e->d_vad.get(), TB * 4)) || (rc = d2h(sl.ratio.get(), e->d_ratio, TB * 4)) ||
       (rc = d2h(sl.wflag.get(), e->d_wflag, TB * 4)) || (rc = d2h(sl.wratio.get(), e->d_wratio, TBW * 4)) ||
       (rc = d2h(sl.wvad.get(), e->d_wvad, TBW * 4)) || (rc = d2h(sl.band.get(), e->d_band, TBW * c.n_channels * c.n_bands * 4)) ||
-      (c.want_denoised && (rc = d2h(sl.den.get(), e->d_den.get(), bytes))))
+      (c.want_denoised && (rc = d2h(sl.den.get(), denoised_source(e), bytes))))
     return rc;
   HIP_TRY(hipEventRecord(sl.done.get(), e->stream.get()));
   sl.pending = true;
@@ -403,7 +466,7 @@ extern "C" int fvad_engine_collect(fvad_engine *e, fvad_outputs *out, int *n_tic
     cp(out->win_ratio, sl.wratio.get(), TBW * 4);
     cp(out->win_vad, sl.wvad.get(), TBW * 4);
     cp(out->band, sl.band.get(), TBW * c.n_channels * c.n_bands * 4);
-    if (out->denoised) par_copy(out->denoised, sl.den.get(), TB * c.n_channels * fvad::kFrame * 4);
+    if (out->denoised) par_copy(out->denoised, sl.den.get(), TB * c.n_channels * denoised_frame(e) * 4);
   }
   if (n_ticks) *n_ticks = sl.n_ticks;
   sl.pending = false;

@@ -42,12 +42,14 @@ uint64_t config_hash_of(const fvad_engine *e) {
   }
   // a resampling engine's rate; an engine of 48 kHz input hashes what it always did
   if (e->rs) h = fnv_add(h, e->rs->d.rate);
+  // likewise the rate of the denoised PCM, when it is not the 48 kHz signal
+  if (e->ro) h = fnv_add(h, e->ro->d.rate);
   return h;
 }
 
 fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
   return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap,
-                           e->rs ? e->rs->d.K - 1 : 0);
+                           e->rs ? e->rs->d.K - 1 : 0, e->ro ? e->ro->d.K - 1 : 0);
 }
 
 fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
@@ -70,6 +72,7 @@ fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   h.model_hash = e->model_hash;
   h.sample_rate = (uint32_t)e->cfg.sample_rate;
   h.reserved[0] = e->rs ? (uint32_t)e->rs->d.rate : 0u;
+  h.reserved[1] = e->ro ? (uint32_t)e->ro->d.rate : 0u;
   return h;
 }
 
@@ -108,6 +111,7 @@ fvad::XferArgs xfer_args(const fvad_engine *e, const fvad::BlobLayout &lay) {
   a.lay = lay;
   a.blob = e->d_blob.get();
   a.rs_tails = e->rs ? e->rs->tails.get() : nullptr;
+  a.ro_tails = e->ro ? e->ro->tails.get() : nullptr;
   return a;
 }
 
@@ -215,6 +219,13 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
       ra.ids = ca.ids;
       HIP_TRY(fvad::launch_resample_clear(ra, resample_stream(e)));
     }
+    if (e->ro) {  // the output resampler's tails, on the engine stream, where k_resample_out runs
+      fvad::ResampleClearArgs ra{};
+      ra.tails = e->ro->tails.get();
+      ra.row_words = e->cfg.n_channels * (e->ro->d.K - 1);
+      ra.ids = ca.ids;
+      HIP_TRY(fvad::launch_resample_clear(ra, e->stream.get()));
+    }
   }
   // clip capture: the streams' positions restart behind the appends already
   // queued, their pending clips go behind the passes already queued
@@ -293,6 +304,7 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
       h.state_words != mine.state_words || h.sample_rate != mine.sample_rate)
     return fail(FVAD_EFORMAT, "stream blob from an engine with another mode, channels, fft_size, bands or machines");
   if (h.reserved[0] != mine.reserved[0]) return fail(FVAD_EFORMAT, "stream blob from an engine with another input_rate");
+  if (h.reserved[1] != mine.reserved[1]) return fail(FVAD_EFORMAT, "stream blob from an engine with another denoised_rate");
   if (h.config_hash != mine.config_hash) return fail(FVAD_EFORMAT, "stream blob from another engine configuration");
   if (h.model_hash != mine.model_hash) return fail(FVAD_EFORMAT, "stream blob from another model");
   if ((h.n_machines > 0) != (h.seg_capacity > 0) || h.seg_capacity > 0x7fffffffu / 32)

@@ -99,8 +99,9 @@ __global__ void __launch_bounds__(kNT) k_vadm_retarget(RetargetArgs a) {
 }
 
 // stream slots[i] -> record recs[i].  part 0: state; 1 + c: channel c's
-// pending window part; 1 + C + m: machine m; 1 + C + n_mach (a resampling
-// engine): the channels' resampler tails
+// pending window part; 1 + C + m: machine m; 1 + C + n_mach: the channels'
+// resampler tails, the input's (a resampling engine) and the output's (an
+// engine with denoised_rate)
 __global__ void __launch_bounds__(kNT) k_stream_gather(XferArgs a) {
   const int s = a.slots.id[blockIdx.x], part = blockIdx.y, tid = threadIdx.x;
   const BlobLayout &L = a.lay;
@@ -110,10 +111,18 @@ __global__ void __launch_bounds__(kNT) k_stream_gather(XferArgs a) {
   if (part == 0) {
     copy4(rec, stp, st::kWords, tid);
   } else if (part == 1 + C + L.n_mach) {
-    const float *tails = a.rs_tails + (size_t)s * C * L.rs_tail;
-    for (int c = 0; c < C; c++)
-      for (int j = tid; j < (int)L.rs_pad; j += kNT)
-        rec[L.o_rs + (size_t)c * L.rs_pad + j] = j < L.rs_tail ? tails[(size_t)c * L.rs_tail + j] : 0.0f;
+    if (L.rs_tail > 0) {
+      const float *tails = a.rs_tails + (size_t)s * C * L.rs_tail;
+      for (int c = 0; c < C; c++)
+        for (int j = tid; j < (int)L.rs_pad; j += kNT)
+          rec[L.o_rs + (size_t)c * L.rs_pad + j] = j < L.rs_tail ? tails[(size_t)c * L.rs_tail + j] : 0.0f;
+    }
+    if (L.ro_tail > 0) {
+      const float *tails = a.ro_tails + (size_t)s * C * L.ro_tail;
+      for (int c = 0; c < C; c++)
+        for (int j = tid; j < (int)L.ro_pad; j += kNT)
+          rec[L.o_ro + (size_t)c * L.ro_pad + j] = j < L.ro_tail ? tails[(size_t)c * L.ro_tail + j] : 0.0f;
+    }
   } else if (part <= C) {
     const int c = part - 1;
     const unsigned long long total = record_samples(stp, L.use_denoiser);
@@ -156,9 +165,16 @@ __global__ void __launch_bounds__(kNT) k_stream_scatter(XferArgs a) {
   if (part == 0) {
     copy4(a.state + (size_t)s * st::kWords, rec, st::kWords, tid);
   } else if (part == 1 + C + L.n_mach) {
-    float *tails = a.rs_tails + (size_t)s * C * L.rs_tail;
-    for (int c = 0; c < C; c++)
-      for (int j = tid; j < L.rs_tail; j += kNT) tails[(size_t)c * L.rs_tail + j] = rec[L.o_rs + (size_t)c * L.rs_pad + j];
+    if (L.rs_tail > 0) {
+      float *tails = a.rs_tails + (size_t)s * C * L.rs_tail;
+      for (int c = 0; c < C; c++)
+        for (int j = tid; j < L.rs_tail; j += kNT) tails[(size_t)c * L.rs_tail + j] = rec[L.o_rs + (size_t)c * L.rs_pad + j];
+    }
+    if (L.ro_tail > 0) {
+      float *tails = a.ro_tails + (size_t)s * C * L.ro_tail;
+      for (int c = 0; c < C; c++)
+        for (int j = tid; j < L.ro_tail; j += kNT) tails[(size_t)c * L.ro_tail + j] = rec[L.o_ro + (size_t)c * L.ro_pad + j];
+    }
   } else if (part <= C) {
     const int c = part - 1;
     const unsigned long long total = record_samples(rec, L.use_denoiser);
@@ -218,7 +234,7 @@ hipError_t launch_vadm_retarget(const RetargetArgs &a, hipStream_t stream) {
 hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream) {
   if (a.slots.n < 1) return hipSuccess;
   (void)hipGetLastError();
-  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach + (a.lay.rs_tail > 0 ? 1u : 0u);
+  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach + (a.lay.rs_tail > 0 || a.lay.ro_tail > 0 ? 1u : 0u);
   hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)a.slots.n, parts), dim3(kNT), 0, stream, a);
   return launched();
 }
@@ -226,7 +242,7 @@ hipError_t launch_stream_gather(const XferArgs &a, hipStream_t stream) {
 hipError_t launch_stream_scatter(const XferArgs &a, hipStream_t stream) {
   if (a.slots.n < 1) return hipSuccess;
   (void)hipGetLastError();
-  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach + (a.lay.rs_tail > 0 ? 1u : 0u);
+  const unsigned parts = 1u + (unsigned)a.lay.n_channels + (unsigned)a.lay.n_mach + (a.lay.rs_tail > 0 || a.lay.ro_tail > 0 ? 1u : 0u);
   hipLaunchKernelGGL(k_stream_scatter, dim3((unsigned)a.slots.n, parts), dim3(kNT), 0, stream, a);
   return launched();
 }

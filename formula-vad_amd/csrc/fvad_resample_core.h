@@ -45,8 +45,33 @@ FVAD_HD inline bool describe(int rate, Desc &d) {
   return true;
 }
 
+// The decimating direction (fvad_engine_config.denoised_rate; DESIGN.md section
+// 7, "Output rate of the denoised PCM"): a tick's 480 denoised samples give
+// n_out = rate / 100.  L = rate / g, M = 48000 / g; output r reads the K
+// 48 kHz samples ending at i = floor(r M / L) through phase p = r M mod L,
+// and 480 L / M = n_out, so a tick starts at phase 0 here too.
+constexpr int kIn = 480;            // 48 kHz samples per tick
+constexpr int kMaxTapsOut = 147 * 96;  // L * K at 44.1 kHz, the largest table
+constexpr int kMaxTailOut = 287;    // K - 1 at 8 kHz, the longest history (<= 480: inside one tick)
+
+struct DescOut {
+  int rate, L, M, K, n_out;
+};
+
+// false off the list (the same closed list as describe's)
+FVAD_HD inline bool describe_out(int rate, DescOut &d) {
+  if (rate != 8000 && rate != 16000 && rate != 24000 && rate != 32000 && rate != 44100 && rate != 96000) return false;
+  const int g = gcd(48000, rate);
+  d.rate = rate;
+  d.L = rate / g;
+  d.M = 48000 / g;
+  d.K = 48 * ((d.M + d.L - 1) / d.L);  // 48 max(1, ceil(M / L))
+  d.n_out = rate / 100;
+  return true;
+}
+
 // output r of a tick: the newest input it reads (relative to the tick's first
-// sample) and its phase.  r M <= 479 * 147.
+// sample) and its phase.  r M <= 479 * 147 (describe), 440 * 160 (describe_out).
 FVAD_HD inline void position(int r, int L, int M, int &i, int &p) {
   const int rm = r * M;
   i = rm / L;

@@ -39,13 +39,20 @@ class EngineConfig(C.Structure):
                 ("fft_size", C.c_int), ("max_ticks", C.c_int), ("n_bands", C.c_int),
                 ("band_lo", C.c_int * MAX_BANDS), ("band_hi", C.c_int * MAX_BANDS), ("want_denoised", C.c_int),
                 ("mode", C.c_int), ("use_denoiser", C.c_int),
-                ("want_spectrum", C.c_int), ("spec_lo", C.c_int), ("spec_hi", C.c_int), ("input_rate", C.c_int)]
+                ("want_spectrum", C.c_int), ("spec_lo", C.c_int), ("spec_hi", C.c_int),
+                ("denoised_rate", C.c_int), ("input_rate", C.c_int)]
 
 
 class ResampleDesc(C.Structure):
     """fvad_resample_desc (include/fvad.h)."""
     _fields_ = [("input_rate", C.c_int), ("L", C.c_int), ("M", C.c_int), ("taps_per_phase", C.c_int),
                 ("frame_in", C.c_int), ("delay", C.c_double)]
+
+
+class ResampleOutDesc(C.Structure):
+    """fvad_resample_out_desc (include/fvad.h)."""
+    _fields_ = [("rate", C.c_int), ("L", C.c_int), ("M", C.c_int), ("taps_per_phase", C.c_int),
+                ("frame_out", C.c_int), ("delay", C.c_double)]
 
 
 MODE_STAGED, MODE_FUSED, MODE_FP16, MODE_FP16_FUSED, MODE_F32_FAST = 0, 1, 2, 3, 4
@@ -268,6 +275,11 @@ SYMBOLS = [
     ("fvad_engine_input_frame", C.c_int, [C.c_void_p]),
     ("fvad_engine_fetch_input", C.c_int, [C.c_void_p, C.c_int, F32P]),
     ("fvad_engine_resample_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("fvad_resample_out_info", C.c_int, [C.c_int, C.c_void_p]),
+    ("fvad_resample_out_taps", C.c_size_t, [C.c_int, F32P, C.c_size_t]),
+    ("fvad_resample_out_host", C.c_int, [C.c_int, F32P, C.c_size_t, F32P, F32P]),
+    ("fvad_engine_denoised_frame", C.c_int, [C.c_void_p]),
+    ("fvad_engine_resample_out_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("fvad_engine_spectrum_bins", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fvad_engine_fetch_spectrum", C.c_int, [C.c_void_p, C.c_int, F32P]),
     ("fvad_vadm_config_default", None, [C.c_void_p]),
@@ -460,11 +472,46 @@ def resample_host(input_rate, x, tail=None):
     return out
 
 
+def resample_out_info(rate):
+    """fvad_resample_out_info: the downsampler from 48 kHz to rate as a dict --
+    L, M, taps_per_phase, frame_out and the delay in 48 kHz samples (host only)."""
+    d = ResampleOutDesc()
+    _check(lib().fvad_resample_out_info(rate, C.byref(d)), "fvad_resample_out_info")
+    return {n: getattr(d, n) for n, _ in d._fields_}
+
+
+def resample_out_taps(rate):
+    """fvad_resample_out_taps: the [L][taps_per_phase] float32 tap table (host only)."""
+    d = resample_out_info(rate)
+    out = np.zeros((d["L"], d["taps_per_phase"]), np.float32)
+    n = lib().fvad_resample_out_taps(rate, fptr(out), out.size)
+    assert n == out.size, (n, out.shape)
+    return out
+
+
+def resample_out_host(rate, y, tail=None):
+    """fvad_resample_out_host: one channel's whole 48 kHz ticks y ([n_ticks * 480]
+    float32) at rate ([n_ticks * frame_out]), the arithmetic of the engine's
+    k_resample_out.  tail (float32 [taps_per_phase - 1], updated in place): the
+    samples before y[0]; None: zeros, nothing kept."""
+    d = resample_out_info(rate)
+    y = np.ascontiguousarray(y, np.float32).reshape(-1)
+    assert y.size % FRAME == 0, y.size
+    n_ticks = y.size // FRAME
+    if tail is not None:
+        assert tail.dtype == np.float32 and tail.flags.c_contiguous and tail.size == d["taps_per_phase"] - 1
+    out = np.zeros(n_ticks * d["frame_out"], np.float32)
+    _check(lib().fvad_resample_out_host(rate, fptr(y), n_ticks, fptr(tail) if tail is not None else None,
+                                        fptr(out)), "fvad_resample_out_host")
+    return out
+
+
 class Engine:
     """Batched hot path for a partition of streams on one GPU."""
 
     def __init__(self, model, n_streams, n_channels=2, device=0, max_ticks=100, fft_size=2048, bands=((4, 64),),
-                 want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000, spectrum=None):
+                 want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000, spectrum=None,
+                 denoised_rate=48000):
         cfg = EngineConfig()
         lib().fvad_engine_config_default(C.byref(cfg), n_streams, n_channels)
         cfg.device = device
@@ -480,6 +527,9 @@ class Engine:
         cfg.use_denoiser = int(use_denoiser)
         # 8000 .. 96000: the pushes are at that rate, resampled to 48 kHz on the device
         cfg.input_rate = 0 if input_rate in (0, 48000) else input_rate
+        # 8000 .. 96000: the denoised PCM comes back at that rate, downsampled on the device
+        # (0 and 48000 both mean the 48 kHz signal: passed on as given)
+        cfg.denoised_rate = denoised_rate
         # spectrum=(lo, hi): every completed window's magnitudes of the FFT-B bins lo..hi
         # are kept for fetch_spectrum, and push returns them as out["spectrum"]
         if spectrum is not None:
@@ -496,6 +546,8 @@ class Engine:
         self.wpt = lib().fvad_engine_windows_per_tick(h)
         # input samples per tick and channel: input_rate / 100 (480 at 48 kHz)
         self.frame_in = lib().fvad_engine_input_frame(h)
+        # denoised samples per tick and channel: denoised_rate / 100 (480 at 48 kHz)
+        self.frame_out = lib().fvad_engine_denoised_frame(h)
         self.n_spec = lib().fvad_engine_spectrum_bins(h, None, None)  # 0: no tap
 
     def _alloc_out(self, n_ticks, denoised):
@@ -505,7 +557,7 @@ class Engine:
              "win_flag": np.zeros((T, B), np.int32), "win_ratio": np.zeros(ws, np.float32),
              "win_vad": np.zeros(ws, np.float32), "band": np.zeros(ws + (Ch, nb), np.float32)}
         if denoised:
-            o["denoised"] = np.zeros((T, B, Ch, FRAME), np.float32)
+            o["denoised"] = np.zeros((T, B, Ch, self.frame_out), np.float32)
         s = Outputs(fptr(o["vad"]), fptr(o["ratio"]), o["win_flag"].ctypes.data_as(I32P), fptr(o["win_ratio"]),
                     fptr(o["win_vad"]), fptr(o["band"]), fptr(o["denoised"]) if denoised else None)
         return o, s
@@ -822,6 +874,12 @@ class Engine:
         """(ms average of a push's resample launches, pushes measured); a sync point."""
         ms, n = C.c_double(), C.c_int()
         _check(lib().fvad_engine_resample_times(self.h, C.byref(ms), C.byref(n)), "fvad_engine_resample_times")
+        return ms.value, n.value
+
+    def resample_out_times(self):
+        """(ms average of a push's two output-resample launches, pushes measured); a sync point."""
+        ms, n = C.c_double(), C.c_int()
+        _check(lib().fvad_engine_resample_out_times(self.h, C.byref(ms), C.byref(n)), "fvad_engine_resample_out_times")
         return ms.value, n.value
 
     def fetch(self, n_ticks, denoised=False):

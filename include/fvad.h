@@ -125,7 +125,14 @@ typedef struct {
    * last field; a binding that declares the struct itself must insert them here */
   /* ABI note (r5): the trailing `unsigned cu_mask[8]` of earlier builds was removed; a binding
    * compiled against them must drop it (fvad_engine_config_default fills every field) */
-  int input_rate;       /* the rate of the pushed samples: 0 or 48000 (default 0) for 48 kHz input, or 8000,
+  int denoised_rate;    /* the rate of the denoised PCM the engine returns: 0 or 48000 (default 0) for the
+                         * 48 kHz signal, or 8000, 16000, 24000, 32000, 44100, 96000 for an engine that
+                         * brings every push's denoised rows to that rate on the device (section 2d below);
+                         * FVAD_ERATE otherwise.  A listed rate needs want_denoised = 1 and use_denoiser = 1
+                         * (FVAD_EINVAL).  Independent of input_rate */
+  /* ABI note: denoised_rate stands in front of input_rate, which stays the struct's last field; a
+   * binding that declares the struct itself must insert it here */
+  int input_rate;      /* the rate of the pushed samples: 0 or 48000 (default 0) for 48 kHz input, or 8000,
                          * 16000, 24000, 32000, 44100, 96000 for an engine that resamples every push to
                          * 48 kHz on the device (section 2b below); FVAD_ERATE otherwise.  sample_rate, the
                          * pipeline's rate, stays 48000 */
@@ -238,7 +245,11 @@ typedef struct {
   uint32_t reserved[13];  /*  76 [0]: the saving engine's input_rate when it resamples (its records then end
                            *     with the resampler's tails, per channel (taps_per_phase + 2) & ~3 words, and
                            *     config_hash covers the rate), 0 otherwise; a blob restores only into an
-                           *     engine of the same input_rate.  [1..12]: zero */
+                           *     engine of the same input_rate.  [1]: the saving engine's denoised_rate when it
+                           *     is a listed rate (its records then end with the output resampler's tails, behind
+                           *     the input tails if there are any, per channel (K + 2) & ~3 words, K section 2d's
+                           *     taps_per_phase, and config_hash covers the rate), 0 otherwise; a blob restores
+                           *     only into an engine of the same denoised_rate.  [2..12]: zero */
 } fvad_stream_blob_header;
 int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams, int n);
 /* bytes a save of n streams needs (0 for a NULL engine or n < 0) */
@@ -265,7 +276,8 @@ typedef struct {
   float *win_vad;      /* [ticks][streams][W]  window vad = last frame's vad (VAD.zig:330) */
   float *band;         /* [ticks][streams][W][channels][n_bands] band sums (PipelineFFT.zig:99-112); 0 in
                         * slots without a window */
-  float *denoised;     /* [ticks][streams][channels][480] normalised denoised PCM (want_denoised) */
+  float *denoised;     /* [ticks][streams][channels][480] normalised denoised PCM (want_denoised); with
+                        * denoised_rate [ticks][streams][channels][fvad_engine_denoised_frame(e)] (section 2d) */
 } fvad_outputs;
 
 /* W, the window slots per (tick, stream) of fvad_outputs: 1 for fft_size >=
@@ -357,7 +369,8 @@ int fvad_engine_fetch(fvad_engine *e, int n_ticks, fvad_outputs *out);
  * 480 out.  Every input shape of section 2 becomes
  * [ticks][streams][channels][frame_in] -- fvad_engine_push[_ex],
  * fvad_engine_submit[_ex], fvad_engine_submit_i16 and both input slots;
- * the outputs keep their shapes (denoised is the 48 kHz signal).
+ * the outputs keep their shapes (denoised is the 48 kHz signal, unless
+ * denoised_rate, section 2d, asks for another rate).
  *
  * The resampler, to the bit: g = gcd(48000, R), L = 48000 / g, M = R / g,
  * K = 48 max(1, ceil(M / L)) taps per phase; the prototype of N = L K taps at
@@ -440,6 +453,72 @@ int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs);
  * n_ticks < 1 or above that push's ticks. */
 int fvad_engine_spectrum_bins(const fvad_engine *e, int *lo, int *hi);
 int fvad_engine_fetch_spectrum(fvad_engine *e, int n_ticks, float *out);
+
+/* ------------------------------------------------------------------ */
+/* 2d. Output rate of the denoised PCM (fvad_engine_config.denoised_rate) */
+/* ------------------------------------------------------------------ */
+/* An engine created with denoised_rate R in {8000, 16000, 24000, 32000, 44100,
+ * 96000} (want_denoised = 1, use_denoiser = 1, any mode, any input_rate)
+ * returns its denoised PCM at R: k_resample_out, queued behind the push's last
+ * writer of the 48 kHz denoised rows, brings them to R on the device, and
+ * every place that delivers denoised PCM -- fvad_engine_push[_ex],
+ * fvad_engine_submit* / fvad_engine_collect, fvad_engine_fetch -- delivers
+ * [ticks][streams][channels][frame_out], frame_out = R / 100 samples per tick
+ * and channel (fvad_engine_denoised_frame).  Every other output is what an
+ * engine without the field gives, and segments, events and clips keep counting
+ * (and holding) the 48 kHz signal.  Ticks past a stream's ticks_valid are
+ * zeros.
+ *
+ * The downsampler, to the bit: g = gcd(48000, R), L = R / g, M = 48000 / g,
+ * K = 48 max(1, ceil(M / L)) taps per phase; the prototype of N = L K taps at
+ * the rate Fp = 48000 L is section 2b's Kaiser-windowed sinc with 48000 as the
+ * source rate, designed in f64: A = 80, beta = 0.1102 (A - 8.7),
+ * df = (A - 8) / (2.285 (N - 1)) Fp / (2 pi), f_stop = min(R, 48000) / 2,
+ * fc = f_stop - df / 2,
+ * proto[j] = sinc(2 fc / Fp (j - (N - 1) / 2)) I0(beta sqrt(1 - (2 j / (N - 1) - 1)^2)) / I0(beta),
+ * scaled to sum L; taps[p][k] = (float)proto[k L + p].  A tick stays 10 ms:
+ * 480 L / M = frame_out, so every tick starts at phase 0.  Output r
+ * (0 .. frame_out - 1) of tick t: i = floor(r M / L), p = r M mod L,
+ * acc = 0.0f, then for k = 0 .. K - 1 acc = acc + taps[p][k] * y[480 t + i - k],
+ * product and sum each rounded to f32, nothing fused or re-associated.  y is
+ * the stream's 48 kHz denoised signal: 0 before the stream's first sample;
+ * across pushes it continues from the row's last K - 1 denoised samples (kept
+ * on the device; reset, saved and restored with the stream; K - 1 <= 480, so
+ * they lie inside one tick).  Only a stream's ticks_valid ticks are consumed.
+ *
+ *   R      L    M    K   frame_out  delay in 48 kHz samples, (L K - 1) / (2 L)
+ *   8000   1    6    288    80      143.5
+ *   16000  1    3    144   160       71.5
+ *   24000  1    2     96   240       47.5
+ *   32000  2    3     96   320       47.75
+ *   44100  147  160   96   441       14111 / 294
+ *   96000  2    1     48   960       23.75
+ *
+ * The rnnoise compat path, fvad_pipeline_*, fvad_multi_* and the simulator
+ * stay 48 kHz. */
+typedef struct {
+  int rate;
+  int L, M;            /* rate / g and 48000 / g */
+  int taps_per_phase;  /* K */
+  int frame_out;       /* output samples per tick and channel */
+  double delay;        /* the filter's group delay in 48 kHz samples, (L K - 1) / (2 L) */
+} fvad_resample_out_desc;
+/* host only (no GPU).  FVAD_ERATE for a rate off the list (0 and 48000 too) */
+int fvad_resample_out_info(int rate, fvad_resample_out_desc *out);
+/* the [L][K] tap table; copies min(count, cap) floats (out may be NULL) and
+ * returns the count, 0 for a rate off the list */
+size_t fvad_resample_out_taps(int rate, float *out, size_t cap);
+/* One channel on the host, the arithmetic above (the kernel's mirror): in48 is
+ * n_ticks * 480 samples, out n_ticks * frame_out.  tail: the K - 1 samples
+ * before in48[0], read and replaced by the last K - 1 of this call's input
+ * (carry it to continue a stream); NULL: zeros, nothing kept. */
+int fvad_resample_out_host(int rate, const float *in48, size_t n_ticks, float *tail, float *out);
+/* denoised samples per tick and channel: frame_out, 480 on a plain engine */
+int fvad_engine_denoised_frame(const fvad_engine *e);
+/* average event time (ms) of a push's two output-resample launches
+ * (k_resample_out and the tail update behind it) and the pushes measured; a
+ * sync point.  denoised_rate engines only (FVAD_EINVAL otherwise). */
+int fvad_engine_resample_out_times(fvad_engine *e, double *ms_avg, int *n_runs);
 
 /* ------------------------------------------------------------------ */
 /* 3. Host mirror of the reference API (C++ above this ABI)             */
