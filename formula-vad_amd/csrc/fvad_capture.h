@@ -4,7 +4,9 @@
 //
 //   history ring  [s][c][H] f32: every input sample of the last `history`
 //                 samples of each stream, written by k_hist_append on the
-//                 stream that reads the push's device input
+//                 stream that reads the push's device input; or, for a capture
+//                 of the denoised rows, every denoised sample at the clip
+//                 rate, written by k_den_append on the engine stream
 //   capture pass  behind a push's machine pass on the side stream: k_cap_plan
 //                 (pending queues, due clips, pool offsets), k_cap_channel
 //                 (the lowest-RMS channel of each due clip), k_cap_copy (ring
@@ -63,6 +65,10 @@ struct CapAppendArgs {
   unsigned long long H;
   CapPos *pos;               // [s], owned by the appending stream
   CapPos *snap;              // [s] the positions after this push, for its capture pass
+  // a capture of the denoised rows (FVAD_CLIP_SOURCE_DENOISED): den set, pcm
+  // and pcm16 null, and everything above counts samples of the clip rate
+  const float *den;          // nullable: [t][s][c][frame], d_den or the output resampler's rows
+  int frame;                 // samples of a tick and channel: 480, or the clip rate / 100
 };
 
 struct CapPassArgs {
@@ -85,6 +91,12 @@ struct CapPassArgs {
   CapHeader *header;         // pinned
   unsigned long long pass, push;
   unsigned long long host_desc_read, host_pool_read;  // the host's read cursors when the pass was enqueued
+  // The clip rate 48000 L / M (1, 1 for the 48 kHz signals): pos, history, H
+  // and a clip's first / n count its samples, a segment's bounds go through
+  // cap::to_rate.  pool16: the pool of an s16 capture (pool is null then).
+  unsigned L, M;
+  int16_t *pool16;           // pinned, [pool_cap]
+  unsigned long long reserved;  // fvad_clip.reserved of every descriptor
 };
 
 struct CapSetArgs {  // the listed streams' position and base to value[i]; their pending clips dropped

@@ -3,7 +3,9 @@
 // k_hist_append / k_hist_advance run on the stream that reads a push's device
 // input: the first copies the valid ticks of every stream into the history
 // ring and only reads the streams' positions, the second advances them and
-// leaves the push's snapshot for its capture pass.
+// leaves the push's snapshot for its capture pass.  A capture of the denoised
+// rows appends with k_den_append on the engine stream instead, in samples of
+// the clip rate; an s16 capture copies with k_cap_copy_short.
 //
 // The capture pass runs on the side stream between a push's machine pass and
 // k_vadm_events: k_cap_plan, k_cap_channel, k_cap_copy, k_cap_publish.  The
@@ -56,19 +58,87 @@ __global__ void __launch_bounds__(kNT) k_hist_append(CapAppendArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// k_den_append: the denoised rows [t][s][c][n] (n = a.frame samples of
+// the clip rate) -> ring [s][c][H], the valid ticks only: the rows past
+// ticks_valid[s] hold zeros (k_resample_out) or an older push (d_den).  A
+// stream's ticks start at wpos, a multiple of n; H is a multiple of 4.
+//
+// A4 (n % 4 == 0: every rate but 44.1 kHz): rows and ring places are 16-byte
+// aligned, float4 by float4 as k_hist_append.
+//
+// Otherwise (n = 441): row R starts at float R n and lands at ring index
+// (wpos + t n) % H, each of any alignment, and a row may straddle the ring's
+// end.  A row is cut into quads that are aligned in the ring: item k covers
+// the row's samples j0 .. j0 + 3, j0 = 4 k - lead, lead = (wpos + t n) % 4,
+// so ring index (wpos + t n + j0) % H is a multiple of 4 and, H being one
+// too, the quad does not straddle the end.  A quad wholly inside the row is
+// one float4 store, from one float4 load where the row's place is aligned too
+// and from four loads otherwise; the row's head and tail quads go sample by
+// sample.
+// ---------------------------------------------------------------------------
+template <bool A4>
+__global__ void __launch_bounds__(kNT) k_den_append(CapAppendArgs a) {
+  const int n = a.frame;
+  const int items = A4 ? n / 4 : n / 4 + 2;  // quads of a row (the last may lie past it)
+  const long long total = (long long)a.n_ticks * a.n_streams * a.n_channels * items;
+  for (long long i = (long long)blockIdx.x * kNT + threadIdx.x; i < total; i += (long long)gridDim.x * kNT) {
+    const int k = (int)(i % items);
+    const long long row = i / items;  // (t * n_streams + s) * n_channels + c
+    long long r = row;
+    const int c = (int)(r % a.n_channels);
+    r /= a.n_channels;
+    const int s = (int)(r % a.n_streams), t = (int)(r / a.n_streams);
+    const int valid = a.ticks_valid ? a.ticks_valid[s] : a.n_ticks;
+    if (t >= valid) continue;
+    const float *src = a.den + row * n;
+    float *dst = a.hist + ((size_t)s * a.n_channels + c) * a.H;
+    const unsigned long long w0 = a.pos[s].wpos + (unsigned long long)t * n;  // ring place of the row's sample 0
+    if (A4) {
+      *reinterpret_cast<float4 *>(dst + (w0 + 4u * (unsigned)k) % a.H) = reinterpret_cast<const float4 *>(src)[k];
+      continue;
+    }
+    const int j0 = 4 * k - (int)(w0 & 3ull);
+    if (j0 >= n) continue;
+    if (j0 >= 0 && j0 + 4 <= n) {
+      float4 v;
+      if ((((unsigned long long)row * (unsigned)n + (unsigned)j0) & 3ull) == 0)
+        v = *reinterpret_cast<const float4 *>(src + j0);
+      else
+        v = make_float4(src[j0], src[j0 + 1], src[j0 + 2], src[j0 + 3]);
+      *reinterpret_cast<float4 *>(dst + (w0 + (unsigned)j0) % a.H) = v;
+    } else {
+      for (int j = j0 < 0 ? 0 : j0; j < j0 + 4 && j < n; j++) dst[(w0 + (unsigned)j) % a.H] = src[j];
+    }
+  }
+}
+
 __global__ void __launch_bounds__(kNT) k_hist_advance(CapAppendArgs a) {
   const int s = blockIdx.x * kNT + threadIdx.x;
   if (s >= a.n_streams) return;
   const int valid = a.ticks_valid ? a.ticks_valid[s] : a.n_ticks;
   CapPos p = a.pos[s];
-  p.pos += (unsigned long long)valid * kFrame;
-  p.wpos += (unsigned long long)valid * kFrame;
+  p.pos += (unsigned long long)valid * a.frame;
+  p.wpos += (unsigned long long)valid * a.frame;
   a.pos[s] = p;
   a.snap[s] = p;
 }
 
 hipError_t launch_hist_append(const CapAppendArgs &a, hipStream_t stream) {
   (void)hipGetLastError();
+  if (a.den) {  // a capture of the denoised rows
+    const bool a4 = a.frame % 4 == 0;
+    const long long total = (long long)a.n_ticks * a.n_streams * a.n_channels * (a4 ? a.frame / 4 : a.frame / 4 + 2);
+    const int grid = (int)std::min<long long>((total + kNT - 1) / kNT, 4096);
+    if (grid > 0) {
+      if (a4)
+        FVAD_KERNEL_TRY(k_den_append<true>, dim3(grid), dim3(kNT), 0, stream, a);
+      else
+        FVAD_KERNEL_TRY(k_den_append<false>, dim3(grid), dim3(kNT), 0, stream, a);
+    }
+    FVAD_KERNEL_TRY(k_hist_advance, dim3((a.n_streams + kNT - 1) / kNT), dim3(kNT), 0, stream, a);
+    return hipSuccess;
+  }
   const long long total = (long long)a.n_ticks * a.n_streams * a.n_channels * kRowQuads;
   const int grid = (int)std::min<long long>((total + kNT - 1) / kNT, 4096);
   if (grid > 0) {
@@ -139,8 +209,11 @@ __global__ void __launch_bounds__(kNT) k_cap_plan(CapPassArgs a) {
       for (int i = 0; i < cap::kQueue; i++) {
         if ((unsigned)i >= qn) continue;
         due[i] = q[i];
-        if (cap::due(due[i].to, P.pos, flush)) {
-          cut[i] = cap::cut(due[i].from, due[i].to, P.pos, P.base, a.history);
+        // the queue keeps the segment's own 48 kHz bounds (the descriptor's);
+        // due and cut see them in samples of the clip rate, as pos and base are
+        const unsigned long long from = cap::to_rate(due[i].from, a.L, a.M), to = cap::to_rate(due[i].to, a.L, a.M);
+        if (cap::due(to, P.pos, flush)) {
+          cut[i] = cap::cut(from, to, P.pos, P.base, a.history);
           len += cut[i].n;
           due_mask |= 1u << i;
           nd++;
@@ -312,6 +385,48 @@ __global__ void __launch_bounds__(kNT) k_cap_copy(CapPassArgs a) {
   }
 }
 
+// k_cap_copy_short: the same into the int16_t pool of an s16 capture, converted
+// on the way (cap::to_s16), two samples to a store.  Pair p of a clip holds
+// its samples 2 p - odd and 2 p - odd + 1, odd = the clip's first pool index
+// & 1, so a pair's first pool index is even until the pool wraps; a pair goes
+// out as one 32-bit store where both samples are the clip's, the place is
+// even and the pair does not straddle the pool's end, sample by sample
+// otherwise (a clip's first and last sample, the pair at the wrap, and the
+// pairs behind the wrap of a pool of odd length).
+__global__ void __launch_bounds__(kNT) k_cap_copy_short(CapPassArgs a) {
+  const unsigned n_work = a.state->n_work;
+  for (unsigned wi = blockIdx.y; wi < n_work; wi += gridDim.y) {
+    const CapWork w = a.work[wi];
+    if (w.n == 0 || w.channel < 0 || w.channel >= a.n_channels) continue;
+    const float *row = a.hist + ((size_t)w.stream * a.n_channels + w.channel) * a.H;
+    const unsigned long long p0 = w.pool_off % a.pool_cap, odd = p0 & 1ull;
+    const unsigned long long pairs = (w.n + odd + 1) / 2;
+    auto sample = [&](unsigned long long i) {  // the clip's sample i < n (widx + i < 2H)
+      unsigned long long src = w.widx + i;
+      if (src >= a.H) src -= a.H;
+      return cap::to_s16(row[src]);
+    };
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kNT + threadIdx.x; p < pairs;
+         p += (unsigned long long)gridDim.x * kNT) {
+      const unsigned long long hi = 2 * p + 1 - odd;  // the pair's second sample; its first is hi - 1
+      const bool has_lo = hi >= 1, has_hi = hi < w.n;
+      unsigned long long dst = p0 + (has_lo ? hi - 1 : 0ull);  // < 2 pool_cap (n <= pool_cap: cap::fits)
+      if (dst >= a.pool_cap) dst -= a.pool_cap;
+      if (has_lo && has_hi && !(dst & 1ull) && dst + 1 < a.pool_cap) {
+        const unsigned lo16 = (unsigned short)sample(hi - 1), hi16 = (unsigned short)sample(hi);
+        *reinterpret_cast<unsigned *>(a.pool16 + dst) = lo16 | hi16 << 16;
+      } else {
+        if (has_lo) a.pool16[dst] = sample(hi - 1);
+        if (has_hi) {
+          unsigned long long d1 = p0 + hi;
+          if (d1 >= a.pool_cap) d1 -= a.pool_cap;
+          a.pool16[d1] = sample(hi);
+        }
+      }
+    }
+  }
+}
+
 // k_cap_publish: the pass's descriptors and its header to pinned memory
 __global__ void __launch_bounds__(kNT) k_cap_publish(CapPassArgs a) {
   const CapState st = *a.state;
@@ -327,7 +442,7 @@ __global__ void __launch_bounds__(kNT) k_cap_publish(CapPassArgs a) {
     d.sample_to = w.to;
     d.first_sample = w.first;
     d.n_samples = w.n;
-    d.reserved = 0;
+    d.reserved = a.reserved;
     a.desc[(st.desc_wr0 + i) % a.desc_cap] = d;
   }
   if (threadIdx.x == 0) {
@@ -344,7 +459,10 @@ hipError_t launch_capture_pass(const CapPassArgs &a, hipStream_t stream) {
   (void)hipGetLastError();
   FVAD_KERNEL_TRY(k_cap_plan, dim3(1), dim3(kNT), 0, stream, a);
   FVAD_KERNEL_TRY(k_cap_channel, dim3(kChGrid), dim3(kNT), 0, stream, a);
-  FVAD_KERNEL_TRY(k_cap_copy, dim3(kCopyGridX, kCopyGridY), dim3(kNT), 0, stream, a);
+  if (a.pool16)
+    FVAD_KERNEL_TRY(k_cap_copy_short, dim3(kCopyGridX, kCopyGridY), dim3(kNT), 0, stream, a);
+  else
+    FVAD_KERNEL_TRY(k_cap_copy, dim3(kCopyGridX, kCopyGridY), dim3(kNT), 0, stream, a);
   FVAD_KERNEL_TRY(k_cap_publish, dim3(1), dim3(kNT), 0, stream, a);
   return hipSuccess;
 }

@@ -8,6 +8,8 @@
 // history), pos): `base` is the stream's first sample of this life (0, or the
 // position of its last reset or restore).  A due clip is cut to what is held.
 #pragma once
+#include <cmath>
+
 #include "fvad_exact.h"  // FVAD_HD
 
 namespace fvad {
@@ -25,6 +27,27 @@ struct Cut {  // what of a due clip is delivered: [first, first + n)
   unsigned long long first, n;
   unsigned flags;
 };
+
+// A capture of the denoised rows works in samples of the clip rate R = 48000
+// L / M (fvad_resample_core.h's describe_out; L = M = 1 for the 48 kHz
+// signals): 48 kHz sample x is covered from clip-rate sample ceil(x L / M) on,
+// so the segment [from, to) covers [to_rate(from), to_rate(to)), the r with
+// from <= r M / L < to.  x < 2^56 (L <= 147).  A stream's position, a multiple
+// of 480, maps exactly (480 L / M = R / 100), so a clip is due in the same
+// push in either unit: to_rate(to) <= pos L / M iff to <= pos.
+FVAD_HD inline unsigned long long to_rate(unsigned long long x, unsigned L, unsigned M) {
+  return (x * L + (M - 1)) / M;
+}
+
+// f32 -> 16-bit PCM: clamp(rint(x * 32768), -32768, 32767), ties to even (the
+// product is exact, a power of two), NaN -> 0
+FVAD_HD inline short to_s16(float x) {
+  float y = rintf(x * 32768.0f);
+  if (!(y == y)) return 0;
+  y = y < -32768.0f ? -32768.0f : y;
+  y = y > 32767.0f ? 32767.0f : y;
+  return (short)(int)y;
+}
 
 // the stream holds the clip's last sample (or a flush ends it now)
 FVAD_HD inline bool due(unsigned long long to, unsigned long long pos, bool flush) { return flush || to <= pos; }

@@ -45,6 +45,12 @@ fvad::CapPassArgs pass_args(const fvad_engine *e, const fvad::VadmArgs &v) {
   a.state = c.state.get();
   a.work = c.work.get();
   a.pool = c.dv_pool;
+  a.pool16 = c.dv_pool16;
+  a.L = c.L;
+  a.M = c.M;
+  a.reserved = c.source == FVAD_CLIP_SOURCE_INPUT && c.format == FVAD_CLIP_F32
+                   ? 0ull
+                   : (unsigned long long)c.rate | (unsigned long long)c.format << 32 | (unsigned long long)c.source << 40;
   a.pool_cap = c.pool_cap;
   a.desc = c.dv_desc;
   a.desc_cap = c.desc_cap;
@@ -81,11 +87,48 @@ int fvad::eng::capture_append(fvad_engine *e, const fvad::StagedArgs &a, int b, 
   p.H = c.H;
   p.pos = c.pos.get();
   p.snap = c.snap[b].get();
+  p.frame = fvad::kFrame;
   int rc;
   if (timed && (rc = c.at[b].begin(s))) return rc;
   HIP_TRY(fvad::launch_hist_append(p, s));
   if (timed && (rc = c.at[b].end(s))) return rc;
   return FVAD_OK;
+}
+
+// The stream that owns the positions and writes the ring: the input's reader,
+// or the engine stream for a capture of the denoised rows
+hipStream_t fvad::eng::capture_appender(const fvad_engine *e) {
+  return e->cap->source == FVAD_CLIP_SOURCE_DENOISED ? e->stream.get() : input_reader(e);
+}
+
+// k_den_append of the push being launched (FVAD_CLIP_SOURCE_DENOISED), on
+// the engine stream behind the push's last writer of the rows it reads --
+// k_resample_out, or the tail kernels without an output rate -- and ahead of
+// ev_buf_free[b]: it reads ticks buffer b, and the rows are single-buffered,
+// rewritten by the next push on this stream.  It waits for the capture pass of
+// the push two before, as capture_append does and for the same words.
+int fvad::eng::capture_append_den(fvad_engine *e, const fvad::StagedArgs &a, int b, bool timed) {
+  Capture &c = *e->cap;
+  const hipStream_t s = e->stream.get();
+  HIP_TRY(wait_event(s, c.ev_pass[b].get()));
+  fvad::CapAppendArgs p{};
+  p.den = denoised_source(e);
+  p.frame = c.frame;
+  p.ticks_valid = a.ticks_valid;
+  p.n_ticks = a.n_ticks;
+  p.n_streams = a.n_streams;
+  p.n_channels = a.n_channels;
+  p.hist = c.hist.get();
+  p.H = c.H;
+  p.pos = c.pos.get();
+  p.snap = c.snap[b].get();
+  // timed on every push without waiting, as the output resampler's launches
+  // ahead of it are (a host-fed push is never a sampled one)
+  (void)timed;
+  int rc;
+  if ((rc = c.at[b].collect(c.ms_sum[0], c.n_timed[0])) || (rc = c.at[b].begin(s))) return rc;
+  HIP_TRY(fvad::launch_hist_append(p, s));
+  return c.at[b].end(s);
 }
 
 // The capture pass of push `push` (parity b) on the side stream, behind its
@@ -147,9 +190,10 @@ int fvad::eng::capture_set_streams(fvad_engine *e, const int32_t *streams, const
     a.ids.n = std::min(fvad::kListMax, n - i0);
     for (int i = 0; i < a.ids.n; i++) {
       a.ids.id[i] = streams[i0 + i];
-      a.value[i] = samples ? samples[i0 + i] : 0;
+      // (a 48 kHz sample count, a multiple of 480, in samples of the clip rate)
+      a.value[i] = samples ? samples[i0 + i] / fvad::kFrame * (unsigned long long)c.frame : 0;
     }
-    HIP_TRY(fvad::launch_capture_set_pos(a, input_reader(e)));
+    HIP_TRY(fvad::launch_capture_set_pos(a, capture_appender(e)));
     HIP_TRY(fvad::launch_capture_drop(a, e->side));
   }
   return FVAD_OK;
@@ -167,8 +211,38 @@ int fvad::eng::capture_collect_timing(fvad_engine *e) {
 
 // All or nothing, as fvad_engine_attach_vadm: everything is made in a local
 // Capture that moves into the engine after the last step that can fail.
+extern "C" void fvad_capture_config_default(fvad_capture_config *c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->machine = 0;
+  c->history_sec = 10.0;
+  c->pool_samples = 0;
+  c->source = FVAD_CLIP_SOURCE_INPUT;
+  c->format = FVAD_CLIP_F32;
+}
+
 extern "C" int fvad_engine_enable_capture(fvad_engine *e, int machine, double history_sec, size_t pool_samples) {
+  fvad_capture_config c;
+  fvad_capture_config_default(&c);
+  c.machine = machine;
+  c.history_sec = history_sec;
+  c.pool_samples = pool_samples;
+  return fvad_engine_enable_capture_ex(e, &c);
+}
+
+extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_config *cc) {
   if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (!cc) return fail(FVAD_EINVAL, "null capture config");
+  const int machine = cc->machine;
+  const double history_sec = cc->history_sec;
+  size_t pool_samples = cc->pool_samples;
+  if (cc->source != FVAD_CLIP_SOURCE_INPUT && cc->source != FVAD_CLIP_SOURCE_DENOISED)
+    return fail(FVAD_EINVAL, "source must be FVAD_CLIP_SOURCE_INPUT or FVAD_CLIP_SOURCE_DENOISED");
+  if (cc->format != FVAD_CLIP_F32 && cc->format != FVAD_CLIP_S16)
+    return fail(FVAD_EINVAL, "format must be FVAD_CLIP_F32 or FVAD_CLIP_S16");
+  const bool den = cc->source == FVAD_CLIP_SOURCE_DENOISED, s16 = cc->format == FVAD_CLIP_S16;
+  if (den && !e->cfg.want_denoised)
+    return fail(FVAD_EINVAL, "a capture of the denoised rows needs an engine created with want_denoised");
   if (e->vadm.n == 0 || !e->events_on)
     return fail(FVAD_EINVAL, "clip capture needs fvad_engine_attach_vadm and fvad_engine_enable_events first");
   if (e->cap) return fail(FVAD_EINVAL, "capture already enabled");
@@ -187,15 +261,25 @@ extern "C" int fvad_engine_enable_capture(fvad_engine *e, int machine, double hi
   const size_t B = e->cfg.n_streams, C = e->cfg.n_channels;
   auto c = std::make_unique<Capture>();
   c->machine = machine;
-  c->history = (unsigned long long)std::floor(48000.0 * history_sec);
-  c->H = (c->history + (unsigned long long)e->cfg.max_ticks * fvad::kFrame + 3) & ~3ull;
+  c->source = cc->source;
+  c->format = cc->format;
+  if (den && e->ro) {  // the engine's denoised_rate: the rows k_resample_out writes
+    c->rate = e->ro->d.rate;
+    c->frame = e->ro->d.n_out;
+    c->L = (unsigned)e->ro->d.L;
+    c->M = (unsigned)e->ro->d.M;
+  }
+  // the ring: history and a whole push, in samples of the clip rate
+  c->history = (unsigned long long)std::floor((double)c->rate * history_sec);
+  c->H = (c->history + (unsigned long long)e->cfg.max_ticks * c->frame + 3) & ~3ull;
   c->pool_cap = pool_samples;
   c->desc_cap = std::max<size_t>(1024, 8 * B);
   if ((rc = fvad::make_dev(c->hist, B * C * (size_t)c->H)) || (rc = fvad::make_dev(c->pos, B)) ||
       (rc = fvad::make_dev(c->snap[0], B)) || (rc = fvad::make_dev(c->snap[1], B)) ||
       (rc = fvad::make_dev(c->pend, B * fvad::cap::kQueue)) || (rc = fvad::make_dev(c->pend_n, B)) ||
       (rc = fvad::make_dev(c->state, 1)) || (rc = fvad::make_dev(c->work, B * fvad::cap::kQueue)) ||
-      (rc = fvad::make_dev(c->flush, B)) || (rc = fvad::make_pinned(c->pool, c->pool_cap)) ||
+      (rc = fvad::make_dev(c->flush, B)) ||
+      (rc = s16 ? fvad::make_pinned(c->pool16, c->pool_cap) : fvad::make_pinned(c->pool, c->pool_cap)) ||
       (rc = fvad::make_pinned(c->desc, c->desc_cap)) ||
       (rc = fvad::make_pinned(c->hdr, (size_t)fvad_engine::kEvHeaders + 1)) || (rc = fvad::make_event(c->ev_pass[0])) ||
       (rc = fvad::make_event(c->ev_pass[1])))
@@ -203,13 +287,16 @@ extern "C" int fvad_engine_enable_capture(fvad_engine *e, int machine, double hi
   for (int k = 0; k < 2; k++)
     if ((rc = c->at[k].create()) || (rc = c->pt[k].create())) return rc;
   void *dv_pool = nullptr, *dv_desc = nullptr, *dv_hdr = nullptr;
-  if (hipHostGetDevicePointer(&dv_pool, c->pool.get(), 0) != hipSuccess ||
+  if (hipHostGetDevicePointer(&dv_pool, s16 ? (void *)c->pool16.get() : (void *)c->pool.get(), 0) != hipSuccess ||
       hipHostGetDevicePointer(&dv_desc, c->desc.get(), 0) != hipSuccess ||
       hipHostGetDevicePointer(&dv_hdr, c->hdr.get(), 0) != hipSuccess) {
     (void)hipGetLastError();
     return fail(FVAD_EDEVICE, "hipHostGetDevicePointer failed (clip capture)");
   }
-  c->dv_pool = static_cast<float *>(dv_pool);
+  if (s16)
+    c->dv_pool16 = static_cast<int16_t *>(dv_pool);
+  else
+    c->dv_pool = static_cast<float *>(dv_pool);
   c->dv_desc = static_cast<fvad::CapClip *>(dv_desc);
   c->dv_hdr = static_cast<fvad::CapHeader *>(dv_hdr);
   // the streams' positions: what each has consumed so far (the state record's
@@ -223,7 +310,7 @@ extern "C" int fvad_engine_enable_capture(fvad_engine *e, int machine, double hi
   }
   for (size_t s = 0; s < B; s++) {
     pos[s] = fvad::CapPos{};
-    pos[s].pos = pos[s].base = (unsigned long long)ticks[s] * fvad::kFrame;
+    pos[s].pos = pos[s].base = (unsigned long long)ticks[s] * c->frame;
   }
   if (hipMemcpy(c->pos.get(), pos.data(), B * sizeof(fvad::CapPos), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(c->snap[0].get(), pos.data(), B * sizeof(fvad::CapPos), hipMemcpyHostToDevice) != hipSuccess ||
@@ -241,9 +328,21 @@ extern "C" int fvad_engine_enable_capture(fvad_engine *e, int machine, double hi
   return FVAD_OK;
 }
 
-extern "C" int fvad_engine_poll_clip(fvad_engine *e, fvad_clip *info, float *pcm, size_t cap_samples, uint64_t *lost) {
+namespace {
+
+// fvad_engine_poll_clip / fvad_engine_poll_clip_s16: `pool` is the capture's
+// pool of this sample type, null when the capture delivers the other one
+template <typename Sample>
+int poll_any(fvad_engine *e, fvad_clip *info, Sample *pcm, size_t cap_samples, uint64_t *lost) {
   if (!e || !info || (cap_samples > 0 && !pcm)) return fail(FVAD_EINVAL, "invalid argument");
   if (!e->cap) return fail(FVAD_EINVAL, "capture not enabled");
+  const Sample *pool;
+  if constexpr (sizeof(Sample) == 2)
+    pool = e->cap->pool16.get();
+  else
+    pool = e->cap->pool.get();
+  if (!pool)
+    return fail(FVAD_EINVAL, "an s16 capture is read with fvad_engine_poll_clip_s16, an f32 capture with fvad_engine_poll_clip");
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (const int rc = events_retire(e, false)) return rc;
   Capture &c = *e->cap;
@@ -255,12 +354,43 @@ extern "C" int fvad_engine_poll_clip(fvad_engine *e, fvad_clip *info, float *pcm
   if (d.n_samples > c.pool_end - c.pool_read) return fail(FVAD_EDEVICE, "clip capture: descriptor past the pool's end");
   const size_t n = (size_t)d.n_samples, at = (size_t)(c.pool_read % c.pool_cap), head = std::min(n, c.pool_cap - at);
   if (n) {
-    std::memcpy(pcm, c.pool.get() + at, head * sizeof(float));
-    std::memcpy(pcm + head, c.pool.get(), (n - head) * sizeof(float));
+    std::memcpy(pcm, pool + at, head * sizeof(Sample));
+    std::memcpy(pcm + head, pool, (n - head) * sizeof(Sample));
   }
   c.pool_read += n;
   c.desc_read++;
   return 1;
+}
+
+}  // namespace
+
+extern "C" int fvad_engine_poll_clip(fvad_engine *e, fvad_clip *info, float *pcm, size_t cap_samples, uint64_t *lost) {
+  return poll_any(e, info, pcm, cap_samples, lost);
+}
+
+extern "C" int fvad_engine_poll_clip_s16(fvad_engine *e, fvad_clip *info, int16_t *pcm, size_t cap_samples,
+                                         uint64_t *lost) {
+  return poll_any(e, info, pcm, cap_samples, lost);
+}
+
+extern "C" int fvad_engine_clip_rate(const fvad_engine *e) { return e && e->cap ? e->cap->rate : 0; }
+
+extern "C" void fvad_pcm_f32_to_s16(const float *x, int16_t *q, size_t n) {
+  for (size_t i = 0; i < n; i++) q[i] = fvad::cap::to_s16(x[i]);
+}
+
+extern "C" int fvad_clip_range(int rate, uint64_t from48, uint64_t to48, uint64_t *first, uint64_t *end) {
+  unsigned L = 1, M = 1;
+  if (rate != 48000) {
+    fvad::rs::DescOut d{};
+    if (!fvad::rs::describe_out(rate, d)) return fail(FVAD_ERATE, "rate must be 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
+    L = (unsigned)d.L;
+    M = (unsigned)d.M;
+  }
+  if (to48 < from48) return fail(FVAD_EINVAL, "to48 < from48");
+  if (first) *first = fvad::cap::to_rate(from48, L, M);
+  if (end) *end = fvad::cap::to_rate(to48, L, M);
+  return FVAD_OK;
 }
 
 extern "C" int fvad_engine_capture_flush(fvad_engine *e, const int32_t *streams, int n) {

@@ -639,7 +639,7 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
     HIP_TRY(fvad::launch_prep(a, e->pstream, timed ? e->ev : nullptr));
     // clip capture: the push's input into the history ring, by the stream that
     // reads it, before ev_prep_done (and the caller's ev_in_free) are recorded
-    if (e->cap)
+    if (e->cap && e->cap->source == FVAD_CLIP_SOURCE_INPUT)
       if (const int rc = capture_append(e, a, b, timed)) return rc;
     HIP_TRY(hipEventRecord(e->ev_prep_done[b].get(), e->pstream));
     HIP_TRY(wait_event(e->stream.get(), e->ev_prep_done[b].get()));
@@ -694,6 +694,11 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
   // last writers of d_den (it reads ticks buffer b: ahead of ev_buf_free)
   if (e->ro)
     if (const int rr = resample_out_push(e, n_ticks, a.ticks_valid)) return rr;
+  // clip capture of the denoised rows: into the history ring behind their last
+  // writer (k_resample_out above, or the tail kernels), by the stream that
+  // owns them, ahead of ev_buf_free (it reads ticks buffer b)
+  if (e->cap && e->cap->source == FVAD_CLIP_SOURCE_DENOISED)
+    if (const int rc = capture_append_den(e, a, b, timed)) return rc;
   // every reader of buffer b (incl. the copy of ticks for k_vadm_hbm) is queued
   HIP_TRY(hipEventRecord(e->ev_buf_free[b].get(), e->stream.get()));
   e->buf_busy[b] = true;
@@ -764,6 +769,7 @@ int fvad::eng::fetch(fvad_engine *e, int n_ticks, fvad_outputs *o) {
     return rc;
   if (o->denoised) {
     if (!e->d_den) return fail(FVAD_EINVAL, "engine created without want_denoised");
+    if (!denoised_to_host(c)) return fail(FVAD_EINVAL, "want_denoised = 2 keeps the denoised rows on the device");
     if ((rc = cp(o->denoised, denoised_source(e), TB * c.n_channels * denoised_frame(e) * 4))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
@@ -780,6 +786,8 @@ extern "C" int fvad_engine_push_ex(fvad_engine *e, const float *pcm, int n_ticks
   if (!e || !pcm) return fail(FVAD_EINVAL, "null argument");
   const fvad_engine_config &c = e->cfg;
   if (n_ticks < 0 || n_ticks > c.max_ticks) return fail(FVAD_EINVAL, "n_ticks out of range [0, max_ticks]");
+  if (out && out->denoised && c.want_denoised == 2)  // (before anything is launched)
+    return fail(FVAD_EINVAL, "want_denoised = 2 keeps the denoised rows on the device");
   if (n_ticks == 0) return FVAD_OK;
   int rc = check_ticks(e, ticks_valid, n_ticks);
   if (rc) return rc;

@@ -35,6 +35,9 @@ namespace eng {
 inline int fail(int code, const std::string &msg) { return set_error(code, msg); }
 // the GRU stack on the matrix cores (configs[4]): split (k_pspecw + k_gru16) or fused (k_fused16)
 inline bool fp16_mode(int mode) { return mode == FVAD_MODE_FP16 || mode == FVAD_MODE_FP16_FUSED; }
+// want_denoised = 2 keeps the denoised rows on the device (for a capture of
+// them): computed as with 1, never copied to the host, no pinned slot buffer
+inline bool denoised_to_host(const fvad_engine_config &c) { return c.want_denoised && c.want_denoised != 2; }
 // a cross-stream wait (skipping the ones already complete measured no gain:
 // DESIGN §8 r4)
 inline hipError_t wait_event(hipStream_t stream, hipEvent_t ev) { return hipStreamWaitEvent(stream, ev, 0); }
@@ -90,8 +93,17 @@ namespace fvad {
 namespace eng {
 struct Capture {
   int machine = 0;
+  // What is recorded and how it is delivered (fvad_capture_config).  A
+  // capture of the denoised rows counts samples of the clip rate `rate` =
+  // 48000 L / M everywhere below (history, H, the positions, the pool), has
+  // `frame` = rate / 100 of them per tick, and appends on the engine stream.
+  int source = FVAD_CLIP_SOURCE_INPUT, format = FVAD_CLIP_F32;
+  int rate = 48000, frame = kFrame;
+  unsigned L = 1, M = 1;
   unsigned long long history = 0, H = 0;
   size_t pool_cap = 0, desc_cap = 0;
+  pinned_ptr<int16_t> pool16;         // the pool of an s16 capture (pool is null then)
+  int16_t *dv_pool16 = nullptr;
   dev_ptr<float> hist;                // [s][c][H]
   dev_ptr<CapPos> pos, snap[2];       // the appending stream's positions; their value after the push of each parity
   dev_ptr<cap::Pend> pend;            // [s][cap::kQueue]
@@ -428,6 +440,8 @@ int events_retire(fvad_engine *e, bool wait_oldest);
 int collect_vadm_timing(fvad_engine *e);
 // fvad_capture_host.cpp
 int capture_append(fvad_engine *e, const fvad::StagedArgs &a, int b, bool timed);
+int capture_append_den(fvad_engine *e, const fvad::StagedArgs &a, int b, bool timed);
+hipStream_t capture_appender(const fvad_engine *e);
 int capture_pass(fvad_engine *e, const fvad::VadmArgs &v, uint64_t push, int b, int slot, bool timed);
 int capture_retire(fvad_engine *e, uint64_t pass);
 int capture_reset(fvad_engine *e);

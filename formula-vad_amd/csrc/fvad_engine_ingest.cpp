@@ -246,7 +246,7 @@ int ensure_slots(fvad_engine *e, int i) {
     // windows_per_tick (up to 240 at fft_size 2): refuse configurations whose
     // slot would not be a sane pinned allocation (the streaming API only:
     // resident and push-from-host engines never allocate a slot)
-    const double slot = 4.0 * ((double)frames + (c.want_denoised ? (double)TB * C * denoised_frame(e) : 0.0) + 3.0 * TB +
+    const double slot = 4.0 * ((double)frames + (denoised_to_host(c) ? (double)TB * C * denoised_frame(e) : 0.0) + 3.0 * TB +
                                2.0 * TBW +
                                (double)TBW * C * c.n_bands);
     if (slot > 16.0 * (1ull << 30))
@@ -272,7 +272,7 @@ int ensure_slots(fvad_engine *e, int i) {
   if ((rc = host(sl.in, TB * C * input_frame(e))) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
       (rc = host(sl.ratio, TB)) || (rc = host(sl.wflag, TB)) || (rc = host(sl.wratio, TBW)) ||
       (rc = host(sl.wvad, TBW)) || (rc = host(sl.band, TBW * C * c.n_bands)) ||
-      (c.want_denoised && (rc = host(sl.den, TB * C * denoised_frame(e)))))
+      (denoised_to_host(c) && (rc = host(sl.den, TB * C * denoised_frame(e)))))
     return rc;
   if ((!sl.h2d && (rc = fvad::make_event(sl.h2d))) || (rc = fvad::make_event(sl.done))) return rc;
   return FVAD_OK;
@@ -408,7 +408,7 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   if ((rc = d2h(sl.vad.get(), e->d_vad.get(), TB * 4)) || (rc = d2h(sl.ratio.get(), e->d_ratio, TB * 4)) ||
       (rc = d2h(sl.wflag.get(), e->d_wflag, TB * 4)) || (rc = d2h(sl.wratio.get(), e->d_wratio, TBW * 4)) ||
       (rc = d2h(sl.wvad.get(), e->d_wvad, TBW * 4)) || (rc = d2h(sl.band.get(), e->d_band, TBW * c.n_channels * c.n_bands * 4)) ||
-      (c.want_denoised && (rc = d2h(sl.den.get(), denoised_source(e), bytes))))
+      (denoised_to_host(c) && (rc = d2h(sl.den.get(), denoised_source(e), bytes))))
     return rc;
   HIP_TRY(hipEventRecord(sl.done.get(), e->stream.get()));
   sl.pending = true;
@@ -456,7 +456,9 @@ extern "C" int fvad_engine_collect(fvad_engine *e, fvad_outputs *out, int *n_tic
   HIP_TRY(hipEventSynchronize(sl.done.get()));
   const size_t TB = (size_t)sl.n_ticks * c.n_streams, TBW = TB * e->wpt;
   if (out) {
-    if (out->denoised && !c.want_denoised) return fail(FVAD_EINVAL, "engine created without want_denoised");
+    if (out->denoised && !denoised_to_host(c))
+      return fail(FVAD_EINVAL, c.want_denoised ? "want_denoised = 2 keeps the denoised rows on the device"
+                                               : "engine created without want_denoised");
     auto cp = [](void *dst, const void *src, size_t n) {
       if (dst) std::memcpy(dst, src, n);
     };

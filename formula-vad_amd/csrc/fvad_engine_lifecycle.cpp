@@ -348,7 +348,7 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
       at[i] = (uint64_t)ticks * fvad::kFrame;
     }
     if ((rc = capture_set_streams(e, streams, at.data(), n))) return rc;
-    HIP_TRY(hipStreamSynchronize(input_reader(e)));
+    HIP_TRY(hipStreamSynchronize(capture_appender(e)));
     HIP_TRY(hipStreamSynchronize(e->side));
   }
   return FVAD_OK;

@@ -161,6 +161,22 @@ class Clip(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+CLIP_SOURCE_INPUT, CLIP_SOURCE_DENOISED = 0, 1  # fvad_capture_config.source
+CLIP_F32, CLIP_S16 = 0, 1                       # fvad_capture_config.format
+
+
+class CaptureConfig(C.Structure):
+    """fvad_capture_config (include/fvad.h)."""
+    _fields_ = [("machine", C.c_int), ("history_sec", C.c_double), ("pool_samples", C.c_size_t),
+                ("source", C.c_int), ("format", C.c_int)]
+
+    @classmethod
+    def default(cls):
+        c = cls()
+        lib().fvad_capture_config_default(C.byref(c))
+        return c
+
+
 class StatConfig(C.Structure):
     _fields_ = [("ignore_shorter_than_sec", C.c_float), ("extrude_start", C.c_float), ("extrude_end", C.c_float),
                 ("fill_gaps", C.c_float)]
@@ -262,6 +278,12 @@ SYMBOLS = [
     ("fvad_engine_poll_clip", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("fvad_engine_capture_flush", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("fvad_engine_capture_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("fvad_capture_config_default", None, [C.c_void_p]),
+    ("fvad_engine_enable_capture_ex", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fvad_engine_poll_clip_s16", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("fvad_engine_clip_rate", C.c_int, [C.c_void_p]),
+    ("fvad_pcm_f32_to_s16", None, [F32P, C.POINTER(C.c_int16), C.c_size_t]),
+    ("fvad_clip_range", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fvad_engine_set_debug", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("fvad_engine_debug_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("fvad_engine_share_streams", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
@@ -506,6 +528,23 @@ def resample_out_host(rate, y, tail=None):
     return out
 
 
+def pcm_f32_to_s16(x):
+    """fvad_pcm_f32_to_s16: clamp(rint(x * 32768), -32768, 32767), ties to even, NaN -> 0,
+    as an int16 array of x's shape -- an s16 capture's conversion (host only)."""
+    x = np.ascontiguousarray(x, np.float32)
+    q = np.zeros(x.shape, np.int16)
+    lib().fvad_pcm_f32_to_s16(fptr(x), q.ctypes.data_as(C.POINTER(C.c_int16)), x.size)
+    return q
+
+
+def clip_range(rate, from48, to48):
+    """fvad_clip_range: the samples [first, end) of a signal at rate that the 48 kHz
+    range [from48, to48) covers (host only)."""
+    a, b = C.c_uint64(), C.c_uint64()
+    _check(lib().fvad_clip_range(rate, from48, to48, C.byref(a), C.byref(b)), "fvad_clip_range")
+    return a.value, b.value
+
+
 class Engine:
     """Batched hot path for a partition of streams on one GPU."""
 
@@ -521,7 +560,9 @@ class Engine:
         for i, (lo, hi) in enumerate(bands):
             cfg.band_lo[i] = lo
             cfg.band_hi[i] = hi
-        cfg.want_denoised = int(want_denoised)
+        # "device": the denoised rows are computed and stay on the device, for a capture of
+        # them (enable_capture(source="denoised")); nothing of them is copied to the host
+        cfg.want_denoised = 2 if want_denoised == "device" else int(want_denoised)
         cfg.mode = {"staged": MODE_STAGED, "fused": MODE_FUSED, "fp16": MODE_FP16, "fp16_fused": MODE_FP16_FUSED,
                     "f32_fast": MODE_F32_FAST}[mode]
         cfg.use_denoiser = int(use_denoiser)
@@ -764,30 +805,52 @@ class Engine:
         _check(lib().fvad_engine_event_times(self.h, C.byref(ms), C.byref(n)), "fvad_engine_event_times")
         return ms.value, n.value
 
-    def enable_capture(self, machine=0, history_sec=10.0, pool_samples=0):
-        """Record machine's segments on the device (fvad_engine_enable_capture): after
+    def enable_capture(self, machine=0, history_sec=10.0, pool_samples=0, source="input", fmt="f32"):
+        """Record machine's segments on the device (fvad_engine_enable_capture[_ex]): after
         attach_vadm and enable_events; history_sec >= 4 of every stream's input is held,
-        pool_samples of finished clips between polls (0: the default, 64 Mi)."""
-        _check(lib().fvad_engine_enable_capture(self.h, machine, history_sec, pool_samples),
-               "fvad_engine_enable_capture")
+        pool_samples of finished clips between polls (0: the default, 64 Mi).
+        source="denoised": the engine's denoised rows at clip_rate() instead of its input
+        (want_denoised=True or "device"); fmt="s16": the clips as 16-bit PCM."""
+        if (source, fmt) == ("input", "f32"):
+            _check(lib().fvad_engine_enable_capture(self.h, machine, history_sec, pool_samples),
+                   "fvad_engine_enable_capture")
+        else:
+            c = CaptureConfig.default()
+            c.machine, c.history_sec, c.pool_samples = machine, history_sec, pool_samples
+            c.source = {"input": CLIP_SOURCE_INPUT, "denoised": CLIP_SOURCE_DENOISED}[source]
+            c.format = {"f32": CLIP_F32, "s16": CLIP_S16}[fmt]
+            _check(lib().fvad_engine_enable_capture_ex(self.h, C.byref(c)), "fvad_engine_enable_capture_ex")
+        self._clip_s16 = fmt == "s16"
+
+    def clip_rate(self):
+        """Samples per second of the captured clips (fvad_engine_clip_rate): 48000 for the
+        input, the engine's denoised rate for the denoised rows, 0 without capture."""
+        return lib().fvad_engine_clip_rate(self.h)
 
     def poll_clips(self):
-        """The finished clips, oldest first, as (descriptor dict, float32 samples); never
-        waits for the device.  The clips lost so far: capture_lost()."""
+        """The finished clips, oldest first, as (descriptor dict, samples) -- float32, or
+        int16 for an s16 capture; never waits for the device.  A non-zero `reserved` is
+        decoded into the keys rate, format and source beside it.  The clips lost so far:
+        capture_lost()."""
         out = []
         info, lost = Clip(), C.c_uint64()
-        buf = np.zeros(0, np.float32)
+        s16 = getattr(self, "_clip_s16", False)
+        poll, name, dtype = (lib().fvad_engine_poll_clip_s16, "fvad_engine_poll_clip_s16", np.int16) if s16 else \
+            (lib().fvad_engine_poll_clip, "fvad_engine_poll_clip", np.float32)
+        buf = np.zeros(0, dtype)
         while True:
-            rc = lib().fvad_engine_poll_clip(self.h, C.byref(info), buf.ctypes.data_as(C.c_void_p), buf.size,
-                                             C.byref(lost))
+            rc = poll(self.h, C.byref(info), buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(lost))
             if rc == -1 and info.n_samples > buf.size:  # FVAD_EINVAL: the clip is still queued, its size known
-                buf = np.zeros(int(info.n_samples), np.float32)
+                buf = np.zeros(int(info.n_samples), dtype)
                 continue
-            _check(min(rc, 0), "fvad_engine_poll_clip")
+            _check(min(rc, 0), name)
             self._clips_lost = lost.value
             if rc == 0:
                 return out
-            out.append((info.as_dict(), buf[: info.n_samples].copy()))
+            d = info.as_dict()
+            if d["reserved"]:
+                d.update(rate=d["reserved"] & 0xffffffff, format=d["reserved"] >> 32 & 0xff, source=d["reserved"] >> 40 & 0xff)
+            out.append((d, buf[: info.n_samples].copy()))
 
     def capture_lost(self):
         """Clips that lost their audio or their descriptor so far, as of the last poll_clips()."""

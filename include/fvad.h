@@ -111,7 +111,9 @@ typedef struct {
   int n_bands;          /* band sums to report per window, 1..4 */
   int band_lo[FVAD_MAX_BANDS]; /* inclusive FFT-B bin ranges (FFT.freqToBin) */
   int band_hi[FVAD_MAX_BANDS];
-  int want_denoised;    /* keep denoised PCM (VAD.zig temp_denoiser_segment) */
+  int want_denoised;    /* keep denoised PCM (VAD.zig temp_denoiser_segment); 2: keep it on the device only, for a
+                         * capture of it (fvad_engine_enable_capture_ex): computed as with 1, never copied to the
+                         * host -- no pinned slot buffer, and fvad_outputs.denoised is FVAD_EINVAL */
   int mode;             /* FVAD_MODE_STAGED (default), FVAD_MODE_FUSED, FVAD_MODE_FP16, FVAD_MODE_FP16_FUSED or
                          * FVAD_MODE_F32_FAST */
   int use_denoiser;     /* VAD.Config.use_denoiser (default 1).  0: fft_size frames of raw input go
@@ -715,7 +717,7 @@ typedef struct {
   uint64_t push;                    /* ordinal of the push whose machine pass completed the clip */
   uint64_t sample_from, sample_to;  /* the segment's */
   uint64_t first_sample, n_samples; /* what is delivered: [first_sample, first_sample + n_samples) */
-  uint64_t reserved;                /* 0 */
+  uint64_t reserved;                /* 0 for an INPUT / F32 capture; else rate | format << 32 | source << 40 (below) */
 } fvad_clip; /* 64 bytes, little endian, no padding */
 /* Start capturing machine `machine`'s segments (the reference records the main
  * machine, 0).  After fvad_engine_attach_vadm and fvad_engine_enable_events,
@@ -754,6 +756,64 @@ int fvad_engine_capture_flush(fvad_engine *e, const int32_t *streams, int n);
  * fvad_engine_clear_times: ms_avg[0] k_hist_append, ms_avg[1] the capture pass
  * (its four kernels); *n_runs (nullable): the timed passes.  Synchronises. */
 int fvad_engine_capture_times(fvad_engine *e, double *ms_avg, int *n_runs);
+
+/* Denoised clips, at the output rate, as f32 or 16-bit PCM.
+ * fvad_engine_enable_capture_ex is fvad_engine_enable_capture with a source
+ * and a format; the old call equals it with {machine, history_sec,
+ * pool_samples, INPUT, F32}, and everything said above holds for both.
+ *
+ * source DENOISED records the engine's denoised rows instead of its input: the
+ * denoised signal of a stream is the concatenation of its valid ticks' rows,
+ * the very values push / collect / fetch deliver, at the clip rate R =
+ * fvad_engine_clip_rate: the engine's denoised_rate, 48000 without one (INPUT:
+ * always 48000).  It needs want_denoised != 0 (FVAD_EINVAL otherwise); with
+ * want_denoised = 2 the rows never leave the device and only the clips cross
+ * to the host.  A bad source or format is FVAD_EINVAL; a failed call leaves
+ * the engine unchanged.
+ *
+ * Units.  sample_from and sample_to stay the segment's 48 kHz values;
+ * first_sample and n_samples count samples of the clip rate, sample r of a
+ * stream being row r / (R / 100), column r % (R / 100).  With R = 48000 L / M
+ * in lowest terms, the segment covers the r with sample_from <= r M / L <
+ * sample_to, [ceil(sample_from L / M), ceil(sample_to L / M)), which
+ * fvad_clip_range computes.  A stream at 48 kHz sample n is at n L / M
+ * clip-rate samples (exact: n is a multiple of 480), so a clip completes in
+ * the same push as an INPUT clip, and the engine holds [max(base L / M, n L /
+ * M - floor(R * history_sec)), n L / M) of it.  The flags keep their meaning.
+ * The output resampler's causal delay, (L K - 1) / (2 L) 48 kHz samples
+ * ("Output rate of the denoised PCM"), is NOT compensated:
+ * the clip holds the resampler's outputs of those indices, which lag the
+ * 48 kHz signal by that much; the segment's 2 s tail covers it.
+ * channel: fvad_recording_channel over exactly the delivered f32 samples of
+ * the source, before any conversion.
+ *
+ * format S16 delivers q = clamp(rint(x * 32768.0f), -32768, 32767), ties to
+ * even, NaN -> 0 (fvad_pcm_f32_to_s16, bit for bit), converted on the device
+ * as the clip is copied: read it with fvad_engine_poll_clip_s16; an F32
+ * capture is read with fvad_engine_poll_clip, and the other call is
+ * FVAD_EINVAL.  pool_samples counts samples in either format (an S16 pool
+ * takes half the pinned bytes). */
+#define FVAD_CLIP_SOURCE_INPUT 0    /* what fvad_engine_enable_capture records */
+#define FVAD_CLIP_SOURCE_DENOISED 1 /* the engine's denoised rows, at fvad_engine_clip_rate */
+#define FVAD_CLIP_F32 0
+#define FVAD_CLIP_S16 1
+typedef struct {
+  int machine;
+  double history_sec;
+  size_t pool_samples; /* as fvad_engine_enable_capture's */
+  int source, format;
+} fvad_capture_config;
+void fvad_capture_config_default(fvad_capture_config *c); /* machine 0, 10 s, 0, INPUT, F32 */
+int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_config *c);
+int fvad_engine_poll_clip_s16(fvad_engine *e, fvad_clip *info, int16_t *pcm, size_t cap_samples, uint64_t *lost);
+/* 48000 for INPUT; the denoised rate for DENOISED; 0 without capture */
+int fvad_engine_clip_rate(const fvad_engine *e);
+/* Host mirrors, no GPU: the S16 conversion, and the clip-rate samples
+ * [*first, *end) a 48 kHz range [from48, to48) covers at `rate` (the identity
+ * at 48000; FVAD_ERATE off the list of rates, FVAD_EINVAL for to48 < from48;
+ * from48, to48 < 2^56). */
+void fvad_pcm_f32_to_s16(const float *x, int16_t *q, size_t n);
+int fvad_clip_range(int rate, uint64_t from48, uint64_t to48, uint64_t *first, uint64_t *end);
 
 /* Several engines on one GPU (e.g. a GPU's streams split into sub-partitions
  * that push concurrently): e runs its k_prep3 (FVAD_SHARE_PREP) and / or its
