@@ -59,6 +59,7 @@ extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams,
   c->band_hi[0] = 64;
   c->want_denoised = 0;
   c->use_denoiser = 1;
+  c->input_rate_max = 0;
   c->denoised_rate = 0;
   c->input_rate = 0;
   c->want_spectrum = 0;
@@ -197,7 +198,8 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
                          sizeof(float) * (size_t)e->ring_len * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
   if (e->rs)  // (their owner, the prep stream, is idle: synchronised above)
     HIP_TRY(hipMemsetAsync(e->rs->tails.get(), 0,
-                           sizeof(float) * (size_t)(e->rs->d.K - 1) * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
+                           sizeof(float) * (size_t)resample_tail_words(e) * e->cfg.n_channels * e->cfg.n_streams,
+                           e->stream.get()));
   if (e->ro)
     HIP_TRY(hipMemsetAsync(e->ro->tails.get(), 0,
                            sizeof(float) * (size_t)(e->ro->d.K - 1) * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
@@ -248,9 +250,17 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   if (c.sample_rate != 48000) return fail(FVAD_ERATE, "only 48 kHz is supported (VAD.zig:101-104)");
   // input_rate: 0 or 48000 for none, or a rate k_resample brings to 48 kHz
   const bool resample = c.input_rate != 0 && c.input_rate != 48000;
+  // FVAD_INPUT_RATE_PER_STREAM: every stream its own rate, up to input_rate_max
+  const bool per_stream = c.input_rate == FVAD_INPUT_RATE_PER_STREAM;
   fvad::rs::Desc rd{};
-  if (resample && !fvad::rs::describe(c.input_rate, rd))
+  if (per_stream) {
+    if (fvad::rs::rate_index(c.input_rate_max) < 0)
+      return fail(FVAD_ERATE, "input_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000");
+  } else if (c.input_rate_max != 0) {
+    return fail(FVAD_ERATE, "input_rate_max is read only with input_rate = FVAD_INPUT_RATE_PER_STREAM");
+  } else if (resample && !fvad::rs::describe(c.input_rate, rd)) {
     return fail(FVAD_ERATE, "input_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
+  }
   // denoised_rate: 0 or 48000 for the 48 kHz signal, or a rate k_resample_out brings it to
   const bool resample_out = c.denoised_rate != 0 && c.denoised_rate != 48000;
   fvad::rs::DescOut od{};
@@ -426,6 +436,8 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   if (resample) {
     e->rs.reset(new Resample());
     e->rs->d = rd;
+    e->rs->ps = per_stream;
+    e->rs->rate_max = c.input_rate_max;
     if ((rc = resample_make(e))) return bail(rc);
   }
   if (resample_out) {
@@ -794,7 +806,7 @@ extern "C" int fvad_engine_push_ex(fvad_engine *e, const float *pcm, int n_ticks
   std::vector<int32_t> tt;
   if ((rc = tail_ticks(e, ticks_valid, last_tick_samples, n_ticks, tt))) return rc;
   HIP_TRY(hipSetDevice(c.device));
-  const size_t bytes = (size_t)n_ticks * c.n_streams * c.n_channels * input_frame(e) * sizeof(float);
+  const size_t bytes = push_samples(e, n_ticks) * sizeof(float);
   // staged: the inputs go through the prep stream (ticks buffer b is free
   // once push k-2 finished)
   hipStream_t cs = e->stream.get();

@@ -145,6 +145,38 @@ struct Resample {
   int slot = 0;
   double ms_sum = 0;
   int n_timed = 0;
+  // Per-stream rates (input_rate = FVAD_INPUT_RATE_PER_STREAM; DESIGN.md
+  // section 7, "Per-stream rates"); none of it on a fixed-rate engine.  d,
+  // taps stay empty; tails are [s][c][rs::kMaxTail]; raw holds max_ticks * B *
+  // C * rate_max / 100 words.
+  bool ps = false;
+  int rate_max = 0;
+  rs::Desc dr[rs::kPsRates]{};          // by rate index (48000: the identity)
+  dev_ptr<float> taps_r[rs::kPsRates];  // the tables of the rates up to rate_max (none at 48000)
+  // what the next submitted push uses: each stream's rate index, the layout
+  // (fvad_input_layout) and the streams by rate; gen counts their changes
+  std::vector<int> ridx, lists;
+  std::vector<long long> offsets;  // [B + 1]
+  int list_at[rs::kPsRates + 1] = {};
+  uint64_t gen = 1;
+  // The device tables of the raw buffer of each parity, [offsets (B + 1) |
+  // rate_idx (B) | lists (B)] (the latter two as int), and the generation
+  // they hold.  A push whose parity's tables are stale copies them from the
+  // next pinned staging row on the resample stream, ahead of its launches:
+  // stream order keeps an in-flight push's tables until its kernels are
+  // done.  stage_ev[i]: the copy out of row i, waited for only should the ring
+  // come round to a row whose copy has not run (more than kStage table copies
+  // queued: not with submit / collect, FVAD_MAX_IN_FLIGHT pushes deep)
+  static constexpr int kStage = 8;
+  dev_ptr<long long> tab[2];
+  uint64_t tab_gen[2] = {0, 0};
+  pinned_ptr<long long> stage;
+  event_ptr stage_ev[kStage];
+  bool stage_used[kStage] = {};
+  int stage_next = 0;
+  size_t tab_words() const { return offsets.size() + (offsets.size() - 1); }  // (2 B ints are B words)
+  int frame(int s) const { return dr[ridx[s]].n_in; }
+  long long tick_len() const { return offsets.back(); }
 };
 
 // The denoised PCM at another rate (fvad_engine_config.denoised_rate;
@@ -421,6 +453,14 @@ int tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, const int32_t *
 // input resampling: samples per tick and channel of a push, where its H2D
 // copy goes, the stream that owns the tails, and the push's resample launches
 int input_frame(const fvad_engine *e);
+// per-stream rates: the largest frame (what the staging is sized by) and the
+// samples of a push of n_ticks in the current layout
+int input_frame_max(const fvad_engine *e);
+size_t push_samples(const fvad_engine *e, int n_ticks);
+// words of a row's tail: K - 1, rs::kMaxTail with per-stream rates
+int resample_tail_words(const fvad_engine *e);
+// per-stream rates: the layout and the lists of the current ridx (gen advances)
+void resample_relayout(fvad_engine *e);
 void *input_target(const fvad_engine *e);
 hipStream_t resample_stream(const fvad_engine *e);
 int resample_make(fvad_engine *e);

@@ -40,6 +40,41 @@ int fvad::eng::release_input(fvad_engine *e) {
 // ---------------------------------------------------------------------------
 int fvad::eng::input_frame(const fvad_engine *e) { return e->rs ? e->rs->d.n_in : fvad::kFrame; }
 
+int fvad::eng::input_frame_max(const fvad_engine *e) {
+  return e->rs && e->rs->ps ? e->rs->rate_max / 100 : input_frame(e);
+}
+
+size_t fvad::eng::push_samples(const fvad_engine *e, int n_ticks) {
+  if (e->rs && e->rs->ps) return (size_t)n_ticks * (size_t)e->rs->tick_len();
+  return (size_t)n_ticks * e->cfg.n_streams * e->cfg.n_channels * input_frame(e);
+}
+
+int fvad::eng::resample_tail_words(const fvad_engine *e) { return e->rs->ps ? fvad::rs::kMaxTail : e->rs->d.K - 1; }
+
+// fvad_input_layout over rate indices (all valid)
+static void layout_of_indices(const int *ridx, int n_streams, int n_channels, long long *offsets) {
+  long long o = 0;
+  for (int s = 0; s < n_streams; s++) {
+    offsets[s] = o;
+    o += (long long)n_channels * (fvad::rs::index_rate(ridx[s]) / 100);
+  }
+  offsets[n_streams] = o;
+}
+
+void fvad::eng::resample_relayout(fvad_engine *e) {
+  Resample &r = *e->rs;
+  const int B = e->cfg.n_streams;
+  layout_of_indices(r.ridx.data(), B, e->cfg.n_channels, r.offsets.data());
+  int n = 0;
+  for (int i = 0; i < fvad::rs::kPsRates; i++) {
+    r.list_at[i] = n;
+    for (int s = 0; s < B; s++)
+      if (r.ridx[s] == i) r.lists[n++] = s;
+  }
+  r.list_at[fvad::rs::kPsRates] = n;
+  r.gen++;
+}
+
 // where the H2D copy of the push about to launch goes (after input_buffer)
 void *fvad::eng::input_target(const fvad_engine *e) {
   return e->rs ? static_cast<void *>(e->rs->raw[e->in_next].get()) : static_cast<void *>(e->d_pcm);
@@ -56,6 +91,32 @@ hipStream_t fvad::eng::resample_stream(const fvad_engine *e) {
 int fvad::eng::resample_make(fvad_engine *e) {
   Resample &r = *e->rs;
   const fvad_engine_config &c = e->cfg;
+  if (r.ps) {
+    // the tables of every rate up to rate_max, each stream at rate_max, the
+    // raw staging and the slots sized by it
+    const size_t B = c.n_streams, rows = B * c.n_channels, raw = (size_t)c.max_ticks * rows * (r.rate_max / 100);
+    int rc;
+    for (int i = 0; i < fvad::rs::kPsRates; i++) {
+      fvad::rs::describe_ps(fvad::rs::index_rate(i), r.dr[i]);
+      if (i == fvad::rs::kPsIndex48 || r.dr[i].rate > r.rate_max) continue;
+      const std::vector<float> &taps = fvad::resample_table(r.dr[i]);
+      if ((rc = fvad::make_dev(r.taps_r[i], taps.size()))) return rc;
+      HIP_TRY(hipMemcpy(r.taps_r[i].get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    r.ridx.assign(B, fvad::rs::rate_index(r.rate_max));
+    r.lists.resize(B);
+    r.offsets.resize(B + 1);
+    resample_relayout(e);
+    if ((rc = fvad::make_dev(r.tails, rows * fvad::rs::kMaxTail)) || (rc = fvad::make_dev(r.raw[0], raw)) ||
+        (rc = fvad::make_dev(r.raw[1], raw)) || (rc = fvad::make_dev(r.tab[0], r.tab_words())) ||
+        (rc = fvad::make_dev(r.tab[1], r.tab_words())) ||
+        (rc = fvad::make_pinned(r.stage, (size_t)Resample::kStage * r.tab_words())) || (rc = r.tm[0].create()) ||
+        (rc = r.tm[1].create()))
+      return rc;
+    for (fvad::event_ptr &ev : r.stage_ev)
+      if ((rc = fvad::make_event(ev))) return rc;
+    return FVAD_OK;
+  }
   const std::vector<float> &taps = fvad::resample_table(r.d);
   const size_t rows = (size_t)c.n_streams * c.n_channels;
   int rc;
@@ -70,8 +131,60 @@ int fvad::eng::resample_make(fvad_engine *e) {
 
 // the resample launches of the push about to launch, timed without waiting
 // (a sample still running when its timer comes round again is dropped)
+namespace {
+// the tables of the push's parity, when a change of rates has overtaken them
+int resample_tables(fvad_engine *e, int ib, hipStream_t st) {
+  Resample &r = *e->rs;
+  if (r.tab_gen[ib] == r.gen) return FVAD_OK;
+  const int B = e->cfg.n_streams, i = r.stage_next;
+  r.stage_next = (i + 1) % Resample::kStage;
+  if (r.stage_used[i]) HIP_TRY(hipEventSynchronize(r.stage_ev[i].get()));  // (complete long ago: see Resample)
+  long long *row = r.stage.get() + (size_t)i * r.tab_words();
+  std::memcpy(row, r.offsets.data(), sizeof(long long) * (size_t)(B + 1));
+  int *ints = reinterpret_cast<int *>(row + B + 1);
+  std::memcpy(ints, r.ridx.data(), sizeof(int) * (size_t)B);
+  std::memcpy(ints + B, r.lists.data(), sizeof(int) * (size_t)B);
+  HIP_TRY(hipMemcpyAsync(r.tab[ib].get(), row, r.tab_words() * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(r.stage_ev[i].get(), st));
+  r.stage_used[i] = true;
+  r.tab_gen[ib] = r.gen;
+  return FVAD_OK;
+}
+
+int resample_push_ps(fvad_engine *e, int n_ticks, const int *d_ticks) {
+  Resample &r = *e->rs;
+  const int ib = e->in_next, B = e->cfg.n_streams;
+  hipStream_t st = resample_stream(e);
+  int rc;
+  if ((rc = resample_tables(e, ib, st))) return rc;
+  fvad::ResamplePsPush p{};
+  p.raw = r.raw[ib].get();
+  p.tails = r.tails.get();
+  p.ticks_valid = d_ticks;
+  p.out = e->d_pcm;
+  p.n_streams = B;
+  p.n_channels = e->cfg.n_channels;
+  p.n_ticks = n_ticks;
+  p.in16 = r.in16;
+  p.offsets = r.tab[ib].get();
+  p.rate_idx = reinterpret_cast<const int *>(r.tab[ib].get() + B + 1);
+  p.lists = p.rate_idx + B;
+  p.tick_len = r.tick_len();
+  for (int i = 0; i <= fvad::rs::kPsRates; i++) p.list_at[i] = r.list_at[i];
+  for (int i = 0; i < fvad::rs::kPsRates; i++) {
+    p.taps[i] = r.taps_r[i].get();
+    p.d[i] = r.dr[i];
+  }
+  EventTimer &tm = r.tm[r.slot ^= 1];
+  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
+  HIP_TRY(fvad::launch_resample_ps(p, st));
+  return tm.end(st);
+}
+}  // namespace
+
 int fvad::eng::resample_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
   Resample &r = *e->rs;
+  if (r.ps) return resample_push_ps(e, n_ticks, d_ticks);
   fvad::ResampleArgs a{};
   a.raw = r.raw[e->in_next].get();
   a.taps = r.taps.get();
@@ -91,7 +204,70 @@ int fvad::eng::resample_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
   return tm.end(st);
 }
 
-extern "C" int fvad_engine_input_frame(const fvad_engine *e) { return e ? input_frame(e) : FVAD_EINVAL; }
+extern "C" int fvad_engine_input_frame(const fvad_engine *e) {
+  if (!e) return FVAD_EINVAL;
+  if (e->rs && e->rs->ps) return fail(FVAD_EINVAL, "a per-stream engine has no single frame: fvad_engine_input_layout");
+  return input_frame(e);
+}
+
+// ---------------------------------------------------------------------------
+// Per-stream rates (FVAD_INPUT_RATE_PER_STREAM)
+// ---------------------------------------------------------------------------
+extern "C" int fvad_input_layout(const int *rates, int n_streams, int n_channels, int64_t *offsets) {
+  if (!rates || !offsets || n_streams < 1 || n_channels < 1 || n_channels > FVAD_MAX_CHANNELS)
+    return fail(FVAD_EINVAL, "fvad_input_layout: rates, offsets, n_streams >= 1 and 1 <= n_channels <= 8 required");
+  for (int s = 0; s < n_streams; s++)
+    if (fvad::rs::rate_index(rates[s]) < 0)
+      return fail(FVAD_ERATE, "a stream's rate must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000");
+  int64_t o = 0;
+  for (int s = 0; s < n_streams; s++) {
+    offsets[s] = o;
+    o += (int64_t)n_channels * (rates[s] / 100);
+  }
+  offsets[n_streams] = o;
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_stream_rates(const fvad_engine *e, int *rates) {
+  if (!e || !rates) return fail(FVAD_EINVAL, "null argument");
+  if (!e->rs || !e->rs->ps) return fail(FVAD_EINVAL, "not a per-stream engine (FVAD_INPUT_RATE_PER_STREAM)");
+  for (int s = 0; s < e->cfg.n_streams; s++) rates[s] = fvad::rs::index_rate(e->rs->ridx[s]);
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_input_layout(const fvad_engine *e, int64_t *offsets) {
+  if (!e || !offsets) return fail(FVAD_EINVAL, "null argument");
+  if (!e->rs || !e->rs->ps) return fail(FVAD_EINVAL, "not a per-stream engine (FVAD_INPUT_RATE_PER_STREAM)");
+  for (size_t i = 0; i < e->rs->offsets.size(); i++) offsets[i] = e->rs->offsets[i];
+  return FVAD_OK;
+}
+
+// The host's rates and layout change here; the device tables follow ahead of
+// the next push (resample_tables), and the listed tails are cleared on the
+// resample stream, behind the pushes already queued.  Nothing waits.
+extern "C" int fvad_engine_set_stream_rates(fvad_engine *e, const int *streams, int n, const int *rates) {
+  if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (!e->rs || !e->rs->ps) return fail(FVAD_EINVAL, "not a per-stream engine (FVAD_INPUT_RATE_PER_STREAM)");
+  if (const int rc = check_stream_list(e, streams, n)) return rc;
+  if (n == 0) return FVAD_OK;
+  if (!rates) return fail(FVAD_EINVAL, "null rates");
+  Resample &r = *e->rs;
+  for (int i = 0; i < n; i++)
+    if (fvad::rs::rate_index(rates[i]) < 0 || rates[i] > r.rate_max)
+      return fail(FVAD_ERATE, "a stream's rate must be a listed rate or 48000, at most input_rate_max");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  for (int i = 0; i < n; i++) r.ridx[streams[i]] = fvad::rs::rate_index(rates[i]);
+  resample_relayout(e);
+  fvad::ResampleClearArgs ra{};
+  ra.tails = r.tails.get();
+  ra.row_words = e->cfg.n_channels * fvad::rs::kMaxTail;
+  for (int i0 = 0; i0 < n; i0 += fvad::kListMax) {
+    ra.ids.n = std::min(fvad::kListMax, n - i0);
+    std::memcpy(ra.ids.id, streams + i0, sizeof(int) * (size_t)ra.ids.n);
+    HIP_TRY(fvad::launch_resample_clear(ra, resample_stream(e)));
+  }
+  return FVAD_OK;
+}
 
 extern "C" int fvad_engine_fetch_input(fvad_engine *e, int n_ticks, float *pcm48) {
   if (!e || !pcm48) return fail(FVAD_EINVAL, "null argument");
@@ -195,7 +371,8 @@ int fvad::eng::tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, cons
   const int B = e->cfg.n_streams;
   if (e->rs) {  // whole ticks only: the resampler's phase restarts with every tick
     for (int s = 0; s < B; s++)
-      if (last[s] != e->rs->d.n_in) return fail(FVAD_EINVAL, "a resampling engine consumes whole ticks only");
+      if (last[s] != (e->rs->ps ? e->rs->frame(s) : e->rs->d.n_in))
+        return fail(FVAD_EINVAL, "a resampling engine consumes whole ticks only");
     return FVAD_OK;
   }
   bool partial = false;
@@ -269,7 +446,7 @@ int ensure_slots(fvad_engine *e, int i) {
   // what an earlier, partly failed call allocated is kept and reused
   auto host = [](auto &p, size_t count) { return p ? FVAD_OK : fvad::make_pinned(p, count); };
   int rc;
-  if ((rc = host(sl.in, TB * C * input_frame(e))) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
+  if ((rc = host(sl.in, TB * C * input_frame_max(e))) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
       (rc = host(sl.ratio, TB)) || (rc = host(sl.wflag, TB)) || (rc = host(sl.wratio, TBW)) ||
       (rc = host(sl.wvad, TBW)) || (rc = host(sl.band, TBW * C * c.n_bands)) ||
       (denoised_to_host(c) && (rc = host(sl.den, TB * C * denoised_frame(e)))))
@@ -282,7 +459,7 @@ int ensure_slots(fvad_engine *e, int i) {
 // (a resampling engine has its raw buffers instead of the staging buffer)
 int ensure_slots16(fvad_engine *e, int i) {
   const fvad_engine_config &c = e->cfg;
-  const size_t n = (size_t)c.max_ticks * c.n_streams * c.n_channels * input_frame(e);
+  const size_t n = (size_t)c.max_ticks * c.n_streams * c.n_channels * input_frame_max(e);
   auto &sl = e->slots[i];
   int rc;
   if ((!sl.in16 && (rc = fvad::make_pinned(sl.in16, n))) ||
@@ -340,7 +517,7 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   if (sl.pending) return fail(FVAD_EINVAL, "FVAD_MAX_IN_FLIGHT pushes in flight: collect the oldest one first");
   const size_t B = c.n_streams, TB = (size_t)n_ticks * B, TBW = TB * e->wpt;
   // (n_samples: the input's, at the engine's input rate; bytes: the denoised output's)
-  const size_t n_samples = TB * c.n_channels * input_frame(e), bytes = TB * c.n_channels * denoised_frame(e) * sizeof(float);
+  const size_t n_samples = push_samples(e, n_ticks), bytes = TB * c.n_channels * denoised_frame(e) * sizeof(float);
   Sample *slot_in;
   if constexpr (k16)
     slot_in = sl.in16.get();

@@ -41,7 +41,8 @@ uint64_t config_hash_of(const fvad_engine *e) {
       h = fnv_add(h, v);
   }
   // a resampling engine's rate; an engine of 48 kHz input hashes what it always did
-  if (e->rs) h = fnv_add(h, e->rs->d.rate);
+  // (per-stream rates: the marker, not input_rate_max -- a record carries its stream's rate)
+  if (e->rs) h = fnv_add(h, e->rs->ps ? (int)FVAD_INPUT_RATE_PER_STREAM : e->rs->d.rate);
   // likewise the rate of the denoised PCM, when it is not the 48 kHz signal
   if (e->ro) h = fnv_add(h, e->ro->d.rate);
   return h;
@@ -49,7 +50,7 @@ uint64_t config_hash_of(const fvad_engine *e) {
 
 fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
   return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap,
-                           e->rs ? e->rs->d.K - 1 : 0, e->ro ? e->ro->d.K - 1 : 0);
+                           e->rs ? resample_tail_words(e) : 0, e->ro ? e->ro->d.K - 1 : 0, e->rs && e->rs->ps);
 }
 
 fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
@@ -71,7 +72,7 @@ fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   h.config_hash = config_hash_of(e);
   h.model_hash = e->model_hash;
   h.sample_rate = (uint32_t)e->cfg.sample_rate;
-  h.reserved[0] = e->rs ? (uint32_t)e->rs->d.rate : 0u;
+  h.reserved[0] = !e->rs ? 0u : e->rs->ps ? 0xFFFFFFFFu : (uint32_t)e->rs->d.rate;
   h.reserved[1] = e->ro ? (uint32_t)e->ro->d.rate : 0u;
   return h;
 }
@@ -215,7 +216,7 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
     if (e->rs) {  // the resampler's tails, on the stream k_resample runs on
       fvad::ResampleClearArgs ra{};
       ra.tails = e->rs->tails.get();
-      ra.row_words = e->cfg.n_channels * (e->rs->d.K - 1);
+      ra.row_words = e->cfg.n_channels * resample_tail_words(e);
       ra.ids = ca.ids;
       HIP_TRY(fvad::launch_resample_clear(ra, resample_stream(e)));
     }
@@ -284,6 +285,13 @@ extern "C" int fvad_engine_save_streams(fvad_engine *e, const int32_t *streams, 
   }
   HIP_TRY(hipMemcpyAsync(static_cast<char *>(blob) + sizeof(h), e->d_blob.get(), body, hipMemcpyDeviceToHost, e->stream.get()));
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
+  if (e->rs && e->rs->ps) {  // each record's rate (the gather leaves these words alone)
+    const long long o_rate = layout_of(e, (int)h.seg_capacity).o_rate;
+    for (int i = 0; i < n; i++) {
+      const uint32_t w[4] = {(uint32_t)fvad::rs::index_rate(e->rs->ridx[streams[i]]), 0u, 0u, 0u};
+      std::memcpy(static_cast<char *>(blob) + sizeof(h) + (size_t)i * (size_t)h.stream_bytes + 4 * (size_t)o_rate, w, sizeof(w));
+    }
+  }
   std::memcpy(blob, &h, sizeof(h));
   return FVAD_OK;
 }
@@ -322,6 +330,16 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
     std::memcpy(head.data(), body + r * (size_t)h.stream_bytes, (size_t)h.stream_bytes);
     if ((rc = check_record(e, lay, head.data()))) return rc;
   }
+  std::vector<int> rec_ridx;  // per-stream rates: the records' rates, checked before a device byte is written
+  if (e->rs && e->rs->ps)
+    for (int i = 0; i < n; i++) {
+      uint32_t rate;
+      std::memcpy(&rate, body + (size_t)(index ? index[i] : i) * (size_t)h.stream_bytes + 4 * (size_t)lay.o_rate, sizeof(rate));
+      const int ri = rate <= 96000u ? fvad::rs::rate_index((int)rate) : -1;
+      if (ri < 0) return fail(FVAD_EFORMAT, "stream record: not a listed rate");
+      if ((int)rate > e->rs->rate_max) return fail(FVAD_EFORMAT, "stream record: its rate exceeds this engine's input_rate_max");
+      rec_ridx.push_back(ri);
+    }
   if ((rc = fvad_engine_sync(e))) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t bytes = (size_t)h.count * (size_t)h.stream_bytes;
@@ -337,6 +355,10 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
     HIP_TRY(fvad::launch_stream_scatter(a, e->stream.get()));
   }
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
+  if (!rec_ridx.empty()) {  // the slots take their records' rates: the layout of the next push follows
+    for (int i = 0; i < n; i++) e->rs->ridx[streams[i]] = rec_ridx[i];
+    resample_relayout(e);
+  }
   if (e->cap) {
     // the slots continue at their records' sample counts with nothing held
     // (a blob carries no audio and no pending clip)

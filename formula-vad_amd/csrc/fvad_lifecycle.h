@@ -44,16 +44,20 @@ static_assert(st::kWords % 64 == 0 && st::kPitch == 0 && kPitchBuf % 4 == 0 && s
 //                               segments [pad4(6 * seg_cap)] (min(n_segs, seg_cap) stored, zeros after)
 //   o_rs + c * rs_pad           a resampling engine only (rs_tail = K - 1 > 0): channel c's resampler
 //                               tail, its last rs_tail input samples, zeros after
+//                               (per-stream rates: rs_tail = rs::kMaxTail, the stream's own K - 1 at
+//                               the front of each, and 4 words behind the last: the stream's rate,
+//                               then zeros -- o_rate, written and read by the host)
 //   o_ro + c * ro_pad           an engine with denoised_rate only (ro_tail = K - 1 > 0), behind the
 //                               input tails: channel c's output resampler tail, its last ro_tail
 //                               denoised samples, zeros after
 struct BlobLayout {
   int n_channels, n_mach, seg_cap, fft_size, use_denoiser, rs_tail, ro_tail;
   long long pend_pad, o_ring, o_mach[kMaxBandCfg], rs_pad, o_rs, ro_pad, o_ro, words;
+  long long o_rate;  // per-stream rates only (0 otherwise)
 };
 constexpr long long pad4(long long x) { return (x + 3) & ~3LL; }
 inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, const VadmArgs &v, int seg_cap,
-                              int rs_tail = 0, int ro_tail = 0) {
+                              int rs_tail = 0, int ro_tail = 0, bool rs_rate = false) {
   BlobLayout L{};
   L.n_channels = n_channels;
   L.n_mach = v.n;
@@ -72,6 +76,10 @@ inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, co
   L.rs_pad = pad4(rs_tail);
   L.o_rs = o;
   o += (long long)n_channels * L.rs_pad;
+  if (rs_rate) {
+    L.o_rate = o;
+    o += 4;
+  }
   L.ro_tail = ro_tail;
   L.ro_pad = pad4(ro_tail);
   L.o_ro = o;

@@ -32,10 +32,60 @@ struct ResampleArgs {
 // valid tick, so the replacing is a launch of its own, in stream order.
 hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream);
 
-// fvad_engine_reset_streams: the listed streams' tails become zeros
+// Per-stream rates (FVAD_INPUT_RATE_PER_STREAM; DESIGN.md section 7, "Per-stream
+// rates"): a push is packed [tick][stream][channel][rate(stream) / 100], and
+//
+//   rate_idx [stream]          rs::rate_index of the stream's rate
+//   offsets  [stream + 1]      a stream's first sample inside a tick; [n_streams]: a tick's length
+//   lists    [stream]          the streams by rate, rate index ascending: rate i's are
+//                              lists[list_at[i] .. list_at[i + 1])
+//   tails    [stream][channel][rs::kMaxTail]   a row's K - 1 words lie at its front
+//
+// k_resample_ps is k_resample's unit body over one rate's list: a unit is
+// (tick, listed stream, channel), its row starts at
+// raw[tick * tick_len + offsets[s] + c * n_in].
+struct ResamplePsArgs {
+  ResampleArgs r;  // taps, d: this launch's rate; n_streams: the engine's; tails as above
+  const int *list;
+  const long long *offsets;
+  long long tick_len;
+  int n_list;
+};
+struct ResampleTailPsArgs {
+  const void *raw;
+  float *tails;
+  const int *ticks_valid, *rate_idx;
+  const long long *offsets;
+  long long tick_len;
+  int n_streams, n_channels, n_ticks, in16;
+  int hist[rs::kPsRates], n_in[rs::kPsRates];  // K - 1 (0 at 48000) and rate / 100 by rate index
+};
+// a push of a per-stream engine: the tables above on the device, the lists'
+// bounds and the rates' descriptions and tap tables (null at 48000) by value
+struct ResamplePsPush {
+  const void *raw;
+  float *tails;
+  const int *ticks_valid;
+  float *out;
+  int n_streams, n_channels, n_ticks, in16;
+  const int *rate_idx, *lists;
+  const long long *offsets;
+  long long tick_len;
+  int list_at[rs::kPsRates + 1];
+  const float *taps[rs::kPsRates];
+  rs::Desc d[rs::kPsRates];
+};
+// One k_resample_ps launch per rate present, in the variant launch_resample
+// picks for that rate; the 48000 streams through k_resample_copy (convert
+// only); then one k_resample_tail_ps over every row, each with its own K - 1
+// and n_in.
+hipError_t launch_resample_ps(const ResamplePsPush &p, hipStream_t stream);
+
+// fvad_engine_reset_streams, fvad_engine_set_stream_rates: the listed streams'
+// tails become zeros
 struct ResampleClearArgs {
   float *tails;
-  int row_words;  // n_channels * (K - 1)
+  int row_words;  // n_channels * (K - 1); per-stream rates: n_channels * rs::kMaxTail
   IdList ids;
 };
 hipError_t launch_resample_clear(const ResampleClearArgs &a, hipStream_t stream);

@@ -20,6 +20,12 @@
 // indices are hist + i - k with 0 <= i <= n_in - 1 (480 M / L = n_in) and
 // 0 <= k <= K - 1 = hist.  launch_resample picks the variant whose static
 // arrays hold the rate's table and window.
+//
+// The unit body is written once, resample_units, over a row map that places a
+// unit: RowsAll for k_resample (the arithmetic above), RowsListed for
+// k_resample_ps, a per-stream engine's launch over the streams of one rate
+// (fvad_resample.h).  k_resample_copy passes such an engine's 48000 streams
+// through, and k_resample_tail_ps replaces every row's tail behind them.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
@@ -36,8 +42,63 @@ __device__ __forceinline__ float load_in(const In *p) {
 }
 }  // namespace
 
-template <typename In, int S, int TAPCAP, int XCAP>
-__global__ void __launch_bounds__(S) k_resample(ResampleArgs a) {
+// A unit's place: its tick and stream, and where its row lies -- the tick's
+// first sample in raw, the row's tail, the tick's 480 outputs (in words).
+struct Unit {
+  size_t tick;
+  int s;
+  size_t cur, tail, dst;
+};
+
+// k_resample's row map: unit u is row u of [tick][stream][channel], at one rate
+struct RowsAll {
+  size_t rows;
+  int n_channels, n_ticks, n_in, hist;
+  using Index = size_t;
+  __device__ __forceinline__ size_t units() const { return rows * (size_t)n_ticks; }
+  __device__ __forceinline__ size_t tick_len() const { return rows * (size_t)n_in; }
+  __device__ __forceinline__ Unit unit(size_t u) const {
+    Unit w;
+    w.tick = u / rows;
+    const size_t row = u - w.tick * rows;
+    w.s = (int)(row / (size_t)n_channels);
+    w.cur = u * (size_t)n_in;
+    w.tail = row * (size_t)hist;
+    w.dst = u * rs::kOut;
+    return w;
+  }
+};
+
+// k_resample_ps's: a workgroup keeps one tick (blockIdx.y) and one channel
+// (blockIdx.z) and walks one rate's list, so placing a unit takes no division
+struct RowsListed {
+  const int *list;
+  const long long *offsets;
+  size_t len;  // a tick's length in samples
+  int n_list, n_streams, n_channels, n_in;
+  using Index = unsigned;
+  __device__ __forceinline__ unsigned units() const { return (unsigned)n_list; }
+  __device__ __forceinline__ size_t tick_len() const { return len; }
+  __device__ __forceinline__ Unit unit(unsigned li) const {
+    Unit w;
+    const unsigned c = blockIdx.z;
+    w.tick = blockIdx.y;
+    // (uniform over the workgroup: kept in scalar registers)
+    w.s = __builtin_amdgcn_readfirstlane(list[li]);
+    const unsigned long long off = (unsigned long long)offsets[w.s];
+    const size_t at = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
+                      (unsigned)__builtin_amdgcn_readfirstlane((int)off);
+    const size_t row = (size_t)w.s * n_channels + c;
+    w.cur = w.tick * len + at + c * (size_t)n_in;
+    w.tail = row * rs::kMaxTail;
+    w.dst = (w.tick * ((size_t)n_streams * n_channels) + row) * rs::kOut;
+    return w;
+  }
+};
+
+// the unit body of k_resample and k_resample_ps
+template <typename In, int S, int TAPCAP, int XCAP, typename Map>
+__device__ __forceinline__ void resample_units(const ResampleArgs &a, const Map &m) {
   constexpr int NOUT = rs::kOut / S;
   static_assert(NOUT * S == rs::kOut, "a thread's outputs cover the tick");
   __shared__ float s_tap[TAPCAP];  // [k][p]
@@ -51,25 +112,25 @@ __global__ void __launch_bounds__(S) k_resample(ResampleArgs a) {
   int i0, p;
   rs::position(tid, L, M, i0, p);
   const int step = S * M / L;  // exact: S M is a multiple of L
-  const size_t rows = (size_t)a.n_streams * a.n_channels, units = rows * (size_t)a.n_ticks;
+  using Index = typename Map::Index;
+  const Index units = m.units();
   const In *raw = static_cast<const In *>(a.raw);
-  for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
-    const size_t tick = u / rows, row = u - tick * rows;
-    const int s = (int)(row / (size_t)a.n_channels);
-    const int tv = a.ticks_valid ? a.ticks_valid[s] : a.n_ticks;
-    float *dst = a.out + u * rs::kOut;
-    if (tick >= (size_t)tv) {  // (the whole workgroup: u and tv are uniform)
+  for (Index u = blockIdx.x; u < units; u += gridDim.x) {
+    const Unit w = m.unit(u);
+    const int tv = a.ticks_valid ? a.ticks_valid[w.s] : a.n_ticks;
+    float *dst = a.out + w.dst;
+    if (w.tick >= (size_t)tv) {  // (the whole workgroup: u and tv are uniform)
       for (int n = 0; n < NOUT; n++) dst[tid + n * S] = 0.0f;
       continue;
     }
     __syncthreads();  // the last unit's reads of s_x are done
-    const In *cur = raw + u * (size_t)n_in;
+    const In *cur = raw + w.cur;
     for (int j = tid; j < n_in; j += S) s_x[hist + j] = load_in(cur + j);
-    if (tick > 0) {
-      const In *prev = cur - rows * (size_t)n_in + (n_in - hist);
+    if (w.tick > 0) {
+      const In *prev = cur - m.tick_len() + (n_in - hist);
       for (int j = tid; j < hist; j += S) s_x[j] = load_in(prev + j);
     } else {
-      const float *tail = a.tails + row * (size_t)hist;
+      const float *tail = a.tails + w.tail;
       for (int j = tid; j < hist; j += S) s_x[j] = tail[j];
     }
     __syncthreads();  // (the first one also covers s_tap)
@@ -78,6 +139,37 @@ __global__ void __launch_bounds__(S) k_resample(ResampleArgs a) {
     rs::accumulate<NOUT>(
         K, [&](int k) { return s_tap[k * L + p]; }, [&](int n, int k) { return xp[n * step - k]; }, acc);
     for (int n = 0; n < NOUT; n++) dst[tid + n * S] = acc[n];
+  }
+}
+
+template <typename In, int S, int TAPCAP, int XCAP>
+__global__ void __launch_bounds__(S) k_resample(ResampleArgs a) {
+  const RowsAll m{(size_t)a.n_streams * a.n_channels, a.n_channels, a.n_ticks, a.d.n_in, a.d.K - 1};
+  resample_units<In, S, TAPCAP, XCAP>(a, m);
+}
+
+// Bounds: list[li] < n_streams and offsets[s] + n_channels * n_in <=
+// offsets[s + 1] <= tick_len for every listed s (the host writes rate_idx,
+// offsets and lists from one set of rates: fvad_input_layout), so a unit's
+// row and the K - 1 <= n_in words before it lie inside the push.
+template <typename In, int S, int TAPCAP, int XCAP>
+__global__ void __launch_bounds__(S) k_resample_ps(ResamplePsArgs a) {
+  const RowsListed m{a.list, a.offsets, (size_t)a.tick_len, a.n_list, a.r.n_streams, a.r.n_channels, a.r.d.n_in};
+  resample_units<In, S, TAPCAP, XCAP>(a.r, m);
+}
+
+// the 48000 streams of a per-stream engine: nothing to filter, a tick's 480
+// samples as floats (rs::sample), zeros past the stream's ticks_valid
+template <typename In>
+__global__ void __launch_bounds__(256) k_resample_copy(ResamplePsArgs a) {
+  const RowsListed m{a.list, a.offsets, (size_t)a.tick_len, a.n_list, a.r.n_streams, a.r.n_channels, rs::kOut};
+  const unsigned units = m.units();
+  const In *raw = static_cast<const In *>(a.r.raw);
+  for (unsigned u = blockIdx.x; u < units; u += gridDim.x) {
+    const Unit w = m.unit(u);
+    const int tv = a.r.ticks_valid ? a.r.ticks_valid[w.s] : a.r.n_ticks;
+    const bool valid = w.tick < (size_t)tv;
+    for (int j = threadIdx.x; j < rs::kOut; j += 256) a.r.out[w.dst + j] = valid ? load_in(raw + w.cur + j) : 0.0f;
   }
 }
 
@@ -97,6 +189,25 @@ __global__ void __launch_bounds__(256) k_resample_tail(ResampleArgs a) {
   a.tails[idx] = load_in(raw + ((size_t)(tv - 1) * rows + row) * (size_t)a.d.n_in + (a.d.n_in - hist) + j);
 }
 
+// k_resample_tail over a per-stream engine's rows [stream][channel][kMaxTail]:
+// each with its stream's own K - 1 and n_in (a 48000 stream has no tail)
+template <typename In>
+__global__ void __launch_bounds__(256) k_resample_tail_ps(ResampleTailPsArgs a) {
+  const size_t rows = (size_t)a.n_streams * a.n_channels;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * (size_t)rs::kMaxTail) return;
+  const size_t row = idx / (size_t)rs::kMaxTail;
+  const int j = (int)(idx - row * (size_t)rs::kMaxTail), s = (int)(row / (size_t)a.n_channels);
+  const int c = (int)(row - (size_t)s * a.n_channels), ri = a.rate_idx[s];
+  const int hist = a.hist[ri], n_in = a.n_in[ri];
+  if (j >= hist) return;
+  const int tv = a.ticks_valid ? a.ticks_valid[s] : a.n_ticks;
+  if (tv < 1) return;
+  const In *raw = static_cast<const In *>(a.raw);
+  a.tails[idx] = load_in(raw + (size_t)(tv - 1) * (size_t)a.tick_len + (size_t)a.offsets[s] + (size_t)c * n_in +
+                         (n_in - hist) + j);
+}
+
 // listed stream blockIdx.x: its channels' tails become zeros
 __global__ void __launch_bounds__(256) k_resample_clear(ResampleClearArgs a) {
   float *row = a.tails + (size_t)a.ids.id[blockIdx.x] * a.row_words;
@@ -106,28 +217,94 @@ __global__ void __launch_bounds__(256) k_resample_clear(ResampleClearArgs a) {
 namespace {
 
 template <typename In, int S, int TAPCAP, int XCAP>
-hipError_t run(const ResampleArgs &a, unsigned grid, hipStream_t stream) {
+hipError_t run(const ResampleArgs &a, dim3 grid, hipStream_t stream) {
   if (a.d.L * a.d.K > TAPCAP || a.d.n_in + a.d.K - 1 > XCAP || (S * a.d.M) % a.d.L) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_resample<In, S, TAPCAP, XCAP>), dim3(grid), dim3(S), 0, stream, a);
+  hipLaunchKernelGGL((k_resample<In, S, TAPCAP, XCAP>), grid, dim3(S), 0, stream, a);
   return hipGetLastError();
+}
+template <typename In, int S, int TAPCAP, int XCAP>
+hipError_t run(const ResamplePsArgs &a, dim3 grid, hipStream_t stream) {
+  if (a.r.d.L * a.r.d.K > TAPCAP || a.r.d.n_in + a.r.d.K - 1 > XCAP || (S * a.r.d.M) % a.r.d.L)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_resample_ps<In, S, TAPCAP, XCAP>), grid, dim3(S), 0, stream, a);
+  return hipGetLastError();
+}
+
+// the variant of a rate: the block size divides 480 and makes S M a multiple
+// of L; the arrays hold the largest table and window of the variant's rates
+template <typename In, typename Args>
+hipError_t run_rate(const rs::Desc &d, const Args &a, dim3 grid, hipStream_t stream) {
+  if (d.L == 160)  // 44.1 kHz
+    return run<In, 160, rs::kMaxTaps, 441 + 47>(a, grid, stream);
+  if (d.L <= 2)  // 24 kHz (L = 2), 96 kHz (L = 1, K = 96)
+    return run<In, 160, 96, 960 + rs::kMaxTail>(a, grid, stream);
+  // 8 kHz (L = 6), 16 and 32 kHz (L = 3)
+  return run<In, 240, 6 * 48, 320 + 47>(a, grid, stream);
 }
 
 template <typename In>
 hipError_t launch_typed(const ResampleArgs &a, hipStream_t stream) {
   const size_t rows = (size_t)a.n_streams * a.n_channels, units = rows * (size_t)a.n_ticks;
   const unsigned grid = (unsigned)std::min<size_t>(units, 2048);
-  hipError_t rc;
-  // the block size divides 480 and makes S M a multiple of L; the arrays hold
-  // the largest table and window of the variant's rates
-  if (a.d.L == 160)  // 44.1 kHz
-    rc = run<In, 160, rs::kMaxTaps, 441 + 47>(a, grid, stream);
-  else if (a.d.L <= 2)  // 24 kHz (L = 2), 96 kHz (L = 1, K = 96)
-    rc = run<In, 160, 96, 960 + rs::kMaxTail>(a, grid, stream);
-  else  // 8 kHz (L = 6), 16 and 32 kHz (L = 3)
-    rc = run<In, 240, 6 * 48, 320 + 47>(a, grid, stream);
+  const hipError_t rc = run_rate<In>(a.d, a, dim3(grid), stream);
   if (rc != hipSuccess) return rc;
   const size_t words = rows * (size_t)(a.d.K - 1);
   hipLaunchKernelGGL(k_resample_tail<In>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+template <typename In>
+hipError_t launch_typed_ps(const ResamplePsPush &p, hipStream_t stream) {
+  ResamplePsArgs a{};
+  a.r.raw = p.raw;
+  a.r.tails = p.tails;
+  a.r.ticks_valid = p.ticks_valid;
+  a.r.out = p.out;
+  a.r.n_streams = p.n_streams;
+  a.r.n_channels = p.n_channels;
+  a.r.n_ticks = p.n_ticks;
+  a.r.in16 = p.in16;
+  a.offsets = p.offsets;
+  a.tick_len = p.tick_len;
+  bool tails = false;
+  for (int i = 0; i < rs::kPsRates; i++) {
+    a.n_list = p.list_at[i + 1] - p.list_at[i];
+    if (a.n_list < 1) continue;
+    a.list = p.lists + p.list_at[i];
+    a.r.taps = p.taps[i];
+    a.r.d = p.d[i];
+    // about 2048 workgroups, as launch_resample: (ticks x channels) of them side by side over the list
+    const unsigned across = (unsigned)p.n_ticks * p.n_channels;
+    const dim3 grid(std::max(1u, std::min((unsigned)a.n_list, 2048u / across)), p.n_ticks, p.n_channels);
+    hipError_t rc;
+    if (i == rs::kPsIndex48) {
+      hipLaunchKernelGGL(k_resample_copy<In>, grid, dim3(256), 0, stream, a);
+      rc = hipGetLastError();
+    } else {
+      if (!a.r.taps) return hipErrorInvalidValue;
+      tails = true;
+      rc = run_rate<In>(a.r.d, a, grid, stream);
+    }
+    if (rc != hipSuccess) return rc;
+  }
+  if (!tails) return hipSuccess;
+  ResampleTailPsArgs t{};
+  t.raw = p.raw;
+  t.tails = p.tails;
+  t.ticks_valid = p.ticks_valid;
+  t.rate_idx = p.rate_idx;
+  t.offsets = p.offsets;
+  t.tick_len = p.tick_len;
+  t.n_streams = p.n_streams;
+  t.n_channels = p.n_channels;
+  t.n_ticks = p.n_ticks;
+  t.in16 = p.in16;
+  for (int i = 0; i < rs::kPsRates; i++) {
+    t.hist[i] = p.d[i].K - 1;
+    t.n_in[i] = p.d[i].n_in;
+  }
+  const size_t words = (size_t)p.n_streams * p.n_channels * rs::kMaxTail;
+  hipLaunchKernelGGL(k_resample_tail_ps<In>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, t);
   return hipGetLastError();
 }
 
@@ -137,6 +314,13 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream) {
   if (a.n_ticks < 1 || a.n_streams < 1 || a.n_channels < 1) return hipSuccess;
   (void)hipGetLastError();
   return a.in16 ? launch_typed<short>(a, stream) : launch_typed<float>(a, stream);
+}
+
+hipError_t launch_resample_ps(const ResamplePsPush &p, hipStream_t stream) {
+  if (p.n_ticks < 1 || p.n_streams < 1 || p.n_channels < 1) return hipSuccess;
+  if (p.n_ticks > 65535 || p.n_channels > 65535) return hipErrorInvalidValue;  // (grid y and z)
+  (void)hipGetLastError();
+  return p.in16 ? launch_typed_ps<short>(p, stream) : launch_typed_ps<float>(p, stream);
 }
 
 hipError_t launch_resample_clear(const ResampleClearArgs &a, hipStream_t stream) {

@@ -45,6 +45,39 @@ FVAD_HD inline bool describe(int rate, Desc &d) {
   return true;
 }
 
+// Per-stream rates (FVAD_INPUT_RATE_PER_STREAM): a stream's rate is a listed
+// one or 48000, which is not resampled (K = 1: no history).  The index of a
+// rate in ascending order, -1 off the list; describe_ps fills 48000 as the
+// identity L = M = K = 1.
+constexpr int kPsRates = kRates + 1;
+constexpr int kPsIndex48 = 5;
+
+FVAD_HD inline int rate_index(int rate) {
+  switch (rate) {
+    case 8000: return 0;
+    case 16000: return 1;
+    case 24000: return 2;
+    case 32000: return 3;
+    case 44100: return 4;
+    case 48000: return kPsIndex48;
+    case 96000: return 6;
+    default: return -1;
+  }
+}
+
+FVAD_HD inline int index_rate(int index) {
+  constexpr int r[kPsRates] = {8000, 16000, 24000, 32000, 44100, 48000, 96000};
+  return r[index];
+}
+
+FVAD_HD inline bool describe_ps(int rate, Desc &d) {
+  if (rate != 48000) return describe(rate, d);
+  d.rate = 48000;
+  d.L = d.M = d.K = 1;
+  d.n_in = kOut;
+  return true;
+}
+
 // The decimating direction (fvad_engine_config.denoised_rate; DESIGN.md section
 // 7, "Output rate of the denoised PCM"): a tick's 480 denoised samples give
 // n_out = rate / 100.  L = rate / g, M = 48000 / g; output r reads the K

@@ -40,7 +40,7 @@ class EngineConfig(C.Structure):
                 ("band_lo", C.c_int * MAX_BANDS), ("band_hi", C.c_int * MAX_BANDS), ("want_denoised", C.c_int),
                 ("mode", C.c_int), ("use_denoiser", C.c_int),
                 ("want_spectrum", C.c_int), ("spec_lo", C.c_int), ("spec_hi", C.c_int),
-                ("denoised_rate", C.c_int), ("input_rate", C.c_int)]
+                ("input_rate_max", C.c_int), ("denoised_rate", C.c_int), ("input_rate", C.c_int)]
 
 
 class ResampleDesc(C.Structure):
@@ -296,6 +296,10 @@ SYMBOLS = [
     ("fvad_resample_host", C.c_int, [C.c_int, F32P, C.c_size_t, F32P, F32P]),
     ("fvad_engine_input_frame", C.c_int, [C.c_void_p]),
     ("fvad_engine_fetch_input", C.c_int, [C.c_void_p, C.c_int, F32P]),
+    ("fvad_input_layout", C.c_int, [I32P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    ("fvad_engine_input_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("fvad_engine_set_stream_rates", C.c_int, [C.c_void_p, I32P, C.c_int, I32P]),
+    ("fvad_engine_stream_rates", C.c_int, [C.c_void_p, I32P]),
     ("fvad_engine_resample_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("fvad_resample_out_info", C.c_int, [C.c_int, C.c_void_p]),
     ("fvad_resample_out_taps", C.c_size_t, [C.c_int, F32P, C.c_size_t]),
@@ -494,6 +498,21 @@ def resample_host(input_rate, x, tail=None):
     return out
 
 
+INPUT_RATE_PER_STREAM = -1
+ERATE = -6
+
+
+def input_layout(rates, n_channels):
+    """fvad_input_layout (host only): offsets[n_streams + 1] (int64) of a per-stream
+    engine's packed push [tick][stream][channel][rate(stream) / 100] -- offsets[s] is
+    stream s's first sample inside a tick, offsets[-1] a tick's length in samples."""
+    r = _ids(rates)
+    off = np.zeros(r.size + 1, np.int64)
+    _check(lib().fvad_input_layout(r.ctypes.data_as(I32P), r.size, n_channels,
+                                   off.ctypes.data_as(C.POINTER(C.c_int64))), "fvad_input_layout")
+    return off
+
+
 def resample_out_info(rate):
     """fvad_resample_out_info: the downsampler from 48 kHz to rate as a dict --
     L, M, taps_per_phase, frame_out and the delay in 48 kHz samples (host only)."""
@@ -550,7 +569,7 @@ class Engine:
 
     def __init__(self, model, n_streams, n_channels=2, device=0, max_ticks=100, fft_size=2048, bands=((4, 64),),
                  want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000, spectrum=None,
-                 denoised_rate=48000):
+                 denoised_rate=48000, input_rate_max=0):
         cfg = EngineConfig()
         lib().fvad_engine_config_default(C.byref(cfg), n_streams, n_channels)
         cfg.device = device
@@ -567,7 +586,10 @@ class Engine:
                     "f32_fast": MODE_F32_FAST}[mode]
         cfg.use_denoiser = int(use_denoiser)
         # 8000 .. 96000: the pushes are at that rate, resampled to 48 kHz on the device
-        cfg.input_rate = 0 if input_rate in (0, 48000) else input_rate
+        # "per_stream": every stream has its own rate, at most input_rate_max (set_stream_rates)
+        self.per_stream = input_rate in ("per_stream", INPUT_RATE_PER_STREAM)
+        cfg.input_rate = INPUT_RATE_PER_STREAM if self.per_stream else 0 if input_rate in (0, 48000) else input_rate
+        cfg.input_rate_max = input_rate_max
         # 8000 .. 96000: the denoised PCM comes back at that rate, downsampled on the device
         # (0 and 48000 both mean the 48 kHz signal: passed on as given)
         cfg.denoised_rate = denoised_rate
@@ -586,10 +608,63 @@ class Engine:
         # (VAD.zig:307-347); with W > 1 the window outputs get a slot axis
         self.wpt = lib().fvad_engine_windows_per_tick(h)
         # input samples per tick and channel: input_rate / 100 (480 at 48 kHz)
-        self.frame_in = lib().fvad_engine_input_frame(h)
+        # (a per-stream engine has none: input_layout())
+        self.frame_in = None if self.per_stream else lib().fvad_engine_input_frame(h)
         # denoised samples per tick and channel: denoised_rate / 100 (480 at 48 kHz)
         self.frame_out = lib().fvad_engine_denoised_frame(h)
         self.n_spec = lib().fvad_engine_spectrum_bins(h, None, None)  # 0: no tap
+
+    def set_stream_rates(self, streams, rates):
+        """fvad_engine_set_stream_rates: the listed streams take the listed rates between the
+        pushes submitted before and after the call (their resampler history restarts from
+        zeros); never waits for the device."""
+        a, r = _ids(streams), _ids(rates)
+        if a.size != r.size:
+            raise ValueError("rates: one per listed stream")
+        _check(lib().fvad_engine_set_stream_rates(self.h, a.ctypes.data_as(I32P), a.size, r.ctypes.data_as(I32P)),
+               "fvad_engine_set_stream_rates")
+
+    def stream_rates(self):
+        """The rates the next submitted push will use (fvad_engine_stream_rates)."""
+        r = np.zeros(self.B, np.int32)
+        _check(lib().fvad_engine_stream_rates(self.h, r.ctypes.data_as(I32P)), "fvad_engine_stream_rates")
+        return [int(v) for v in r]
+
+    def input_layout(self):
+        """fvad_engine_input_layout: input_layout() over the engine's current rates."""
+        off = np.zeros(self.B + 1, np.int64)
+        _check(lib().fvad_engine_input_layout(self.h, off.ctypes.data_as(C.POINTER(C.c_int64))),
+               "fvad_engine_input_layout")
+        return off
+
+    def pack_input(self, rows):
+        """rows: one [ticks][channels][rate / 100] array per stream, all float32 or all int16.
+        Returns the packed push of the current layout, 1-D, [tick][stream][channel][rate / 100]."""
+        off = self.input_layout()
+        rows = [np.asarray(x) for x in rows]
+        if len(rows) != self.B:
+            raise ValueError("rows: one array per stream")
+        dt = np.int16 if rows[0].dtype == np.int16 else np.float32
+        T = rows[0].shape[0]
+        out = np.zeros((T, int(off[-1])), dt)
+        for s, x in enumerate(rows):
+            n = int(off[s + 1] - off[s])
+            if x.shape != (T, self.C, n // self.C) or (dt == np.int16) != (x.dtype == np.int16):
+                raise ValueError("rows[%d]: shape %s, dtype %s; expected (%d, %d, %d) %s"
+                                 % (s, x.shape, x.dtype, T, self.C, n // self.C, np.dtype(dt).name))
+            out[:, off[s]:off[s + 1]] = x.reshape(T, n)
+        return out.reshape(-1)
+
+    def _slot_samples(self):
+        return self.max_ticks * self.B * self.C * (self.cfg.input_rate_max // 100)
+
+    def _packed(self, pcm, dtype):
+        """A per-stream engine's push: the packed 1-D array, and its ticks."""
+        pcm = np.ascontiguousarray(pcm, dtype).reshape(-1)
+        tick = int(self.input_layout()[-1])
+        if pcm.size == 0 or pcm.size % tick:
+            raise ValueError("packed push: %d samples are no multiple of a tick's %d" % (pcm.size, tick))
+        return pcm, pcm.size // tick
 
     def _alloc_out(self, n_ticks, denoised):
         T, B, Ch, nb, W = n_ticks, self.B, self.C, self.nb, self.wpt
@@ -606,9 +681,12 @@ class Engine:
     def push(self, pcm, ticks_valid=None, denoised=False, last_tick_samples=None):
         """pcm: [ticks][streams][channels][frame_in] normalised f32; last_tick_samples
         (no-denoiser engines): real samples in each stream's last valid tick."""
-        pcm = np.ascontiguousarray(pcm, np.float32)
-        T = pcm.shape[0]
-        assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
+        if self.per_stream:
+            pcm, T = self._packed(pcm, np.float32)
+        else:
+            pcm = np.ascontiguousarray(pcm, np.float32)
+            T = pcm.shape[0]
+            assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
         o, s = self._alloc_out(T, denoised)
         tv = None
         if ticks_valid is not None:
@@ -628,17 +706,23 @@ class Engine:
         p = lib().fvad_engine_input_slot(self.h)
         if not p:
             raise FvadError("fvad_engine_input_slot: %s" % last_error())
+        if self.per_stream:  # (flat: max_ticks ticks of the highest rate)
+            return np.ctypeslib.as_array(C.cast(p, F32P), shape=(self._slot_samples(),))
         n = self.max_ticks * self.B * self.C * self.frame_in
         arr = np.ctypeslib.as_array(C.cast(p, F32P), shape=(n,))
         return arr.reshape(self.max_ticks, self.B, self.C, self.frame_in)
 
     def submit(self, pcm, ticks_valid=None):
         """Asynchronous push (fvad_engine_submit): returns once queued."""
-        pcm = np.ascontiguousarray(pcm, np.float32)
-        assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
+        if self.per_stream:
+            pcm, T = self._packed(pcm, np.float32)
+        else:
+            pcm = np.ascontiguousarray(pcm, np.float32)
+            assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
+            T = pcm.shape[0]
         tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
         self._sub_keep = tv
-        _check(lib().fvad_engine_submit(self.h, fptr(pcm), pcm.shape[0],
+        _check(lib().fvad_engine_submit(self.h, fptr(pcm), T,
                                         tv.ctypes.data_as(I32P) if tv is not None else None), "fvad_engine_submit")
 
     def input_slot_i16(self):
@@ -647,6 +731,8 @@ class Engine:
         p = lib().fvad_engine_input_slot_i16(self.h)
         if not p:
             raise FvadError("fvad_engine_input_slot_i16: %s" % last_error())
+        if self.per_stream:
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(self._slot_samples(),))
         n = self.max_ticks * self.B * self.C * self.frame_in
         arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(n,))
         return arr.reshape(self.max_ticks, self.B, self.C, self.frame_in)
@@ -654,12 +740,16 @@ class Engine:
     def submit_i16(self, pcm, ticks_valid=None, last_tick_samples=None):
         """Asynchronous push of 16-bit samples k (fvad_engine_submit_i16): the
         same outputs as submit() of k / 32768.0f, half the PCIe bytes."""
-        pcm = np.ascontiguousarray(pcm, np.int16)
-        assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
+        if self.per_stream:
+            pcm, T = self._packed(pcm, np.int16)
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
+            T = pcm.shape[0]
         tv = np.ascontiguousarray(ticks_valid, np.int32) if ticks_valid is not None else None
         lt = np.ascontiguousarray(last_tick_samples, np.int32) if last_tick_samples is not None else None
         self._sub_keep = (tv, lt)
-        _check(lib().fvad_engine_submit_i16(self.h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), pcm.shape[0],
+        _check(lib().fvad_engine_submit_i16(self.h, pcm.ctypes.data_as(C.POINTER(C.c_int16)), T,
                                             tv.ctypes.data_as(I32P) if tv is not None else None,
                                             lt.ctypes.data_as(I32P) if lt is not None else None),
                "fvad_engine_submit_i16")

@@ -127,6 +127,12 @@ typedef struct {
    * last field; a binding that declares the struct itself must insert them here */
   /* ABI note (r5): the trailing `unsigned cu_mask[8]` of earlier builds was removed; a binding
    * compiled against them must drop it (fvad_engine_config_default fills every field) */
+  int input_rate_max;   /* read only with input_rate = FVAD_INPUT_RATE_PER_STREAM (section 2b-ps below): the
+                         * highest rate a stream of the engine may take, 8000, 16000, 24000, 32000, 44100,
+                         * 48000 or 96000; it bounds the raw staging buffers and the pinned slots.  Default
+                         * 0; any other value with another input_rate is FVAD_ERATE */
+  /* ABI note: input_rate_max stands in front of denoised_rate and input_rate, which stay the struct's
+   * last two fields; a binding that declares the struct itself must insert it here */
   int denoised_rate;    /* the rate of the denoised PCM the engine returns: 0 or 48000 (default 0) for the
                          * 48 kHz signal, or 8000, 16000, 24000, 32000, 44100, 96000 for an engine that
                          * brings every push's denoised rows to that rate on the device (section 2d below);
@@ -136,9 +142,13 @@ typedef struct {
    * binding that declares the struct itself must insert it here */
   int input_rate;      /* the rate of the pushed samples: 0 or 48000 (default 0) for 48 kHz input, or 8000,
                          * 16000, 24000, 32000, 44100, 96000 for an engine that resamples every push to
-                         * 48 kHz on the device (section 2b below); FVAD_ERATE otherwise.  sample_rate, the
-                         * pipeline's rate, stays 48000 */
+                         * 48 kHz on the device (section 2b below), or FVAD_INPUT_RATE_PER_STREAM for an
+                         * engine whose streams each have a rate of their own (section 2b-ps);
+                         * FVAD_ERATE otherwise.  sample_rate, the pipeline's rate, stays 48000 */
 } fvad_engine_config;
+
+/* fvad_engine_config.input_rate: every stream has its own input rate (section 2b-ps) */
+#define FVAD_INPUT_RATE_PER_STREAM (-1)
 
 /* staged: time-parallel frame kernels + a thin per-stream recurrence kernel;
  * fused: one workgroup runs every frame of a stream (lower memory); staged
@@ -247,7 +257,8 @@ typedef struct {
   uint32_t reserved[13];  /*  76 [0]: the saving engine's input_rate when it resamples (its records then end
                            *     with the resampler's tails, per channel (taps_per_phase + 2) & ~3 words, and
                            *     config_hash covers the rate), 0 otherwise; a blob restores only into an
-                           *     engine of the same input_rate.  [1]: the saving engine's denoised_rate when it
+                           *     engine of the same input_rate; 0xFFFFFFFF: a per-stream engine, section
+                           *     2b-ps).  [1]: the saving engine's denoised_rate when it
                            *     is a listed rate (its records then end with the output resampler's tails, behind
                            *     the input tails if there are any, per channel (K + 2) & ~3 words, K section 2d's
                            *     taps_per_phase, and config_hash covers the rate), 0 otherwise; a blob restores
@@ -415,7 +426,8 @@ size_t fvad_resample_taps(int input_rate, float *out, size_t cap);
  * before in[0], read and replaced by the last K - 1 of this call's input
  * (carry it to continue a stream); NULL: zeros, nothing kept. */
 int fvad_resample_host(int input_rate, const float *in, size_t n_ticks, float *tail, float *out);
-/* input samples per tick and channel: frame_in, 480 on a plain engine */
+/* input samples per tick and channel: frame_in, 480 on a plain engine (FVAD_EINVAL on a
+ * per-stream engine, section 2b-ps) */
 int fvad_engine_input_frame(const fvad_engine *e);
 /* The 48 kHz device input of the last push, [ticks][streams][channels][480]:
  * what k_resample wrote (zeros in the ticks past a stream's ticks_valid).  A
@@ -424,6 +436,66 @@ int fvad_engine_fetch_input(fvad_engine *e, int n_ticks, float *pcm48);
 /* average event time (ms) of a push's resample launches (k_resample and the
  * tail update behind it) and the pushes measured; a sync point */
 int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs);
+
+/* ------------------------------------------------------------------ */
+/* 2b-ps. Per-stream input rates (input_rate = FVAD_INPUT_RATE_PER_STREAM) */
+/* ------------------------------------------------------------------ */
+/* An engine created with input_rate = FVAD_INPUT_RATE_PER_STREAM and
+ * input_rate_max = Rmax carries streams of different input rates at once.  A
+ * stream's rate is one of 8000, 16000, 24000, 32000, 44100, 48000, 96000 and
+ * at most Rmax; every stream starts at Rmax.  Each stream is resampled to
+ * 48 kHz exactly as a section-2b engine of its rate resamples it (the same
+ * taps, arithmetic and K - 1 samples of history).  A 48000 stream is not
+ * resampled: float samples pass by their bits, 16-bit samples k as
+ * (float)k * (1.0f / 32768.0f), and it has no history.  The input side only:
+ * denoised_rate and clips are the engine's, as before.
+ *
+ * Layout.  A push is packed [tick][stream][channel][rate(stream) / 100]:
+ * offsets[s] is stream s's first sample inside a tick, offsets[n_streams] a
+ * tick's length in samples (fvad_input_layout; fvad_engine_input_layout is the
+ * same over the engine's current rates).  fvad_engine_push[_ex],
+ * fvad_engine_submit[_ex], fvad_engine_submit_i16 and both input slots carry
+ * n_ticks * offsets[n_streams] samples in that layout; a pinned slot holds
+ * max_ticks * n_streams * n_channels * Rmax / 100 samples.
+ * fvad_engine_input_frame is FVAD_EINVAL: no single frame length exists.
+ *
+ * fvad_engine_set_stream_rates gives the n listed streams the listed rates.
+ * Indices must be distinct and in range (FVAD_EINVAL), every rate a listed one
+ * or 48000 and at most Rmax (FVAD_ERATE); on either error nothing is touched.
+ * n == 0 is a no-op.  It never waits for the device and takes effect between
+ * the pushes submitted before it and those submitted after it: pushes still in
+ * flight (submitted, not collected) keep the rates, the layout and the
+ * history they were submitted with.  Each listed stream's resampler history
+ * becomes zeros -- also when its rate did not change; nothing else of the
+ * stream and nothing of any other stream is touched (a host that wants a
+ * fresh stream also calls fvad_engine_reset_streams).  On any other engine it
+ * is FVAD_EINVAL.  fvad_engine_stream_rates returns the rates the next
+ * submitted push will use.
+ *
+ * As on a section-2b engine: last_tick_samples must be whole ticks, each
+ * stream's value its own rate / 100 (FVAD_EINVAL otherwise); ticks_valid,
+ * fvad_engine_fetch_input (48 kHz rows, [tick][stream][channel][480]) and
+ * fvad_engine_resample_times (all of a push's resample launches together)
+ * work unchanged, and every reported sample index counts 48 kHz samples.
+ * Resident input is refused as there: fvad_engine_load_synthetic[_ex] and
+ * fvad_engine_run_resident are FVAD_EINVAL.  fvad_engine_reset and
+ * fvad_engine_reset_streams zero the history; the streams keep their rates.
+ *
+ * Stream blobs.  A per-stream engine's header carries reserved[0] =
+ * 0xFFFFFFFF; its records end with n_channels rows of 96 words (the
+ * stream's K - 1 history samples, zeros after) and 4 words behind them (the
+ * stream's rate, then zeros).  Such blobs move only between per-stream
+ * engines (FVAD_EFORMAT otherwise, as between engines of different
+ * input_rate); config_hash covers the marker, not input_rate_max.  A restore
+ * gives the target slot its record's rate, so the layout of the next push
+ * changes; a record whose rate exceeds the target's input_rate_max is
+ * FVAD_EFORMAT, found before anything is written. */
+/* host only (no GPU): offsets[n_streams + 1] of the packed layout above.
+ * FVAD_ERATE for a rate that is neither listed nor 48000 */
+int fvad_input_layout(const int *rates, int n_streams, int n_channels, int64_t *offsets /* n_streams + 1 */);
+int fvad_engine_input_layout(const fvad_engine *e, int64_t *offsets /* n_streams + 1 */);
+int fvad_engine_set_stream_rates(fvad_engine *e, const int *streams, int n, const int *rates);
+int fvad_engine_stream_rates(const fvad_engine *e, int *rates /* n_streams */);
 
 /* ------------------------------------------------------------------ */
 /* 2c. Window spectra (fvad_engine_config.want_spectrum)                */
