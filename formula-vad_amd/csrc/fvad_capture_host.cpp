@@ -243,6 +243,8 @@ extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_
   const bool den = cc->source == FVAD_CLIP_SOURCE_DENOISED, s16 = cc->format == FVAD_CLIP_S16;
   if (den && !e->cfg.want_denoised)
     return fail(FVAD_EINVAL, "a capture of the denoised rows needs an engine created with want_denoised");
+  if (den && e->ro && e->ro->ps)  // (clips at a stream's own rate: not built)
+    return fail(FVAD_EINVAL, "a capture of the denoised rows is not available with per-stream denoised rates");
   if (e->vadm.n == 0 || !e->events_on)
     return fail(FVAD_EINVAL, "clip capture needs fvad_engine_attach_vadm and fvad_engine_enable_events first");
   if (e->cap) return fail(FVAD_EINVAL, "capture already enabled");

@@ -59,6 +59,7 @@ extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams,
   c->band_hi[0] = 64;
   c->want_denoised = 0;
   c->use_denoiser = 1;
+  c->denoised_rate_max = 0;
   c->input_rate_max = 0;
   c->denoised_rate = 0;
   c->input_rate = 0;
@@ -202,7 +203,8 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
                            e->stream.get()));
   if (e->ro)
     HIP_TRY(hipMemsetAsync(e->ro->tails.get(), 0,
-                           sizeof(float) * (size_t)(e->ro->d.K - 1) * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
+                           sizeof(float) * (size_t)resample_out_tail_words(e) * e->cfg.n_channels * e->cfg.n_streams,
+                           e->stream.get()));
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
   return FVAD_OK;
 }
@@ -263,10 +265,21 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   }
   // denoised_rate: 0 or 48000 for the 48 kHz signal, or a rate k_resample_out brings it to
   const bool resample_out = c.denoised_rate != 0 && c.denoised_rate != 48000;
+  // FVAD_DENOISED_RATE_PER_STREAM: every stream its own rate, up to denoised_rate_max
+  const bool per_stream_out = c.denoised_rate == FVAD_DENOISED_RATE_PER_STREAM;
   fvad::rs::DescOut od{};
-  if (resample_out && !fvad::rs::describe_out(c.denoised_rate, od))
+  if (per_stream_out) {
+    if (fvad::rs::rate_index(c.denoised_rate_max) < 0)
+      return fail(FVAD_ERATE, "denoised_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000");
+    if (c.want_denoised != 1 || !c.use_denoiser)
+      return fail(FVAD_EINVAL, "per-stream denoised rates need want_denoised = 1 and use_denoiser = 1");
+    if (c.max_ticks > 65535) return fail(FVAD_EINVAL, "per-stream denoised rates: max_ticks <= 65535 (a grid dimension)");
+  } else if (c.denoised_rate_max != 0) {
+    return fail(FVAD_ERATE, "denoised_rate_max is read only with denoised_rate = FVAD_DENOISED_RATE_PER_STREAM");
+  } else if (resample_out && !fvad::rs::describe_out(c.denoised_rate, od)) {
     return fail(FVAD_ERATE, "denoised_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
-  if (resample_out && (!c.want_denoised || !c.use_denoiser))
+  }
+  if (resample_out && !per_stream_out && (!c.want_denoised || !c.use_denoiser))
     return fail(FVAD_EINVAL, "denoised_rate needs want_denoised = 1 and use_denoiser = 1");
   if (c.n_streams < 1 || c.n_channels < 1 || c.n_channels > FVAD_MAX_CHANNELS)
     return fail(FVAD_EINVAL, "n_streams >= 1 and 1 <= n_channels <= 8 required");
@@ -443,6 +456,8 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   if (resample_out) {
     e->ro.reset(new ResampleOut());
     e->ro->d = od;
+    e->ro->ps = per_stream_out;
+    e->ro->rate_max = c.denoised_rate_max;
     if ((rc = resample_out_make(e))) return bail(rc);
   }
   if ((rc = fvad_engine_reset(e))) return bail(rc);
@@ -782,7 +797,7 @@ int fvad::eng::fetch(fvad_engine *e, int n_ticks, fvad_outputs *o) {
   if (o->denoised) {
     if (!e->d_den) return fail(FVAD_EINVAL, "engine created without want_denoised");
     if (!denoised_to_host(c)) return fail(FVAD_EINVAL, "want_denoised = 2 keeps the denoised rows on the device");
-    if ((rc = cp(o->denoised, denoised_source(e), TB * c.n_channels * denoised_frame(e) * 4))) return rc;
+    if ((rc = cp(o->denoised, denoised_source(e), denoised_floats(e, n_ticks) * 4))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
   return FVAD_OK;

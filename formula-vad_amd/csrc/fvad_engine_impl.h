@@ -192,6 +192,39 @@ struct ResampleOut {
   int slot = 0;
   double ms_sum = 0;
   int n_timed = 0;
+  // Per-stream rates (denoised_rate = FVAD_DENOISED_RATE_PER_STREAM; DESIGN.md
+  // section 7, "Per-stream denoised rates"); none of it on a fixed-rate
+  // engine.  d, taps stay empty; tails are [s][c][rs::kMaxTailOut], a row's
+  // last 48 kHz denoised samples whatever its rate; out holds max_ticks * B *
+  // C * rate_max / 100 words, packed [tick][s][c][rate(s) / 100].
+  bool ps = false;
+  int rate_max = 0;
+  rs::DescOut dr[rs::kPsRates]{};       // by rate index (48000: only its rate and n_out)
+  dev_ptr<float> taps_r[rs::kPsRates];  // the tables of the rates up to rate_max (none at 48000)
+  // what the next submitted push uses: each stream's rate index, the layout
+  // (fvad_denoised_layout) and the streams by rate; gen counts their changes
+  std::vector<int> ridx, lists;
+  std::vector<long long> offsets;  // [B + 1]
+  int list_at[rs::kPsRates + 1] = {};
+  uint64_t gen = 1;
+  // a tick's length of the push launched last: what fetch and the D2H copies
+  // of that push move (the layout may have changed since)
+  long long pushed_len = 0;
+  // The device tables [offsets (B + 1) | lists (B, as int)] and the generation
+  // they hold: one copy, the engine stream's.  A push that finds them stale
+  // copies them from the next pinned staging row on the engine stream, ahead
+  // of its launches and behind those of every push before it.  stage_ev[i]:
+  // the copy out of row i, waited for only should the ring come round to a row
+  // whose copy has not run (as Resample::stage_ev)
+  static constexpr int kStage = 8;
+  dev_ptr<long long> tab;
+  uint64_t tab_gen = 0;
+  pinned_ptr<long long> stage;
+  event_ptr stage_ev[kStage];
+  bool stage_used[kStage] = {};
+  int stage_next = 0;
+  size_t tab_words() const { return offsets.size() + offsets.size() / 2; }  // (B ints fit (B + 1) / 2 words)
+  long long tick_len() const { return offsets.back(); }
 };
 }  // namespace eng
 }  // namespace fvad
@@ -405,6 +438,7 @@ struct fvad_engine {
     fvad::event_ptr h2d, done;
     bool h2d_busy = false, pending = false;
     int n_ticks = 0;
+    size_t den_floats = 0;  // the denoised floats of the push in den (per-stream rates: in its own layout)
   } slots[FVAD_MAX_IN_FLIGHT];
   int sub_next = 0, col_next = 0;
   // device staging of a 16-bit submit that k_pcm16 converts into d_pcm: fused
@@ -470,6 +504,14 @@ int resample_push(fvad_engine *e, int n_ticks, const int *d_ticks);
 // the push's two launches on the engine stream (behind its last writer of d_den)
 int denoised_frame(const fvad_engine *e);
 const float *denoised_source(const fvad_engine *e);
+// per-stream denoised rates: the largest frame (what the slots are sized by),
+// the denoised floats of the push launched last (n_ticks of it), the words of
+// a row's history (K - 1, rs::kMaxTailOut with per-stream rates), and the
+// layout and the lists of the current ridx (gen advances)
+int denoised_frame_max(const fvad_engine *e);
+size_t denoised_floats(const fvad_engine *e, int n_ticks);
+int resample_out_tail_words(const fvad_engine *e);
+void resample_out_relayout(fvad_engine *e);
 int resample_out_make(fvad_engine *e);
 int resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks);
 // fvad_engine_vadm.cpp

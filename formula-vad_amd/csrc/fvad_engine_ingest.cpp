@@ -300,11 +300,72 @@ int fvad::eng::denoised_frame(const fvad_engine *e) { return e->ro ? e->ro->d.n_
 
 const float *fvad::eng::denoised_source(const fvad_engine *e) { return e->ro ? e->ro->out.get() : e->d_den.get(); }
 
+int fvad::eng::denoised_frame_max(const fvad_engine *e) {
+  return e->ro && e->ro->ps ? e->ro->rate_max / 100 : denoised_frame(e);
+}
+
+size_t fvad::eng::denoised_floats(const fvad_engine *e, int n_ticks) {
+  if (e->ro && e->ro->ps) return (size_t)n_ticks * (size_t)e->ro->pushed_len;
+  return (size_t)n_ticks * e->cfg.n_streams * e->cfg.n_channels * denoised_frame(e);
+}
+
+int fvad::eng::resample_out_tail_words(const fvad_engine *e) {
+  return e->ro->ps ? fvad::rs::kMaxTailOut : e->ro->d.K - 1;
+}
+
+void fvad::eng::resample_out_relayout(fvad_engine *e) {
+  ResampleOut &r = *e->ro;
+  const int B = e->cfg.n_streams;
+  layout_of_indices(r.ridx.data(), B, e->cfg.n_channels, r.offsets.data());
+  int n = 0;
+  for (int i = 0; i < fvad::rs::kPsRates; i++) {
+    r.list_at[i] = n;
+    for (int s = 0; s < B; s++)
+      if (r.ridx[s] == i) r.lists[n++] = s;
+  }
+  r.list_at[fvad::rs::kPsRates] = n;
+  r.gen++;
+}
+
 // fvad_engine_create's part: the table, the tails (zeroed by the reset that
 // follows) and the output rows
 int fvad::eng::resample_out_make(fvad_engine *e) {
   ResampleOut &r = *e->ro;
   const fvad_engine_config &c = e->cfg;
+  if (r.ps) {
+    // the tables of every listed rate up to rate_max, each stream at rate_max,
+    // the output rows sized by it
+    const size_t B = c.n_streams, rows = B * c.n_channels;
+    int rc;
+    for (int i = 0; i < fvad::rs::kPsRates; i++) {
+      const int rate = fvad::rs::index_rate(i);
+      if (i == fvad::rs::kPsIndex48) {  // (no filter: k_resample_out_copy)
+        r.dr[i].rate = rate;
+        r.dr[i].L = r.dr[i].M = r.dr[i].K = 1;
+        r.dr[i].n_out = fvad::rs::kIn;
+        continue;
+      }
+      fvad::rs::describe_out(rate, r.dr[i]);
+      if (rate > r.rate_max) continue;
+      const std::vector<float> &taps = fvad::resample_out_table(r.dr[i]);
+      if ((rc = fvad::make_dev(r.taps_r[i], taps.size()))) return rc;
+      HIP_TRY(hipMemcpy(r.taps_r[i].get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    r.ridx.assign(B, fvad::rs::rate_index(r.rate_max));
+    r.lists.resize(B);
+    r.offsets.resize(B + 1);
+    resample_out_relayout(e);
+    if ((rc = fvad::make_dev(r.tails, rows * fvad::rs::kMaxTailOut)) ||
+        (rc = fvad::make_dev(r.out, (size_t)c.max_ticks * rows * (r.rate_max / 100))) ||
+        (rc = fvad::make_dev(r.tab, r.tab_words())) ||
+        (rc = fvad::make_pinned(r.stage, (size_t)ResampleOut::kStage * r.tab_words())))
+      return rc;
+    for (EventTimer &tm : r.tm)
+      if ((rc = tm.create())) return rc;
+    for (fvad::event_ptr &ev : r.stage_ev)
+      if ((rc = fvad::make_event(ev))) return rc;
+    return FVAD_OK;
+  }
   const std::vector<float> &taps = fvad::resample_out_table(r.d);
   const size_t rows = (size_t)c.n_streams * c.n_channels;
   int rc;
@@ -317,10 +378,60 @@ int fvad::eng::resample_out_make(fvad_engine *e) {
   return FVAD_OK;
 }
 
+namespace {
+// the device tables, when a change of rates has overtaken them: queued on the
+// engine stream, so behind the launches of every push before this one
+int resample_out_tables(fvad_engine *e, hipStream_t st) {
+  ResampleOut &r = *e->ro;
+  if (r.tab_gen == r.gen) return FVAD_OK;
+  const int B = e->cfg.n_streams, i = r.stage_next;
+  r.stage_next = (i + 1) % ResampleOut::kStage;
+  if (r.stage_used[i]) HIP_TRY(hipEventSynchronize(r.stage_ev[i].get()));  // (complete long ago: see ResampleOut)
+  long long *row = r.stage.get() + (size_t)i * r.tab_words();
+  std::memcpy(row, r.offsets.data(), sizeof(long long) * (size_t)(B + 1));
+  std::memcpy(row + B + 1, r.lists.data(), sizeof(int) * (size_t)B);
+  HIP_TRY(hipMemcpyAsync(r.tab.get(), row, r.tab_words() * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(r.stage_ev[i].get(), st));
+  r.stage_used[i] = true;
+  r.tab_gen = r.gen;
+  return FVAD_OK;
+}
+
+int resample_out_push_ps(fvad_engine *e, int n_ticks, const int *d_ticks) {
+  ResampleOut &r = *e->ro;
+  const int B = e->cfg.n_streams;
+  hipStream_t st = e->stream.get();
+  int rc;
+  if ((rc = resample_out_tables(e, st))) return rc;
+  fvad::ResampleOutPsPush p{};
+  p.den = e->d_den.get();
+  p.tails = r.tails.get();
+  p.ticks_valid = d_ticks;
+  p.out = r.out.get();
+  p.n_streams = B;
+  p.n_channels = e->cfg.n_channels;
+  p.n_ticks = n_ticks;
+  p.offsets = r.tab.get();
+  p.lists = reinterpret_cast<const int *>(r.tab.get() + B + 1);
+  p.tick_len = r.tick_len();
+  for (int i = 0; i <= fvad::rs::kPsRates; i++) p.list_at[i] = r.list_at[i];
+  for (int i = 0; i < fvad::rs::kPsRates; i++) {
+    p.taps[i] = r.taps_r[i].get();
+    p.d[i] = r.dr[i];
+  }
+  r.pushed_len = r.tick_len();
+  EventTimer &tm = r.tm[r.slot = (r.slot + 1) % 4];
+  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
+  HIP_TRY(fvad::launch_resample_out_ps(p, st));
+  return tm.end(st);
+}
+}  // namespace
+
 // the two launches of the push being launched, on the engine stream behind
 // its last writer of d_den, timed without waiting (as resample_push)
 int fvad::eng::resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
   ResampleOut &r = *e->ro;
+  if (r.ps) return resample_out_push_ps(e, n_ticks, d_ticks);
   fvad::ResampleOutArgs a{};
   a.den = e->d_den.get();
   a.taps = r.taps.get();
@@ -339,7 +450,51 @@ int fvad::eng::resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks
   return tm.end(st);
 }
 
-extern "C" int fvad_engine_denoised_frame(const fvad_engine *e) { return e ? denoised_frame(e) : FVAD_EINVAL; }
+extern "C" int fvad_engine_denoised_frame(const fvad_engine *e) {
+  if (!e) return FVAD_EINVAL;
+  if (e->ro && e->ro->ps)
+    return fail(FVAD_EINVAL, "an engine of per-stream denoised rates has no single frame: fvad_engine_denoised_layout");
+  return denoised_frame(e);
+}
+
+// ---------------------------------------------------------------------------
+// Per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)
+// ---------------------------------------------------------------------------
+extern "C" int fvad_denoised_layout(const int *rates, int n_streams, int n_channels, int64_t *offsets) {
+  return fvad_input_layout(rates, n_streams, n_channels, offsets);  // (the same arithmetic, the same refusals)
+}
+
+extern "C" int fvad_engine_stream_denoised_rates(const fvad_engine *e, int *rates) {
+  if (!e || !rates) return fail(FVAD_EINVAL, "null argument");
+  if (!e->ro || !e->ro->ps) return fail(FVAD_EINVAL, "not an engine of per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)");
+  for (int s = 0; s < e->cfg.n_streams; s++) rates[s] = fvad::rs::index_rate(e->ro->ridx[s]);
+  return FVAD_OK;
+}
+
+extern "C" int fvad_engine_denoised_layout(const fvad_engine *e, int64_t *offsets) {
+  if (!e || !offsets) return fail(FVAD_EINVAL, "null argument");
+  if (!e->ro || !e->ro->ps) return fail(FVAD_EINVAL, "not an engine of per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)");
+  for (size_t i = 0; i < e->ro->offsets.size(); i++) offsets[i] = e->ro->offsets[i];
+  return FVAD_OK;
+}
+
+// Only the host's rates and layout change here: the device tables follow ahead
+// of the next push (resample_out_tables), and the history, which does not
+// depend on a row's rate, is left alone.  No device call at all.
+extern "C" int fvad_engine_set_stream_denoised_rates(fvad_engine *e, const int *streams, int n, const int *rates) {
+  if (!e) return fail(FVAD_EINVAL, "null engine");
+  if (!e->ro || !e->ro->ps) return fail(FVAD_EINVAL, "not an engine of per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)");
+  if (const int rc = check_stream_list(e, streams, n)) return rc;
+  if (n == 0) return FVAD_OK;
+  if (!rates) return fail(FVAD_EINVAL, "null rates");
+  ResampleOut &r = *e->ro;
+  for (int i = 0; i < n; i++)
+    if (fvad::rs::rate_index(rates[i]) < 0 || rates[i] > r.rate_max)
+      return fail(FVAD_ERATE, "a stream's denoised rate must be a listed rate or 48000, at most denoised_rate_max");
+  for (int i = 0; i < n; i++) r.ridx[streams[i]] = fvad::rs::rate_index(rates[i]);
+  resample_out_relayout(e);
+  return FVAD_OK;
+}
 
 extern "C" int fvad_engine_resample_out_times(fvad_engine *e, double *ms_avg, int *n_runs) {
   if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
@@ -423,7 +578,7 @@ int ensure_slots(fvad_engine *e, int i) {
     // windows_per_tick (up to 240 at fft_size 2): refuse configurations whose
     // slot would not be a sane pinned allocation (the streaming API only:
     // resident and push-from-host engines never allocate a slot)
-    const double slot = 4.0 * ((double)frames + (denoised_to_host(c) ? (double)TB * C * denoised_frame(e) : 0.0) + 3.0 * TB +
+    const double slot = 4.0 * ((double)frames + (denoised_to_host(c) ? (double)TB * C * denoised_frame_max(e) : 0.0) + 3.0 * TB +
                                2.0 * TBW +
                                (double)TBW * C * c.n_bands);
     if (slot > 16.0 * (1ull << 30))
@@ -449,7 +604,7 @@ int ensure_slots(fvad_engine *e, int i) {
   if ((rc = host(sl.in, TB * C * input_frame_max(e))) || (rc = host(sl.ticks, 2 * B)) || (rc = host(sl.vad, TB)) ||
       (rc = host(sl.ratio, TB)) || (rc = host(sl.wflag, TB)) || (rc = host(sl.wratio, TBW)) ||
       (rc = host(sl.wvad, TBW)) || (rc = host(sl.band, TBW * C * c.n_bands)) ||
-      (denoised_to_host(c) && (rc = host(sl.den, TB * C * denoised_frame(e)))))
+      (denoised_to_host(c) && (rc = host(sl.den, TB * C * denoised_frame_max(e)))))
     return rc;
   if ((!sl.h2d && (rc = fvad::make_event(sl.h2d))) || (rc = fvad::make_event(sl.done))) return rc;
   return FVAD_OK;
@@ -516,8 +671,8 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   auto &sl = e->slots[si];
   if (sl.pending) return fail(FVAD_EINVAL, "FVAD_MAX_IN_FLIGHT pushes in flight: collect the oldest one first");
   const size_t B = c.n_streams, TB = (size_t)n_ticks * B, TBW = TB * e->wpt;
-  // (n_samples: the input's, at the engine's input rate; bytes: the denoised output's)
-  const size_t n_samples = push_samples(e, n_ticks), bytes = TB * c.n_channels * denoised_frame(e) * sizeof(float);
+  // (n_samples: the input's, at the engine's input rate)
+  const size_t n_samples = push_samples(e, n_ticks);
   Sample *slot_in;
   if constexpr (k16)
     slot_in = sl.in16.get();
@@ -576,6 +731,8 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   e->pcm16_push = false;
   if (rc) return rc;
   if ((rc = release_input(e))) return rc;
+  // the denoised output's floats: this push's (per-stream rates: in the layout it was launched with)
+  sl.den_floats = denoised_floats(e, n_ticks);
   // outputs into the slot's pinned buffers, after the kernels on the engine
   // stream (the next push's kernels queue behind these copies)
   auto d2h = [&](void *dst, const void *src, size_t n) -> int {
@@ -585,7 +742,7 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   if ((rc = d2h(sl.vad.get(), e->d_vad.get(), TB * 4)) || (rc = d2h(sl.ratio.get(), e->d_ratio, TB * 4)) ||
       (rc = d2h(sl.wflag.get(), e->d_wflag, TB * 4)) || (rc = d2h(sl.wratio.get(), e->d_wratio, TBW * 4)) ||
       (rc = d2h(sl.wvad.get(), e->d_wvad, TBW * 4)) || (rc = d2h(sl.band.get(), e->d_band, TBW * c.n_channels * c.n_bands * 4)) ||
-      (denoised_to_host(c) && (rc = d2h(sl.den.get(), denoised_source(e), bytes))))
+      (denoised_to_host(c) && (rc = d2h(sl.den.get(), denoised_source(e), sl.den_floats * sizeof(float)))))
     return rc;
   HIP_TRY(hipEventRecord(sl.done.get(), e->stream.get()));
   sl.pending = true;
@@ -645,7 +802,7 @@ extern "C" int fvad_engine_collect(fvad_engine *e, fvad_outputs *out, int *n_tic
     cp(out->win_ratio, sl.wratio.get(), TBW * 4);
     cp(out->win_vad, sl.wvad.get(), TBW * 4);
     cp(out->band, sl.band.get(), TBW * c.n_channels * c.n_bands * 4);
-    if (out->denoised) par_copy(out->denoised, sl.den.get(), TB * c.n_channels * denoised_frame(e) * 4);
+    if (out->denoised) par_copy(out->denoised, sl.den.get(), sl.den_floats * 4);
   }
   if (n_ticks) *n_ticks = sl.n_ticks;
   sl.pending = false;

@@ -44,13 +44,15 @@ uint64_t config_hash_of(const fvad_engine *e) {
   // (per-stream rates: the marker, not input_rate_max -- a record carries its stream's rate)
   if (e->rs) h = fnv_add(h, e->rs->ps ? (int)FVAD_INPUT_RATE_PER_STREAM : e->rs->d.rate);
   // likewise the rate of the denoised PCM, when it is not the 48 kHz signal
-  if (e->ro) h = fnv_add(h, e->ro->d.rate);
+  // (per-stream denoised rates: the marker, not denoised_rate_max)
+  if (e->ro) h = fnv_add(h, e->ro->ps ? (int)FVAD_DENOISED_RATE_PER_STREAM : e->ro->d.rate);
   return h;
 }
 
 fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
   return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap,
-                           e->rs ? resample_tail_words(e) : 0, e->ro ? e->ro->d.K - 1 : 0, e->rs && e->rs->ps);
+                           e->rs ? resample_tail_words(e) : 0, e->ro ? resample_out_tail_words(e) : 0, e->rs && e->rs->ps,
+                           e->ro && e->ro->ps);
 }
 
 fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
@@ -73,7 +75,7 @@ fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   h.model_hash = e->model_hash;
   h.sample_rate = (uint32_t)e->cfg.sample_rate;
   h.reserved[0] = !e->rs ? 0u : e->rs->ps ? 0xFFFFFFFFu : (uint32_t)e->rs->d.rate;
-  h.reserved[1] = e->ro ? (uint32_t)e->ro->d.rate : 0u;
+  h.reserved[1] = !e->ro ? 0u : e->ro->ps ? 0xFFFFFFFFu : (uint32_t)e->ro->d.rate;
   return h;
 }
 
@@ -223,7 +225,7 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
     if (e->ro) {  // the output resampler's tails, on the engine stream, where k_resample_out runs
       fvad::ResampleClearArgs ra{};
       ra.tails = e->ro->tails.get();
-      ra.row_words = e->cfg.n_channels * (e->ro->d.K - 1);
+      ra.row_words = e->cfg.n_channels * resample_out_tail_words(e);
       ra.ids = ca.ids;
       HIP_TRY(fvad::launch_resample_clear(ra, e->stream.get()));
     }
@@ -292,6 +294,13 @@ extern "C" int fvad_engine_save_streams(fvad_engine *e, const int32_t *streams, 
       std::memcpy(static_cast<char *>(blob) + sizeof(h) + (size_t)i * (size_t)h.stream_bytes + 4 * (size_t)o_rate, w, sizeof(w));
     }
   }
+  if (e->ro && e->ro->ps) {  // likewise each record's denoised rate
+    const long long o_orate = layout_of(e, (int)h.seg_capacity).o_orate;
+    for (int i = 0; i < n; i++) {
+      const uint32_t w[4] = {(uint32_t)fvad::rs::index_rate(e->ro->ridx[streams[i]]), 0u, 0u, 0u};
+      std::memcpy(static_cast<char *>(blob) + sizeof(h) + (size_t)i * (size_t)h.stream_bytes + 4 * (size_t)o_orate, w, sizeof(w));
+    }
+  }
   std::memcpy(blob, &h, sizeof(h));
   return FVAD_OK;
 }
@@ -340,6 +349,17 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
       if ((int)rate > e->rs->rate_max) return fail(FVAD_EFORMAT, "stream record: its rate exceeds this engine's input_rate_max");
       rec_ridx.push_back(ri);
     }
+  std::vector<int> rec_oridx;  // per-stream denoised rates: likewise
+  if (e->ro && e->ro->ps)
+    for (int i = 0; i < n; i++) {
+      uint32_t rate;
+      std::memcpy(&rate, body + (size_t)(index ? index[i] : i) * (size_t)h.stream_bytes + 4 * (size_t)lay.o_orate, sizeof(rate));
+      const int ri = rate <= 96000u ? fvad::rs::rate_index((int)rate) : -1;
+      if (ri < 0) return fail(FVAD_EFORMAT, "stream record: not a listed denoised rate");
+      if ((int)rate > e->ro->rate_max)
+        return fail(FVAD_EFORMAT, "stream record: its denoised rate exceeds this engine's denoised_rate_max");
+      rec_oridx.push_back(ri);
+    }
   if ((rc = fvad_engine_sync(e))) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t bytes = (size_t)h.count * (size_t)h.stream_bytes;
@@ -358,6 +378,10 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
   if (!rec_ridx.empty()) {  // the slots take their records' rates: the layout of the next push follows
     for (int i = 0; i < n; i++) e->rs->ridx[streams[i]] = rec_ridx[i];
     resample_relayout(e);
+  }
+  if (!rec_oridx.empty()) {  // and their records' denoised rates: the layout of the next push's denoised PCM follows
+    for (int i = 0; i < n; i++) e->ro->ridx[streams[i]] = rec_oridx[i];
+    resample_out_relayout(e);
   }
   if (e->cap) {
     // the slots continue at their records' sample counts with nothing held

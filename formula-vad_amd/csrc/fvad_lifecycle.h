@@ -50,14 +50,19 @@ static_assert(st::kWords % 64 == 0 && st::kPitch == 0 && kPitchBuf % 4 == 0 && s
 //   o_ro + c * ro_pad           an engine with denoised_rate only (ro_tail = K - 1 > 0), behind the
 //                               input tails: channel c's output resampler tail, its last ro_tail
 //                               denoised samples, zeros after
+//                               (per-stream denoised rates: ro_tail = rs::kMaxTailOut, the row's last
+//                               287 48 kHz denoised samples as on the device, and 4 words behind the
+//                               last: the stream's denoised rate, then zeros -- o_orate, written and
+//                               read by the host)
 struct BlobLayout {
   int n_channels, n_mach, seg_cap, fft_size, use_denoiser, rs_tail, ro_tail;
   long long pend_pad, o_ring, o_mach[kMaxBandCfg], rs_pad, o_rs, ro_pad, o_ro, words;
-  long long o_rate;  // per-stream rates only (0 otherwise)
+  long long o_rate;   // per-stream rates only (0 otherwise)
+  long long o_orate;  // per-stream denoised rates only (0 otherwise)
 };
 constexpr long long pad4(long long x) { return (x + 3) & ~3LL; }
 inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, const VadmArgs &v, int seg_cap,
-                              int rs_tail = 0, int ro_tail = 0, bool rs_rate = false) {
+                              int rs_tail = 0, int ro_tail = 0, bool rs_rate = false, bool ro_rate = false) {
   BlobLayout L{};
   L.n_channels = n_channels;
   L.n_mach = v.n;
@@ -84,6 +89,10 @@ inline BlobLayout blob_layout(int n_channels, int fft_size, int use_denoiser, co
   L.ro_pad = pad4(ro_tail);
   L.o_ro = o;
   o += (long long)n_channels * L.ro_pad;
+  if (ro_rate) {
+    L.o_orate = o;
+    o += 4;
+  }
   L.words = o;
   return L;
 }

@@ -32,6 +32,47 @@ struct ResampleOutArgs {
 // launch_resample_clear.)
 hipError_t launch_resample_out(const ResampleOutArgs &a, hipStream_t stream);
 
+// Per-stream rates (FVAD_DENOISED_RATE_PER_STREAM; DESIGN.md section 7,
+// "Per-stream denoised rates"): out is packed [tick][stream][channel]
+// [rate(stream) / 100], and
+//
+//   offsets  [stream + 1]      a stream's first sample inside a tick of out; [n_streams]: a tick's length
+//   lists    [stream]          the streams by rate, rate index ascending (rs::rate_index): rate i's are
+//                              lists[list_at[i] .. list_at[i + 1])
+//   tails    [stream][channel][rs::kMaxTailOut]   a row's last 287 48 kHz denoised samples, whatever
+//                              its rate; a launch at K taps reads the last K - 1 of them
+//
+// k_resample_out_ps is k_resample_out's unit body over one rate's list: a unit
+// is (tick, listed stream, channel), its 48 kHz row den[((tick * n_streams + s)
+// * n_channels + c) * 480], its outputs out[tick * tick_len + offsets[s] + c * n_out].
+struct ResampleOutPsArgs {
+  ResampleOutArgs r;  // taps, d: this launch's rate; n_streams: the engine's; tails, out as above
+  const int *list;
+  const long long *offsets;
+  long long tick_len;
+  int n_list;
+};
+// a push of a per-stream engine: the tables above on the device, the lists'
+// bounds and the rates' descriptions and tap tables (null at 48000) by value
+struct ResampleOutPsPush {
+  const float *den;
+  float *tails;
+  const int *ticks_valid;
+  float *out;
+  int n_streams, n_channels, n_ticks;
+  const int *lists;
+  const long long *offsets;
+  long long tick_len;
+  int list_at[rs::kPsRates + 1];
+  const float *taps[rs::kPsRates];
+  rs::DescOut d[rs::kPsRates];
+};
+// One k_resample_out_ps launch per listed rate present, in the variant
+// launch_resample_out picks for that rate; the 48000 streams through
+// k_resample_out_copy (their rows by the bits); then one k_resample_out_tail_ps
+// over every row.
+hipError_t launch_resample_out_ps(const ResampleOutPsPush &p, hipStream_t stream);
+
 // the [L][K] table of a listed rate (designed on first use, kept)
 const std::vector<float> &resample_out_table(const rs::DescOut &d);
 

@@ -40,7 +40,8 @@ class EngineConfig(C.Structure):
                 ("band_lo", C.c_int * MAX_BANDS), ("band_hi", C.c_int * MAX_BANDS), ("want_denoised", C.c_int),
                 ("mode", C.c_int), ("use_denoiser", C.c_int),
                 ("want_spectrum", C.c_int), ("spec_lo", C.c_int), ("spec_hi", C.c_int),
-                ("input_rate_max", C.c_int), ("denoised_rate", C.c_int), ("input_rate", C.c_int)]
+                ("denoised_rate_max", C.c_int), ("input_rate_max", C.c_int), ("denoised_rate", C.c_int),
+                ("input_rate", C.c_int)]
 
 
 class ResampleDesc(C.Structure):
@@ -306,6 +307,10 @@ SYMBOLS = [
     ("fvad_resample_out_host", C.c_int, [C.c_int, F32P, C.c_size_t, F32P, F32P]),
     ("fvad_engine_denoised_frame", C.c_int, [C.c_void_p]),
     ("fvad_engine_resample_out_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("fvad_denoised_layout", C.c_int, [I32P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    ("fvad_engine_denoised_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("fvad_engine_set_stream_denoised_rates", C.c_int, [C.c_void_p, I32P, C.c_int, I32P]),
+    ("fvad_engine_stream_denoised_rates", C.c_int, [C.c_void_p, I32P]),
     ("fvad_engine_spectrum_bins", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fvad_engine_fetch_spectrum", C.c_int, [C.c_void_p, C.c_int, F32P]),
     ("fvad_vadm_config_default", None, [C.c_void_p]),
@@ -513,6 +518,21 @@ def input_layout(rates, n_channels):
     return off
 
 
+DENOISED_RATE_PER_STREAM = -1
+
+
+def denoised_layout(rates, n_channels):
+    """fvad_denoised_layout (host only): offsets[n_streams + 1] (int64) of the packed
+    denoised PCM [tick][stream][channel][rate(stream) / 100] of an engine of per-stream
+    denoised rates -- offsets[s] is stream s's first sample inside a tick, offsets[-1] a
+    tick's length in samples."""
+    r = _ids(rates)
+    off = np.zeros(r.size + 1, np.int64)
+    _check(lib().fvad_denoised_layout(r.ctypes.data_as(I32P), r.size, n_channels,
+                                      off.ctypes.data_as(C.POINTER(C.c_int64))), "fvad_denoised_layout")
+    return off
+
+
 def resample_out_info(rate):
     """fvad_resample_out_info: the downsampler from 48 kHz to rate as a dict --
     L, M, taps_per_phase, frame_out and the delay in 48 kHz samples (host only)."""
@@ -569,7 +589,7 @@ class Engine:
 
     def __init__(self, model, n_streams, n_channels=2, device=0, max_ticks=100, fft_size=2048, bands=((4, 64),),
                  want_denoised=False, mode="staged", use_denoiser=True, input_rate=48000, spectrum=None,
-                 denoised_rate=48000, input_rate_max=0):
+                 denoised_rate=48000, input_rate_max=0, denoised_rate_max=0):
         cfg = EngineConfig()
         lib().fvad_engine_config_default(C.byref(cfg), n_streams, n_channels)
         cfg.device = device
@@ -592,7 +612,12 @@ class Engine:
         cfg.input_rate_max = input_rate_max
         # 8000 .. 96000: the denoised PCM comes back at that rate, downsampled on the device
         # (0 and 48000 both mean the 48 kHz signal: passed on as given)
-        cfg.denoised_rate = denoised_rate
+        # "per_stream": every stream's denoised PCM at its own rate, at most denoised_rate_max
+        # (set_stream_denoised_rates); out["denoised"] is then a list, one array per stream
+        self.per_stream_out = denoised_rate in ("per_stream", DENOISED_RATE_PER_STREAM)
+        cfg.denoised_rate = DENOISED_RATE_PER_STREAM if self.per_stream_out else denoised_rate
+        cfg.denoised_rate_max = denoised_rate_max
+        self._den_layouts, self._den_last = [], None  # the submitted pushes' layouts, oldest first; the last delivered
         # spectrum=(lo, hi): every completed window's magnitudes of the FFT-B bins lo..hi
         # are kept for fetch_spectrum, and push returns them as out["spectrum"]
         if spectrum is not None:
@@ -611,7 +636,8 @@ class Engine:
         # (a per-stream engine has none: input_layout())
         self.frame_in = None if self.per_stream else lib().fvad_engine_input_frame(h)
         # denoised samples per tick and channel: denoised_rate / 100 (480 at 48 kHz)
-        self.frame_out = lib().fvad_engine_denoised_frame(h)
+        # (an engine of per-stream denoised rates has none: denoised_layout())
+        self.frame_out = None if self.per_stream_out else lib().fvad_engine_denoised_frame(h)
         self.n_spec = lib().fvad_engine_spectrum_bins(h, None, None)  # 0: no tap
 
     def set_stream_rates(self, streams, rates):
@@ -636,6 +662,42 @@ class Engine:
         _check(lib().fvad_engine_input_layout(self.h, off.ctypes.data_as(C.POINTER(C.c_int64))),
                "fvad_engine_input_layout")
         return off
+
+    def set_stream_denoised_rates(self, streams, rates):
+        """fvad_engine_set_stream_denoised_rates: the listed streams' denoised PCM comes back at
+        the listed rates from the next submitted push on (their history, 48 kHz samples, is
+        kept: no onset transient); never waits for the device."""
+        a, r = _ids(streams), _ids(rates)
+        if a.size != r.size:
+            raise ValueError("rates: one per listed stream")
+        _check(lib().fvad_engine_set_stream_denoised_rates(self.h, a.ctypes.data_as(I32P), a.size,
+                                                           r.ctypes.data_as(I32P)),
+               "fvad_engine_set_stream_denoised_rates")
+
+    def stream_denoised_rates(self):
+        """The denoised rates the next submitted push will use (fvad_engine_stream_denoised_rates)."""
+        r = np.zeros(self.B, np.int32)
+        _check(lib().fvad_engine_stream_denoised_rates(self.h, r.ctypes.data_as(I32P)),
+               "fvad_engine_stream_denoised_rates")
+        return [int(v) for v in r]
+
+    def denoised_layout(self):
+        """fvad_engine_denoised_layout: denoised_layout() over the engine's current rates, the
+        layout the next submitted push is delivered in."""
+        off = np.zeros(self.B + 1, np.int64)
+        _check(lib().fvad_engine_denoised_layout(self.h, off.ctypes.data_as(C.POINTER(C.c_int64))),
+               "fvad_engine_denoised_layout")
+        return off
+
+    def unpack_denoised(self, flat, n_ticks, layout=None):
+        """The packed denoised PCM of n_ticks ticks, [tick][stream][channel][rate / 100], as one
+        [ticks][channels][rate / 100] array per stream.  layout: the offsets the push was
+        submitted under (default: the current denoised_layout())."""
+        off = self.denoised_layout() if layout is None else np.asarray(layout, np.int64)
+        tick = int(off[-1])
+        ticks = np.asarray(flat).reshape(-1)[: n_ticks * tick].reshape(n_ticks, tick)
+        return [ticks[:, off[s]:off[s + 1]].reshape(n_ticks, self.C, int(off[s + 1] - off[s]) // self.C)
+                for s in range(len(off) - 1)]
 
     def pack_input(self, rows):
         """rows: one [ticks][channels][rate / 100] array per stream, all float32 or all int16.
@@ -672,7 +734,9 @@ class Engine:
         o = {"vad": np.zeros((T, B), np.float32), "ratio": np.zeros((T, B), np.float32),
              "win_flag": np.zeros((T, B), np.int32), "win_ratio": np.zeros(ws, np.float32),
              "win_vad": np.zeros(ws, np.float32), "band": np.zeros(ws + (Ch, nb), np.float32)}
-        if denoised:
+        if denoised and self.per_stream_out:  # (packed: max_ticks-proof for any layout of the push)
+            o["denoised"] = np.zeros(T * B * Ch * (self.cfg.denoised_rate_max // 100), np.float32)
+        elif denoised:
             o["denoised"] = np.zeros((T, B, Ch, self.frame_out), np.float32)
         s = Outputs(fptr(o["vad"]), fptr(o["ratio"]), o["win_flag"].ctypes.data_as(I32P), fptr(o["win_ratio"]),
                     fptr(o["win_vad"]), fptr(o["band"]), fptr(o["denoised"]) if denoised else None)
@@ -688,6 +752,7 @@ class Engine:
             T = pcm.shape[0]
             assert pcm.shape[1:] == (self.B, self.C, self.frame_in), pcm.shape
         o, s = self._alloc_out(T, denoised)
+        lay = self.denoised_layout() if self.per_stream_out else None  # (the layout this push is delivered in)
         tv = None
         if ticks_valid is not None:
             tv = np.ascontiguousarray(ticks_valid, np.int32)
@@ -695,6 +760,10 @@ class Engine:
         _check(lib().fvad_engine_push_ex(self.h, fptr(pcm), T, tv.ctypes.data_as(I32P) if tv is not None else None,
                                          lt.ctypes.data_as(I32P) if lt is not None else None, C.byref(s)),
                "fvad_engine_push_ex")
+        if self.per_stream_out:
+            self._den_last = lay
+            if denoised:
+                o["denoised"] = self.unpack_denoised(o["denoised"], T, lay)
         if self.n_spec:
             o["spectrum"] = self.fetch_spectrum(T)
         return o
@@ -724,6 +793,8 @@ class Engine:
         self._sub_keep = tv
         _check(lib().fvad_engine_submit(self.h, fptr(pcm), T,
                                         tv.ctypes.data_as(I32P) if tv is not None else None), "fvad_engine_submit")
+        if self.per_stream_out:
+            self._den_layouts.append(self.denoised_layout())
 
     def input_slot_i16(self):
         """The pinned 16-bit input slot for the next submit_i16, as a
@@ -753,15 +824,26 @@ class Engine:
                                             tv.ctypes.data_as(I32P) if tv is not None else None,
                                             lt.ctypes.data_as(I32P) if lt is not None else None),
                "fvad_engine_submit_i16")
+        if self.per_stream_out:
+            self._den_layouts.append(self.denoised_layout())
 
     def collect(self, denoised=False, want=True):
         """Outputs of the oldest submitted push (fvad_engine_collect)."""
         if not want:
             _check(lib().fvad_engine_collect(self.h, None, None), "fvad_engine_collect")
+            if self.per_stream_out:
+                self._den_last = self._den_layouts.pop(0)
             return None
         o, s = self._alloc_out(self.max_ticks, denoised)
         n = C.c_int()
         _check(lib().fvad_engine_collect(self.h, C.byref(s), C.byref(n)), "fvad_engine_collect")
+        if self.per_stream_out:  # the layout this push was submitted under
+            self._den_last = self._den_layouts.pop(0)
+            den = o.pop("denoised", None)
+            o = {k: v[: n.value] for k, v in o.items()}
+            if den is not None:
+                o["denoised"] = self.unpack_denoised(den, n.value, self._den_last)
+            return o
         return {k: v[: n.value] for k, v in o.items()}
 
     def reset(self):
@@ -1038,6 +1120,8 @@ class Engine:
     def fetch(self, n_ticks, denoised=False):
         o, s = self._alloc_out(n_ticks, denoised)
         _check(lib().fvad_engine_fetch(self.h, n_ticks, C.byref(s)), "fvad_engine_fetch")
+        if denoised and self.per_stream_out:  # (the layout of the push launched last)
+            o["denoised"] = self.unpack_denoised(o["denoised"], n_ticks, self._den_last)
         return o
 
     def __del__(self):

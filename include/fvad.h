@@ -127,6 +127,12 @@ typedef struct {
    * last field; a binding that declares the struct itself must insert them here */
   /* ABI note (r5): the trailing `unsigned cu_mask[8]` of earlier builds was removed; a binding
    * compiled against them must drop it (fvad_engine_config_default fills every field) */
+  int denoised_rate_max; /* read only with denoised_rate = FVAD_DENOISED_RATE_PER_STREAM (section 2d-ps below):
+                         * the highest rate a stream's denoised PCM may take, 8000, 16000, 24000, 32000,
+                         * 44100, 48000 or 96000; it bounds the device's output rows and the pinned slots.
+                         * Default 0; any other value with another denoised_rate is FVAD_ERATE */
+  /* ABI note: denoised_rate_max stands in front of input_rate_max, denoised_rate and input_rate, which
+   * stay the struct's last three fields; a binding that declares the struct itself must insert it here */
   int input_rate_max;   /* read only with input_rate = FVAD_INPUT_RATE_PER_STREAM (section 2b-ps below): the
                          * highest rate a stream of the engine may take, 8000, 16000, 24000, 32000, 44100,
                          * 48000 or 96000; it bounds the raw staging buffers and the pinned slots.  Default
@@ -137,7 +143,9 @@ typedef struct {
                          * 48 kHz signal, or 8000, 16000, 24000, 32000, 44100, 96000 for an engine that
                          * brings every push's denoised rows to that rate on the device (section 2d below);
                          * FVAD_ERATE otherwise.  A listed rate needs want_denoised = 1 and use_denoiser = 1
-                         * (FVAD_EINVAL).  Independent of input_rate */
+                         * (FVAD_EINVAL), or FVAD_DENOISED_RATE_PER_STREAM for an engine whose streams each
+                         * get their denoised PCM at a rate of their own (section 2d-ps; want_denoised = 1 and
+                         * use_denoiser = 1, FVAD_EINVAL otherwise).  Independent of input_rate */
   /* ABI note: denoised_rate stands in front of input_rate, which stays the struct's last field; a
    * binding that declares the struct itself must insert it here */
   int input_rate;      /* the rate of the pushed samples: 0 or 48000 (default 0) for 48 kHz input, or 8000,
@@ -149,6 +157,8 @@ typedef struct {
 
 /* fvad_engine_config.input_rate: every stream has its own input rate (section 2b-ps) */
 #define FVAD_INPUT_RATE_PER_STREAM (-1)
+/* fvad_engine_config.denoised_rate: every stream has its own denoised rate (section 2d-ps) */
+#define FVAD_DENOISED_RATE_PER_STREAM (-1)
 
 /* staged: time-parallel frame kernels + a thin per-stream recurrence kernel;
  * fused: one workgroup runs every frame of a stream (lower memory); staged
@@ -262,7 +272,8 @@ typedef struct {
                            *     is a listed rate (its records then end with the output resampler's tails, behind
                            *     the input tails if there are any, per channel (K + 2) & ~3 words, K section 2d's
                            *     taps_per_phase, and config_hash covers the rate), 0 otherwise; a blob restores
-                           *     only into an engine of the same denoised_rate.  [2..12]: zero */
+                           *     only into an engine of the same denoised_rate; 0xFFFFFFFF: an engine of
+                           *     per-stream denoised rates, section 2d-ps.  [2..12]: zero */
 } fvad_stream_blob_header;
 int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams, int n);
 /* bytes a save of n streams needs (0 for a NULL engine or n < 0) */
@@ -290,7 +301,9 @@ typedef struct {
   float *band;         /* [ticks][streams][W][channels][n_bands] band sums (PipelineFFT.zig:99-112); 0 in
                         * slots without a window */
   float *denoised;     /* [ticks][streams][channels][480] normalised denoised PCM (want_denoised); with
-                        * denoised_rate [ticks][streams][channels][fvad_engine_denoised_frame(e)] (section 2d) */
+                        * denoised_rate [ticks][streams][channels][fvad_engine_denoised_frame(e)] (section 2d);
+                        * with per-stream denoised rates packed [ticks][streams][channels][rate(stream) / 100],
+                        * n_ticks * offsets[n_streams] floats (section 2d-ps) */
 } fvad_outputs;
 
 /* W, the window slots per (tick, stream) of fvad_outputs: 1 for fft_size >=
@@ -448,7 +461,8 @@ int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs);
  * taps, arithmetic and K - 1 samples of history).  A 48000 stream is not
  * resampled: float samples pass by their bits, 16-bit samples k as
  * (float)k * (1.0f / 32768.0f), and it has no history.  The input side only:
- * denoised_rate and clips are the engine's, as before.
+ * clips are the engine's, as before, and the denoised PCM's rate is a setting
+ * of its own, per engine (section 2d) or per stream (section 2d-ps).
  *
  * Layout.  A push is packed [tick][stream][channel][rate(stream) / 100]:
  * offsets[s] is stream s's first sample inside a tick, offsets[n_streams] a
@@ -593,6 +607,76 @@ int fvad_engine_denoised_frame(const fvad_engine *e);
  * (k_resample_out and the tail update behind it) and the pushes measured; a
  * sync point.  denoised_rate engines only (FVAD_EINVAL otherwise). */
 int fvad_engine_resample_out_times(fvad_engine *e, double *ms_avg, int *n_runs);
+
+/* ------------------------------------------------------------------ */
+/* 2d-ps. Per-stream denoised rates (denoised_rate = FVAD_DENOISED_RATE_PER_STREAM) */
+/* ------------------------------------------------------------------ */
+/* An engine created with denoised_rate = FVAD_DENOISED_RATE_PER_STREAM and
+ * denoised_rate_max = Rmax (want_denoised = 1 and use_denoiser = 1, FVAD_EINVAL
+ * otherwise -- want_denoised = 2 too; any mode; any input_rate, also
+ * FVAD_INPUT_RATE_PER_STREAM: the two sets of rates are independent) returns
+ * every stream's denoised PCM at that stream's own rate.  A stream's rate is
+ * one of 8000, 16000, 24000, 32000, 44100, 48000, 96000 and at most Rmax;
+ * every stream starts at Rmax.  A stream at a listed rate R is downsampled
+ * exactly as section 2d specifies for R (the same taps, arithmetic and K - 1
+ * samples of history); a 48000 stream's rows are the 48 kHz denoised rows bit
+ * for bit.  Ticks past a stream's ticks_valid are zeros.  Every other output,
+ * segment, event and clip is what a plain engine gives.
+ *
+ * Layout.  The denoised PCM is packed [tick][stream][channel][rate(stream) /
+ * 100]: offsets[s] is stream s's first sample inside a tick, offsets[n_streams]
+ * a tick's length in samples (fvad_denoised_layout, fvad_input_layout's
+ * arithmetic; fvad_engine_denoised_layout is the same over the engine's current
+ * rates: the layout the next submitted push will be delivered in).
+ * fvad_engine_push[_ex], fvad_engine_submit* / fvad_engine_collect,
+ * fvad_engine_fetch and the pinned output slots deliver n_ticks *
+ * offsets[n_streams] floats in that layout, which is what fvad_outputs.denoised
+ * must hold; the pinned slots and the device's output rows hold max_ticks *
+ * n_streams * n_channels * Rmax / 100.  A collected push is delivered in the
+ * layout the engine had when it was submitted: a host that changes rates with
+ * pushes in flight takes fvad_engine_denoised_layout at every submit and keeps
+ * it with the push.  fvad_engine_denoised_frame is FVAD_EINVAL: no single frame
+ * length exists.
+ *
+ * fvad_engine_set_stream_denoised_rates gives the n listed streams the listed
+ * rates.  Indices must be distinct and in range (FVAD_EINVAL), every rate a
+ * listed one or 48000 and at most Rmax (FVAD_ERATE); on either error nothing
+ * is touched.  n == 0 is a no-op.  It never waits for the device and takes
+ * effect between the pushes submitted before it and those submitted after it.
+ * On any other engine it is FVAD_EINVAL.  fvad_engine_stream_denoised_rates
+ * returns the rates the next submitted push will use.
+ *
+ * History.  Unlike the input side's, a row's history does not depend on its
+ * rate: it is the row's last 287 48 kHz denoised samples (K - 1 at 8 kHz, the
+ * longest), of which a stream at rate R reads the last K(R) - 1.  A change of
+ * rate therefore clears nothing and has no onset transient: the stream's first
+ * tick at the new rate R' is fvad_resample_out_host(R', ..., tail = the
+ * K(R') - 1 denoised samples before it).  48000 streams keep their history
+ * too, so they may take a listed rate later.  fvad_engine_reset and
+ * fvad_engine_reset_streams zero the history; the streams keep their rates.
+ *
+ * Stream blobs.  Such an engine's header carries reserved[1] = 0xFFFFFFFF; its
+ * records end -- behind the input tails and the input rate word, if the engine
+ * has them -- with n_channels rows of 288 words (the 287 history samples, then
+ * one zero word) and 4 words behind them (the stream's denoised rate, then
+ * zeros).  Such blobs move only between engines of per-stream denoised rates
+ * (FVAD_EFORMAT otherwise, as between engines of different denoised_rate);
+ * config_hash covers the marker, not denoised_rate_max.  A restore gives the
+ * target slot its record's rate, so the layout of the next push changes; a
+ * record whose rate exceeds the target's denoised_rate_max is FVAD_EFORMAT,
+ * found before anything is written.
+ *
+ * fvad_engine_resample_out_times works and reports all of a push's
+ * output-resample launches together.  A capture of the denoised rows
+ * (fvad_engine_enable_capture_ex with FVAD_CLIP_SOURCE_DENOISED) is FVAD_EINVAL
+ * on such an engine: clips at a stream's own rate do not exist.  A capture of
+ * the input, events and machines work unchanged. */
+/* host only (no GPU): offsets[n_streams + 1] of the packed layout above.
+ * FVAD_ERATE for a rate that is neither listed nor 48000 */
+int fvad_denoised_layout(const int *rates, int n_streams, int n_channels, int64_t *offsets /* n_streams + 1 */);
+int fvad_engine_denoised_layout(const fvad_engine *e, int64_t *offsets /* n_streams + 1 */);
+int fvad_engine_set_stream_denoised_rates(fvad_engine *e, const int *streams, int n, const int *rates);
+int fvad_engine_stream_denoised_rates(const fvad_engine *e, int *rates /* n_streams */);
 
 /* ------------------------------------------------------------------ */
 /* 3. Host mirror of the reference API (C++ above this ABI)             */
