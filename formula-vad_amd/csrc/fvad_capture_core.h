@@ -29,7 +29,7 @@ struct Cut {  // what of a due clip is delivered: [first, first + n)
 };
 
 // A capture of the denoised rows works in samples of the clip rate R = 48000
-// L / M (fvad_resample_core.h's describe_out; L = M = 1 for the 48 kHz
+// L / M (fvad_resample_core.h's describe, kOut; L = M = 1 for the 48 kHz
 // signals): 48 kHz sample x is covered from clip-rate sample ceil(x L / M) on,
 // so the segment [from, to) covers [to_rate(from), to_rate(to)), the r with
 // from <= r M / L < to.  x < 2^56 (L <= 147).  A stream's position, a multiple

@@ -243,7 +243,7 @@ extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_
   const bool den = cc->source == FVAD_CLIP_SOURCE_DENOISED, s16 = cc->format == FVAD_CLIP_S16;
   if (den && !e->cfg.want_denoised)
     return fail(FVAD_EINVAL, "a capture of the denoised rows needs an engine created with want_denoised");
-  if (den && e->ro && e->ro->ps)  // (clips at a stream's own rate: not built)
+  if (den && e->ro && e->ro->plan.on())  // (clips at a stream's own rate: not built)
     return fail(FVAD_EINVAL, "a capture of the denoised rows is not available with per-stream denoised rates");
   if (e->vadm.n == 0 || !e->events_on)
     return fail(FVAD_EINVAL, "clip capture needs fvad_engine_attach_vadm and fvad_engine_enable_events first");
@@ -267,7 +267,7 @@ extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_
   c->format = cc->format;
   if (den && e->ro) {  // the engine's denoised_rate: the rows k_resample_out writes
     c->rate = e->ro->d.rate;
-    c->frame = e->ro->d.n_out;
+    c->frame = e->ro->d.n;
     c->L = (unsigned)e->ro->d.L;
     c->M = (unsigned)e->ro->d.M;
   }
@@ -384,8 +384,8 @@ extern "C" void fvad_pcm_f32_to_s16(const float *x, int16_t *q, size_t n) {
 extern "C" int fvad_clip_range(int rate, uint64_t from48, uint64_t to48, uint64_t *first, uint64_t *end) {
   unsigned L = 1, M = 1;
   if (rate != 48000) {
-    fvad::rs::DescOut d{};
-    if (!fvad::rs::describe_out(rate, d)) return fail(FVAD_ERATE, "rate must be 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
+    fvad::rs::Desc d{};
+    if (!fvad::rs::describe(rate, fvad::rs::Dir::kOut, d)) return fail(FVAD_ERATE, "rate must be 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
     L = (unsigned)d.L;
     M = (unsigned)d.M;
   }

@@ -197,14 +197,7 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
   if (e->d_work) HIP_TRY(hipMemsetAsync(e->d_work.get(), 0, sizeof(unsigned) * fvad::kWorkCounters, e->stream.get()));
   HIP_TRY(hipMemsetAsync(e->d_ring.get(), 0,
                          sizeof(float) * (size_t)e->ring_len * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
-  if (e->rs)  // (their owner, the prep stream, is idle: synchronised above)
-    HIP_TRY(hipMemsetAsync(e->rs->tails.get(), 0,
-                           sizeof(float) * (size_t)resample_tail_words(e) * e->cfg.n_channels * e->cfg.n_streams,
-                           e->stream.get()));
-  if (e->ro)
-    HIP_TRY(hipMemsetAsync(e->ro->tails.get(), 0,
-                           sizeof(float) * (size_t)resample_out_tail_words(e) * e->cfg.n_channels * e->cfg.n_streams,
-                           e->stream.get()));
+  if (const int rc = resample_reset(e)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
   return FVAD_OK;
 }
@@ -222,6 +215,19 @@ void fill_bands(const fvad_engine_config &c, int *band_lo, int *band_hi, int *lo
   }
   *lo_all = lo;
   *hi_all = hi;
+}
+
+// fvad_engine_create's check of input_rate / denoised_rate and its *_rate_max:
+// per-stream, rate_max is a listed rate or 48000; otherwise rate_max is 0 and
+// the rate, when it is not 0 or 48000, a listed one, described in d
+struct RateTexts {
+  const char *max_off_list, *max_unread, *rate_off_list;
+};
+int check_rate(int rate, int rate_max, bool per_stream, fvad::rs::Dir dir, fvad::rs::Desc &d, const RateTexts &t) {
+  if (per_stream) return fvad::rs::rate_index(rate_max) < 0 ? fail(FVAD_ERATE, t.max_off_list) : FVAD_OK;
+  if (rate_max != 0) return fail(FVAD_ERATE, t.max_unread);
+  if (rate != 0 && rate != 48000 && !fvad::rs::describe(rate, dir, d)) return fail(FVAD_ERATE, t.rate_off_list);
+  return FVAD_OK;
 }
 
 }  // namespace
@@ -250,34 +256,30 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
   if (!cfg || !model || !out) return fail(FVAD_EINVAL, "null argument");
   const fvad_engine_config &c = *cfg;
   if (c.sample_rate != 48000) return fail(FVAD_ERATE, "only 48 kHz is supported (VAD.zig:101-104)");
-  // input_rate: 0 or 48000 for none, or a rate k_resample brings to 48 kHz
-  const bool resample = c.input_rate != 0 && c.input_rate != 48000;
+  // input_rate: 0 or 48000 for none, or a rate k_resample brings to 48 kHz;
   // FVAD_INPUT_RATE_PER_STREAM: every stream its own rate, up to input_rate_max
+  const bool resample = c.input_rate != 0 && c.input_rate != 48000;
   const bool per_stream = c.input_rate == FVAD_INPUT_RATE_PER_STREAM;
   fvad::rs::Desc rd{};
-  if (per_stream) {
-    if (fvad::rs::rate_index(c.input_rate_max) < 0)
-      return fail(FVAD_ERATE, "input_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000");
-  } else if (c.input_rate_max != 0) {
-    return fail(FVAD_ERATE, "input_rate_max is read only with input_rate = FVAD_INPUT_RATE_PER_STREAM");
-  } else if (resample && !fvad::rs::describe(c.input_rate, rd)) {
-    return fail(FVAD_ERATE, "input_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
-  }
-  // denoised_rate: 0 or 48000 for the 48 kHz signal, or a rate k_resample_out brings it to
-  const bool resample_out = c.denoised_rate != 0 && c.denoised_rate != 48000;
+  if (const int rc = check_rate(c.input_rate, c.input_rate_max, per_stream, fvad::rs::Dir::kIn, rd,
+                                {"input_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000",
+                                 "input_rate_max is read only with input_rate = FVAD_INPUT_RATE_PER_STREAM",
+                                 "input_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000"}))
+    return rc;
+  // denoised_rate: 0 or 48000 for the 48 kHz signal, or a rate k_resample_out brings it to;
   // FVAD_DENOISED_RATE_PER_STREAM: every stream its own rate, up to denoised_rate_max
+  const bool resample_out = c.denoised_rate != 0 && c.denoised_rate != 48000;
   const bool per_stream_out = c.denoised_rate == FVAD_DENOISED_RATE_PER_STREAM;
-  fvad::rs::DescOut od{};
+  fvad::rs::Desc od{};
+  if (const int rc = check_rate(c.denoised_rate, c.denoised_rate_max, per_stream_out, fvad::rs::Dir::kOut, od,
+                                {"denoised_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000",
+                                 "denoised_rate_max is read only with denoised_rate = FVAD_DENOISED_RATE_PER_STREAM",
+                                 "denoised_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000"}))
+    return rc;
   if (per_stream_out) {
-    if (fvad::rs::rate_index(c.denoised_rate_max) < 0)
-      return fail(FVAD_ERATE, "denoised_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000");
     if (c.want_denoised != 1 || !c.use_denoiser)
       return fail(FVAD_EINVAL, "per-stream denoised rates need want_denoised = 1 and use_denoiser = 1");
     if (c.max_ticks > 65535) return fail(FVAD_EINVAL, "per-stream denoised rates: max_ticks <= 65535 (a grid dimension)");
-  } else if (c.denoised_rate_max != 0) {
-    return fail(FVAD_ERATE, "denoised_rate_max is read only with denoised_rate = FVAD_DENOISED_RATE_PER_STREAM");
-  } else if (resample_out && !fvad::rs::describe_out(c.denoised_rate, od)) {
-    return fail(FVAD_ERATE, "denoised_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000");
   }
   if (resample_out && !per_stream_out && (!c.want_denoised || !c.use_denoiser))
     return fail(FVAD_EINVAL, "denoised_rate needs want_denoised = 1 and use_denoiser = 1");
@@ -446,20 +448,8 @@ extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_mode
     e->n_spec = c.spec_hi - c.spec_lo + 1;
     if ((rc = make_dev(e->d_spec, T * B * e->wpt * C * (size_t)e->n_spec))) return bail(rc);
   }
-  if (resample) {
-    e->rs.reset(new Resample());
-    e->rs->d = rd;
-    e->rs->ps = per_stream;
-    e->rs->rate_max = c.input_rate_max;
-    if ((rc = resample_make(e))) return bail(rc);
-  }
-  if (resample_out) {
-    e->ro.reset(new ResampleOut());
-    e->ro->d = od;
-    e->ro->ps = per_stream_out;
-    e->ro->rate_max = c.denoised_rate_max;
-    if ((rc = resample_out_make(e))) return bail(rc);
-  }
+  if (resample && (rc = resample_make(e, rd, c.input_rate_max))) return bail(rc);
+  if (resample_out && (rc = resample_out_make(e, od, c.denoised_rate_max))) return bail(rc);
   if ((rc = fvad_engine_reset(e))) return bail(rc);
   *out = e;
   return FVAD_OK;
@@ -987,14 +977,8 @@ extern "C" int fvad_engine_clear_times(fvad_engine *e) {
   }
   e->et_ms_sum = 0;
   e->et_timed = 0;
-  if (e->rs) {
-    e->rs->ms_sum = 0;
-    e->rs->n_timed = 0;
-  }
-  if (e->ro) {
-    e->ro->ms_sum = 0;
-    e->ro->n_timed = 0;
-  }
+  if (e->rs) e->rs->tm.clear();
+  if (e->ro) e->ro->tm.clear();
   if (e->cap)
     for (int k = 0; k < 2; k++) {
       e->cap->ms_sum[k] = 0;

@@ -1,6 +1,7 @@
 // The batched engine's private parts: struct fvad_engine and the functions its
 // translation units share (fvad_engine.cpp, fvad_engine_ingest.cpp,
-// fvad_engine_vadm.cpp, fvad_engine_lifecycle.cpp, fvad_capture_host.cpp).
+// fvad_engine_rates.cpp, fvad_engine_vadm.cpp, fvad_engine_lifecycle.cpp,
+// fvad_capture_host.cpp).
 // Host code only: not installed, and no .hip file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -129,28 +130,50 @@ struct Capture {
   int n_timed[2] = {};
 };
 
-// Input resampling (fvad_engine_config.input_rate; DESIGN.md section 7, "Input
-// resampling"): everything it owns, made by fvad_engine_create; an engine of
-// 48 kHz input has none of it.
-struct Resample {
-  rs::Desc d{};
-  dev_ptr<float> taps;    // [L][K]
-  dev_ptr<float> tails;   // [s][c][K - 1], the prep stream's (fused: the engine stream's)
-  // the push as the host sent it, float or int16: the parity of d_pcm_b,
-  // released by the same ev_in_free (recorded behind the reader of d_pcm,
-  // which is behind k_resample)
-  dev_ptr<float> raw[2];  // max_ticks * B * C * n_in words each
-  bool in16 = false;      // the push being launched holds int16 samples
-  EventTimer tm[2];       // the resample launches of a push, alternately
-  int slot = 0;
+// EventTimers round the launches of one kind, taken in turn and read without
+// waiting (a sample still running when its timer comes round again is
+// dropped): the two resamplers' launches of a push.
+struct TimerRing {
+  static constexpr int kMax = 4;
+  EventTimer tm[kMax];
+  int n = 0, slot = 0;
   double ms_sum = 0;
   int n_timed = 0;
-  // Per-stream rates (input_rate = FVAD_INPUT_RATE_PER_STREAM; DESIGN.md
-  // section 7, "Per-stream rates"); none of it on a fixed-rate engine.  d,
-  // taps stay empty; tails are [s][c][rs::kMaxTail]; raw holds max_ticks * B *
-  // C * rate_max / 100 words.
-  bool ps = false;
-  int rate_max = 0;
+  int create(int slots) {
+    for (n = 0; n < slots; n++)
+      if (const int rc = tm[n].create()) return rc;
+    return FVAD_OK;
+  }
+  // the next timer: what it held is collected, then it begins (n > 0: the
+  // resamplers' make functions create the ring, and an engine whose create
+  // failed is destroyed before a push)
+  int begin(hipStream_t s) {
+    EventTimer &t = tm[slot = (slot + 1) % n];
+    if (const int rc = t.collect(ms_sum, n_timed)) return rc;
+    return t.begin(s);
+  }
+  int end(hipStream_t s) { return tm[slot].end(s); }
+  // (after a sync: every pending sample is complete)
+  int read(double *ms_avg, int *n_runs) {
+    for (int i = 0; i < n; i++)
+      if (const int rc = tm[i].collect(ms_sum, n_timed)) return rc;
+    *ms_avg = n_timed ? ms_sum / n_timed : 0.0;
+    if (n_runs) *n_runs = n_timed;
+    return FVAD_OK;
+  }
+  void clear() {
+    ms_sum = 0;
+    n_timed = 0;
+  }
+};
+
+// Per-stream rates of either resampler (input_rate = FVAD_INPUT_RATE_PER_STREAM,
+// denoised_rate = FVAD_DENOISED_RATE_PER_STREAM; DESIGN.md section 7,
+// "Per-stream rates"): each stream's rate, the layout of a packed push and the
+// device tables a push's launches read.  Empty (on() false) on a fixed-rate
+// engine.  fvad_engine_rates.cpp.
+struct RatePlan {
+  int n_streams = 0, n_channels = 0, rate_max = 0;
   rs::Desc dr[rs::kPsRates]{};          // by rate index (48000: the identity)
   dev_ptr<float> taps_r[rs::kPsRates];  // the tables of the rates up to rate_max (none at 48000)
   // what the next submitted push uses: each stream's rate index, the layout
@@ -159,14 +182,15 @@ struct Resample {
   std::vector<long long> offsets;  // [B + 1]
   int list_at[rs::kPsRates + 1] = {};
   uint64_t gen = 1;
-  // The device tables of the raw buffer of each parity, [offsets (B + 1) |
-  // rate_idx (B) | lists (B)] (the latter two as int), and the generation
-  // they hold.  A push whose parity's tables are stale copies them from the
-  // next pinned staging row on the resample stream, ahead of its launches:
-  // stream order keeps an in-flight push's tables until its kernels are
-  // done.  stage_ev[i]: the copy out of row i, waited for only should the ring
-  // come round to a row whose copy has not run (more than kStage table copies
-  // queued: not with submit / collect, FVAD_MAX_IN_FLIGHT pushes deep)
+  // The device tables, [offsets (B + 1) | rate_idx (B) | lists (B)] (the
+  // latter two as int), in one or two copies -- the input side keeps one per
+  // raw buffer parity, the output side one -- and the generation each holds.  A
+  // push that finds its copy stale (sync) copies it from the next pinned
+  // staging row on its stream, ahead of its launches: stream order keeps an
+  // in-flight push's tables until its kernels are done.  stage_ev[i]: the
+  // copy out of row i, waited for only should the ring come round to a row
+  // whose copy has not run (more than kStage table copies queued: not with
+  // submit / collect, FVAD_MAX_IN_FLIGHT pushes deep)
   static constexpr int kStage = 8;
   dev_ptr<long long> tab[2];
   uint64_t tab_gen[2] = {0, 0};
@@ -174,9 +198,49 @@ struct Resample {
   event_ptr stage_ev[kStage];
   bool stage_used[kStage] = {};
   int stage_next = 0;
+
+  bool on() const { return rate_max != 0; }
   size_t tab_words() const { return offsets.size() + (offsets.size() - 1); }  // (2 B ints are B words)
-  int frame(int s) const { return dr[ridx[s]].n_in; }
+  int frame(int s) const { return dr[ridx[s]].n; }
+  int rate(int s) const { return dr[ridx[s]].rate; }
   long long tick_len() const { return offsets.back(); }
+  // fvad_engine_create's part: the descriptions and device tap tables of the
+  // rates up to rate_max, every stream at rate_max, n_tab copies of the
+  // device tables and the staging ring
+  int make(rs::Dir dir, int n_streams, int n_channels, int rate_max, int n_tab);
+  // the layout and the lists of the current ridx (gen advances)
+  void relayout();
+  // a change of rates in two steps, so that a caller can stand between them:
+  // check that each of n rates is a listed rate or 48000 up to rate_max
+  // (FVAD_ERATE with bad_rate otherwise), then streams[i] takes rates[i]
+  int check(int n, const int *rates, const char *bad_rate) const;
+  void apply(const int *streams, int n, const int *rates);
+  // copy `copy` of the device tables follows the host's, on stream st
+  int sync(int copy, hipStream_t st);
+  // a push's tables: copy `copy` on the device, the rest by value
+  void fill(PsTables &t, int copy) const;
+  // a stream blob's rate word of a stream, and a restored one's rate index:
+  // 0, 1 off the list, 2 above rate_max
+  uint32_t save_rate(int stream) const { return (uint32_t)rate(stream); }
+  int check_restored_rate(uint32_t word, int *ri) const;
+};
+
+// Input resampling (fvad_engine_config.input_rate; DESIGN.md section 7, "Input
+// resampling"): everything it owns, made by fvad_engine_create; an engine of
+// 48 kHz input has none of it.
+struct Resample {
+  rs::Desc d{};           // fixed rate; empty with per-stream rates, as taps
+  dev_ptr<float> taps;    // [L][K]
+  // [s][c][K - 1], per-stream rates: [s][c][rs::kMaxTail]; the prep stream's
+  // (fused: the engine stream's)
+  dev_ptr<float> tails;
+  // the push as the host sent it, float or int16: the parity of d_pcm_b,
+  // released by the same ev_in_free (recorded behind the reader of d_pcm,
+  // which is behind k_resample)
+  dev_ptr<float> raw[2];  // max_ticks * B * C * (rate or rate_max) / 100 words each
+  bool in16 = false;      // the push being launched holds int16 samples
+  TimerRing tm;           // the resample launches of a push: two timers
+  RatePlan plan;          // per-stream rates; tables by raw buffer parity
 };
 
 // The denoised PCM at another rate (fvad_engine_config.denoised_rate;
@@ -184,47 +248,19 @@ struct Resample {
 // made by fvad_engine_create; an engine that returns the 48 kHz signal has
 // none of it.  All of it is the engine stream's.
 struct ResampleOut {
-  rs::DescOut d{};
+  rs::Desc d{};          // fixed rate; empty with per-stream rates, as taps
   dev_ptr<float> taps;   // [L][K]
-  dev_ptr<float> tails;  // [s][c][K - 1]
-  dev_ptr<float> out;    // d_den_out: [tick][s][c][n_out], max_ticks ticks
-  EventTimer tm[4];      // the two launches of a push, in turn (three pushes in flight and their copies)
-  int slot = 0;
-  double ms_sum = 0;
-  int n_timed = 0;
-  // Per-stream rates (denoised_rate = FVAD_DENOISED_RATE_PER_STREAM; DESIGN.md
-  // section 7, "Per-stream denoised rates"); none of it on a fixed-rate
-  // engine.  d, taps stay empty; tails are [s][c][rs::kMaxTailOut], a row's
-  // last 48 kHz denoised samples whatever its rate; out holds max_ticks * B *
-  // C * rate_max / 100 words, packed [tick][s][c][rate(s) / 100].
-  bool ps = false;
-  int rate_max = 0;
-  rs::DescOut dr[rs::kPsRates]{};       // by rate index (48000: only its rate and n_out)
-  dev_ptr<float> taps_r[rs::kPsRates];  // the tables of the rates up to rate_max (none at 48000)
-  // what the next submitted push uses: each stream's rate index, the layout
-  // (fvad_denoised_layout) and the streams by rate; gen counts their changes
-  std::vector<int> ridx, lists;
-  std::vector<long long> offsets;  // [B + 1]
-  int list_at[rs::kPsRates + 1] = {};
-  uint64_t gen = 1;
+  // [s][c][K - 1]; per-stream rates: [s][c][rs::kMaxTailOut], a row's last
+  // 48 kHz denoised samples whatever its rate
+  dev_ptr<float> tails;
+  // d_den_out: [tick][s][c][n], max_ticks ticks; per-stream rates: packed
+  // [tick][s][c][rate(s) / 100], max_ticks * B * C * rate_max / 100 words
+  dev_ptr<float> out;
+  TimerRing tm;          // the launches of a push: four timers (three pushes in flight and their copies)
+  RatePlan plan;         // per-stream rates; one copy of the tables
   // a tick's length of the push launched last: what fetch and the D2H copies
   // of that push move (the layout may have changed since)
   long long pushed_len = 0;
-  // The device tables [offsets (B + 1) | lists (B, as int)] and the generation
-  // they hold: one copy, the engine stream's.  A push that finds them stale
-  // copies them from the next pinned staging row on the engine stream, ahead
-  // of its launches and behind those of every push before it.  stage_ev[i]:
-  // the copy out of row i, waited for only should the ring come round to a row
-  // whose copy has not run (as Resample::stage_ev)
-  static constexpr int kStage = 8;
-  dev_ptr<long long> tab;
-  uint64_t tab_gen = 0;
-  pinned_ptr<long long> stage;
-  event_ptr stage_ev[kStage];
-  bool stage_used[kStage] = {};
-  int stage_next = 0;
-  size_t tab_words() const { return offsets.size() + offsets.size() / 2; }  // (B ints fit (B + 1) / 2 words)
-  long long tick_len() const { return offsets.back(); }
 };
 }  // namespace eng
 }  // namespace fvad
@@ -484,36 +520,36 @@ int release_input(fvad_engine *e);
 int check_ticks(const fvad_engine *e, const int32_t *ticks_valid, int n_ticks);
 int tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, const int32_t *last, int n_ticks,
                std::vector<int32_t> &tt);
-// input resampling: samples per tick and channel of a push, where its H2D
-// copy goes, the stream that owns the tails, and the push's resample launches
+// fvad_engine_rates.cpp: the two resamplers' host side.  Input: samples per
+// tick and channel of a push, where its H2D copy goes, the stream that owns
+// the tails, and the push's resample launches
 int input_frame(const fvad_engine *e);
 // per-stream rates: the largest frame (what the staging is sized by) and the
 // samples of a push of n_ticks in the current layout
 int input_frame_max(const fvad_engine *e);
 size_t push_samples(const fvad_engine *e, int n_ticks);
-// words of a row's tail: K - 1, rs::kMaxTail with per-stream rates
-int resample_tail_words(const fvad_engine *e);
-// per-stream rates: the layout and the lists of the current ridx (gen advances)
-void resample_relayout(fvad_engine *e);
 void *input_target(const fvad_engine *e);
 hipStream_t resample_stream(const fvad_engine *e);
-int resample_make(fvad_engine *e);
+int resample_make(fvad_engine *e, const rs::Desc &d, int rate_max);
 int resample_push(fvad_engine *e, int n_ticks, const int *d_ticks);
 // the denoised PCM at another rate: samples per tick and channel of the
 // denoised rows the host receives, the device rows they are copied from, and
-// the push's two launches on the engine stream (behind its last writer of d_den)
+// the push's launches on the engine stream (behind its last writer of d_den)
 int denoised_frame(const fvad_engine *e);
 const float *denoised_source(const fvad_engine *e);
-// per-stream denoised rates: the largest frame (what the slots are sized by),
-// the denoised floats of the push launched last (n_ticks of it), the words of
-// a row's history (K - 1, rs::kMaxTailOut with per-stream rates), and the
-// layout and the lists of the current ridx (gen advances)
+// per-stream denoised rates: the largest frame (what the slots are sized by)
+// and the denoised floats of the push launched last (n_ticks of it)
 int denoised_frame_max(const fvad_engine *e);
 size_t denoised_floats(const fvad_engine *e, int n_ticks);
-int resample_out_tail_words(const fvad_engine *e);
-void resample_out_relayout(fvad_engine *e);
-int resample_out_make(fvad_engine *e);
+int resample_out_make(fvad_engine *e, const rs::Desc &d, int rate_max);
 int resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks);
+// words of a row's tail of either resampler: K - 1; rs::kMaxTail /
+// rs::kMaxTailOut with per-stream rates
+int resample_tail_words(const fvad_engine *e, rs::Dir dir);
+// both resamplers' tails become zeros: every stream's on the engine stream
+// (fvad_engine_reset), the listed streams' on the streams that own them
+int resample_reset(fvad_engine *e);
+int resample_reset_streams(fvad_engine *e, const IdList &ids);
 // fvad_engine_vadm.cpp
 int vadm_reset(fvad_engine *e);
 int vadm_flush(fvad_engine *e, bool fast = true);

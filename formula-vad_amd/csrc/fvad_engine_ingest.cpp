@@ -34,480 +34,6 @@ int fvad::eng::release_input(fvad_engine *e) {
   return FVAD_OK;
 }
 
-// ---------------------------------------------------------------------------
-// Input resampling (input_rate set; fvad_resample.h): the host's copies go to
-// the raw buffer of d_pcm's parity, k_resample writes d_pcm from it
-// ---------------------------------------------------------------------------
-int fvad::eng::input_frame(const fvad_engine *e) { return e->rs ? e->rs->d.n_in : fvad::kFrame; }
-
-int fvad::eng::input_frame_max(const fvad_engine *e) {
-  return e->rs && e->rs->ps ? e->rs->rate_max / 100 : input_frame(e);
-}
-
-size_t fvad::eng::push_samples(const fvad_engine *e, int n_ticks) {
-  if (e->rs && e->rs->ps) return (size_t)n_ticks * (size_t)e->rs->tick_len();
-  return (size_t)n_ticks * e->cfg.n_streams * e->cfg.n_channels * input_frame(e);
-}
-
-int fvad::eng::resample_tail_words(const fvad_engine *e) { return e->rs->ps ? fvad::rs::kMaxTail : e->rs->d.K - 1; }
-
-// fvad_input_layout over rate indices (all valid)
-static void layout_of_indices(const int *ridx, int n_streams, int n_channels, long long *offsets) {
-  long long o = 0;
-  for (int s = 0; s < n_streams; s++) {
-    offsets[s] = o;
-    o += (long long)n_channels * (fvad::rs::index_rate(ridx[s]) / 100);
-  }
-  offsets[n_streams] = o;
-}
-
-void fvad::eng::resample_relayout(fvad_engine *e) {
-  Resample &r = *e->rs;
-  const int B = e->cfg.n_streams;
-  layout_of_indices(r.ridx.data(), B, e->cfg.n_channels, r.offsets.data());
-  int n = 0;
-  for (int i = 0; i < fvad::rs::kPsRates; i++) {
-    r.list_at[i] = n;
-    for (int s = 0; s < B; s++)
-      if (r.ridx[s] == i) r.lists[n++] = s;
-  }
-  r.list_at[fvad::rs::kPsRates] = n;
-  r.gen++;
-}
-
-// where the H2D copy of the push about to launch goes (after input_buffer)
-void *fvad::eng::input_target(const fvad_engine *e) {
-  return e->rs ? static_cast<void *>(e->rs->raw[e->in_next].get()) : static_cast<void *>(e->d_pcm);
-}
-
-// the tails' owner: k_resample runs there, ahead of the push's first reader
-// of d_pcm (staged: the prep stream, with and without the denoiser)
-hipStream_t fvad::eng::resample_stream(const fvad_engine *e) {
-  return e->cfg.mode != FVAD_MODE_FUSED ? e->pstream : e->stream.get();
-}
-
-// fvad_engine_create's part: the table, the tails (zeroed by the reset that
-// follows) and the raw staging
-int fvad::eng::resample_make(fvad_engine *e) {
-  Resample &r = *e->rs;
-  const fvad_engine_config &c = e->cfg;
-  if (r.ps) {
-    // the tables of every rate up to rate_max, each stream at rate_max, the
-    // raw staging and the slots sized by it
-    const size_t B = c.n_streams, rows = B * c.n_channels, raw = (size_t)c.max_ticks * rows * (r.rate_max / 100);
-    int rc;
-    for (int i = 0; i < fvad::rs::kPsRates; i++) {
-      fvad::rs::describe_ps(fvad::rs::index_rate(i), r.dr[i]);
-      if (i == fvad::rs::kPsIndex48 || r.dr[i].rate > r.rate_max) continue;
-      const std::vector<float> &taps = fvad::resample_table(r.dr[i]);
-      if ((rc = fvad::make_dev(r.taps_r[i], taps.size()))) return rc;
-      HIP_TRY(hipMemcpy(r.taps_r[i].get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    r.ridx.assign(B, fvad::rs::rate_index(r.rate_max));
-    r.lists.resize(B);
-    r.offsets.resize(B + 1);
-    resample_relayout(e);
-    if ((rc = fvad::make_dev(r.tails, rows * fvad::rs::kMaxTail)) || (rc = fvad::make_dev(r.raw[0], raw)) ||
-        (rc = fvad::make_dev(r.raw[1], raw)) || (rc = fvad::make_dev(r.tab[0], r.tab_words())) ||
-        (rc = fvad::make_dev(r.tab[1], r.tab_words())) ||
-        (rc = fvad::make_pinned(r.stage, (size_t)Resample::kStage * r.tab_words())) || (rc = r.tm[0].create()) ||
-        (rc = r.tm[1].create()))
-      return rc;
-    for (fvad::event_ptr &ev : r.stage_ev)
-      if ((rc = fvad::make_event(ev))) return rc;
-    return FVAD_OK;
-  }
-  const std::vector<float> &taps = fvad::resample_table(r.d);
-  const size_t rows = (size_t)c.n_streams * c.n_channels;
-  int rc;
-  if ((rc = fvad::make_dev(r.taps, taps.size())) || (rc = fvad::make_dev(r.tails, rows * (r.d.K - 1))) ||
-      (rc = fvad::make_dev(r.raw[0], (size_t)c.max_ticks * rows * r.d.n_in)) ||
-      (rc = fvad::make_dev(r.raw[1], (size_t)c.max_ticks * rows * r.d.n_in)) || (rc = r.tm[0].create()) ||
-      (rc = r.tm[1].create()))
-    return rc;
-  HIP_TRY(hipMemcpy(r.taps.get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
-  return FVAD_OK;
-}
-
-// the resample launches of the push about to launch, timed without waiting
-// (a sample still running when its timer comes round again is dropped)
-namespace {
-// the tables of the push's parity, when a change of rates has overtaken them
-int resample_tables(fvad_engine *e, int ib, hipStream_t st) {
-  Resample &r = *e->rs;
-  if (r.tab_gen[ib] == r.gen) return FVAD_OK;
-  const int B = e->cfg.n_streams, i = r.stage_next;
-  r.stage_next = (i + 1) % Resample::kStage;
-  if (r.stage_used[i]) HIP_TRY(hipEventSynchronize(r.stage_ev[i].get()));  // (complete long ago: see Resample)
-  long long *row = r.stage.get() + (size_t)i * r.tab_words();
-  std::memcpy(row, r.offsets.data(), sizeof(long long) * (size_t)(B + 1));
-  int *ints = reinterpret_cast<int *>(row + B + 1);
-  std::memcpy(ints, r.ridx.data(), sizeof(int) * (size_t)B);
-  std::memcpy(ints + B, r.lists.data(), sizeof(int) * (size_t)B);
-  HIP_TRY(hipMemcpyAsync(r.tab[ib].get(), row, r.tab_words() * sizeof(long long), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(r.stage_ev[i].get(), st));
-  r.stage_used[i] = true;
-  r.tab_gen[ib] = r.gen;
-  return FVAD_OK;
-}
-
-int resample_push_ps(fvad_engine *e, int n_ticks, const int *d_ticks) {
-  Resample &r = *e->rs;
-  const int ib = e->in_next, B = e->cfg.n_streams;
-  hipStream_t st = resample_stream(e);
-  int rc;
-  if ((rc = resample_tables(e, ib, st))) return rc;
-  fvad::ResamplePsPush p{};
-  p.raw = r.raw[ib].get();
-  p.tails = r.tails.get();
-  p.ticks_valid = d_ticks;
-  p.out = e->d_pcm;
-  p.n_streams = B;
-  p.n_channels = e->cfg.n_channels;
-  p.n_ticks = n_ticks;
-  p.in16 = r.in16;
-  p.offsets = r.tab[ib].get();
-  p.rate_idx = reinterpret_cast<const int *>(r.tab[ib].get() + B + 1);
-  p.lists = p.rate_idx + B;
-  p.tick_len = r.tick_len();
-  for (int i = 0; i <= fvad::rs::kPsRates; i++) p.list_at[i] = r.list_at[i];
-  for (int i = 0; i < fvad::rs::kPsRates; i++) {
-    p.taps[i] = r.taps_r[i].get();
-    p.d[i] = r.dr[i];
-  }
-  EventTimer &tm = r.tm[r.slot ^= 1];
-  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
-  HIP_TRY(fvad::launch_resample_ps(p, st));
-  return tm.end(st);
-}
-}  // namespace
-
-int fvad::eng::resample_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
-  Resample &r = *e->rs;
-  if (r.ps) return resample_push_ps(e, n_ticks, d_ticks);
-  fvad::ResampleArgs a{};
-  a.raw = r.raw[e->in_next].get();
-  a.taps = r.taps.get();
-  a.tails = r.tails.get();
-  a.ticks_valid = d_ticks;
-  a.out = e->d_pcm;
-  a.n_streams = e->cfg.n_streams;
-  a.n_channels = e->cfg.n_channels;
-  a.n_ticks = n_ticks;
-  a.in16 = r.in16;
-  a.d = r.d;
-  hipStream_t st = resample_stream(e);
-  EventTimer &tm = r.tm[r.slot ^= 1];
-  int rc;
-  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
-  HIP_TRY(fvad::launch_resample(a, st));
-  return tm.end(st);
-}
-
-extern "C" int fvad_engine_input_frame(const fvad_engine *e) {
-  if (!e) return FVAD_EINVAL;
-  if (e->rs && e->rs->ps) return fail(FVAD_EINVAL, "a per-stream engine has no single frame: fvad_engine_input_layout");
-  return input_frame(e);
-}
-
-// ---------------------------------------------------------------------------
-// Per-stream rates (FVAD_INPUT_RATE_PER_STREAM)
-// ---------------------------------------------------------------------------
-extern "C" int fvad_input_layout(const int *rates, int n_streams, int n_channels, int64_t *offsets) {
-  if (!rates || !offsets || n_streams < 1 || n_channels < 1 || n_channels > FVAD_MAX_CHANNELS)
-    return fail(FVAD_EINVAL, "fvad_input_layout: rates, offsets, n_streams >= 1 and 1 <= n_channels <= 8 required");
-  for (int s = 0; s < n_streams; s++)
-    if (fvad::rs::rate_index(rates[s]) < 0)
-      return fail(FVAD_ERATE, "a stream's rate must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000");
-  int64_t o = 0;
-  for (int s = 0; s < n_streams; s++) {
-    offsets[s] = o;
-    o += (int64_t)n_channels * (rates[s] / 100);
-  }
-  offsets[n_streams] = o;
-  return FVAD_OK;
-}
-
-extern "C" int fvad_engine_stream_rates(const fvad_engine *e, int *rates) {
-  if (!e || !rates) return fail(FVAD_EINVAL, "null argument");
-  if (!e->rs || !e->rs->ps) return fail(FVAD_EINVAL, "not a per-stream engine (FVAD_INPUT_RATE_PER_STREAM)");
-  for (int s = 0; s < e->cfg.n_streams; s++) rates[s] = fvad::rs::index_rate(e->rs->ridx[s]);
-  return FVAD_OK;
-}
-
-extern "C" int fvad_engine_input_layout(const fvad_engine *e, int64_t *offsets) {
-  if (!e || !offsets) return fail(FVAD_EINVAL, "null argument");
-  if (!e->rs || !e->rs->ps) return fail(FVAD_EINVAL, "not a per-stream engine (FVAD_INPUT_RATE_PER_STREAM)");
-  for (size_t i = 0; i < e->rs->offsets.size(); i++) offsets[i] = e->rs->offsets[i];
-  return FVAD_OK;
-}
-
-// The host's rates and layout change here; the device tables follow ahead of
-// the next push (resample_tables), and the listed tails are cleared on the
-// resample stream, behind the pushes already queued.  Nothing waits.
-extern "C" int fvad_engine_set_stream_rates(fvad_engine *e, const int *streams, int n, const int *rates) {
-  if (!e) return fail(FVAD_EINVAL, "null engine");
-  if (!e->rs || !e->rs->ps) return fail(FVAD_EINVAL, "not a per-stream engine (FVAD_INPUT_RATE_PER_STREAM)");
-  if (const int rc = check_stream_list(e, streams, n)) return rc;
-  if (n == 0) return FVAD_OK;
-  if (!rates) return fail(FVAD_EINVAL, "null rates");
-  Resample &r = *e->rs;
-  for (int i = 0; i < n; i++)
-    if (fvad::rs::rate_index(rates[i]) < 0 || rates[i] > r.rate_max)
-      return fail(FVAD_ERATE, "a stream's rate must be a listed rate or 48000, at most input_rate_max");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  for (int i = 0; i < n; i++) r.ridx[streams[i]] = fvad::rs::rate_index(rates[i]);
-  resample_relayout(e);
-  fvad::ResampleClearArgs ra{};
-  ra.tails = r.tails.get();
-  ra.row_words = e->cfg.n_channels * fvad::rs::kMaxTail;
-  for (int i0 = 0; i0 < n; i0 += fvad::kListMax) {
-    ra.ids.n = std::min(fvad::kListMax, n - i0);
-    std::memcpy(ra.ids.id, streams + i0, sizeof(int) * (size_t)ra.ids.n);
-    HIP_TRY(fvad::launch_resample_clear(ra, resample_stream(e)));
-  }
-  return FVAD_OK;
-}
-
-extern "C" int fvad_engine_fetch_input(fvad_engine *e, int n_ticks, float *pcm48) {
-  if (!e || !pcm48) return fail(FVAD_EINVAL, "null argument");
-  if (!e->rs) return fail(FVAD_EINVAL, "fvad_engine_fetch_input reads a resampling engine (input_rate)");
-  if (n_ticks < 1 || n_ticks > e->cfg.max_ticks) return fail(FVAD_EINVAL, "n_ticks out of range");
-  if (const int rc = fvad_engine_sync(e)) return rc;
-  HIP_TRY(hipMemcpy(pcm48, e->d_pcm, (size_t)n_ticks * e->cfg.n_streams * e->cfg.n_channels * fvad::kFrame * sizeof(float),
-                    hipMemcpyDeviceToHost));
-  return FVAD_OK;
-}
-
-extern "C" int fvad_engine_resample_times(fvad_engine *e, double *ms_avg, int *n_runs) {
-  if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
-  if (!e->rs) return fail(FVAD_EINVAL, "fvad_engine_resample_times reads a resampling engine (input_rate)");
-  if (const int rc = fvad_engine_sync(e)) return rc;
-  Resample &r = *e->rs;
-  for (EventTimer &tm : r.tm)
-    if (const int rc = tm.collect(r.ms_sum, r.n_timed)) return rc;
-  *ms_avg = r.n_timed ? r.ms_sum / r.n_timed : 0.0;
-  if (n_runs) *n_runs = r.n_timed;
-  return FVAD_OK;
-}
-
-// ---------------------------------------------------------------------------
-// The denoised PCM at another rate (denoised_rate set; fvad_resample_out.h):
-// k_resample_out writes d_den_out from d_den on the engine stream, and every
-// copy of denoised rows to the host reads d_den_out
-// ---------------------------------------------------------------------------
-int fvad::eng::denoised_frame(const fvad_engine *e) { return e->ro ? e->ro->d.n_out : fvad::kFrame; }
-
-const float *fvad::eng::denoised_source(const fvad_engine *e) { return e->ro ? e->ro->out.get() : e->d_den.get(); }
-
-int fvad::eng::denoised_frame_max(const fvad_engine *e) {
-  return e->ro && e->ro->ps ? e->ro->rate_max / 100 : denoised_frame(e);
-}
-
-size_t fvad::eng::denoised_floats(const fvad_engine *e, int n_ticks) {
-  if (e->ro && e->ro->ps) return (size_t)n_ticks * (size_t)e->ro->pushed_len;
-  return (size_t)n_ticks * e->cfg.n_streams * e->cfg.n_channels * denoised_frame(e);
-}
-
-int fvad::eng::resample_out_tail_words(const fvad_engine *e) {
-  return e->ro->ps ? fvad::rs::kMaxTailOut : e->ro->d.K - 1;
-}
-
-void fvad::eng::resample_out_relayout(fvad_engine *e) {
-  ResampleOut &r = *e->ro;
-  const int B = e->cfg.n_streams;
-  layout_of_indices(r.ridx.data(), B, e->cfg.n_channels, r.offsets.data());
-  int n = 0;
-  for (int i = 0; i < fvad::rs::kPsRates; i++) {
-    r.list_at[i] = n;
-    for (int s = 0; s < B; s++)
-      if (r.ridx[s] == i) r.lists[n++] = s;
-  }
-  r.list_at[fvad::rs::kPsRates] = n;
-  r.gen++;
-}
-
-// fvad_engine_create's part: the table, the tails (zeroed by the reset that
-// follows) and the output rows
-int fvad::eng::resample_out_make(fvad_engine *e) {
-  ResampleOut &r = *e->ro;
-  const fvad_engine_config &c = e->cfg;
-  if (r.ps) {
-    // the tables of every listed rate up to rate_max, each stream at rate_max,
-    // the output rows sized by it
-    const size_t B = c.n_streams, rows = B * c.n_channels;
-    int rc;
-    for (int i = 0; i < fvad::rs::kPsRates; i++) {
-      const int rate = fvad::rs::index_rate(i);
-      if (i == fvad::rs::kPsIndex48) {  // (no filter: k_resample_out_copy)
-        r.dr[i].rate = rate;
-        r.dr[i].L = r.dr[i].M = r.dr[i].K = 1;
-        r.dr[i].n_out = fvad::rs::kIn;
-        continue;
-      }
-      fvad::rs::describe_out(rate, r.dr[i]);
-      if (rate > r.rate_max) continue;
-      const std::vector<float> &taps = fvad::resample_out_table(r.dr[i]);
-      if ((rc = fvad::make_dev(r.taps_r[i], taps.size()))) return rc;
-      HIP_TRY(hipMemcpy(r.taps_r[i].get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    r.ridx.assign(B, fvad::rs::rate_index(r.rate_max));
-    r.lists.resize(B);
-    r.offsets.resize(B + 1);
-    resample_out_relayout(e);
-    if ((rc = fvad::make_dev(r.tails, rows * fvad::rs::kMaxTailOut)) ||
-        (rc = fvad::make_dev(r.out, (size_t)c.max_ticks * rows * (r.rate_max / 100))) ||
-        (rc = fvad::make_dev(r.tab, r.tab_words())) ||
-        (rc = fvad::make_pinned(r.stage, (size_t)ResampleOut::kStage * r.tab_words())))
-      return rc;
-    for (EventTimer &tm : r.tm)
-      if ((rc = tm.create())) return rc;
-    for (fvad::event_ptr &ev : r.stage_ev)
-      if ((rc = fvad::make_event(ev))) return rc;
-    return FVAD_OK;
-  }
-  const std::vector<float> &taps = fvad::resample_out_table(r.d);
-  const size_t rows = (size_t)c.n_streams * c.n_channels;
-  int rc;
-  if ((rc = fvad::make_dev(r.taps, taps.size())) || (rc = fvad::make_dev(r.tails, rows * (r.d.K - 1))) ||
-      (rc = fvad::make_dev(r.out, (size_t)c.max_ticks * rows * r.d.n_out)))
-    return rc;
-  for (EventTimer &tm : r.tm)
-    if ((rc = tm.create())) return rc;
-  HIP_TRY(hipMemcpy(r.taps.get(), taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
-  return FVAD_OK;
-}
-
-namespace {
-// the device tables, when a change of rates has overtaken them: queued on the
-// engine stream, so behind the launches of every push before this one
-int resample_out_tables(fvad_engine *e, hipStream_t st) {
-  ResampleOut &r = *e->ro;
-  if (r.tab_gen == r.gen) return FVAD_OK;
-  const int B = e->cfg.n_streams, i = r.stage_next;
-  r.stage_next = (i + 1) % ResampleOut::kStage;
-  if (r.stage_used[i]) HIP_TRY(hipEventSynchronize(r.stage_ev[i].get()));  // (complete long ago: see ResampleOut)
-  long long *row = r.stage.get() + (size_t)i * r.tab_words();
-  std::memcpy(row, r.offsets.data(), sizeof(long long) * (size_t)(B + 1));
-  std::memcpy(row + B + 1, r.lists.data(), sizeof(int) * (size_t)B);
-  HIP_TRY(hipMemcpyAsync(r.tab.get(), row, r.tab_words() * sizeof(long long), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(r.stage_ev[i].get(), st));
-  r.stage_used[i] = true;
-  r.tab_gen = r.gen;
-  return FVAD_OK;
-}
-
-int resample_out_push_ps(fvad_engine *e, int n_ticks, const int *d_ticks) {
-  ResampleOut &r = *e->ro;
-  const int B = e->cfg.n_streams;
-  hipStream_t st = e->stream.get();
-  int rc;
-  if ((rc = resample_out_tables(e, st))) return rc;
-  fvad::ResampleOutPsPush p{};
-  p.den = e->d_den.get();
-  p.tails = r.tails.get();
-  p.ticks_valid = d_ticks;
-  p.out = r.out.get();
-  p.n_streams = B;
-  p.n_channels = e->cfg.n_channels;
-  p.n_ticks = n_ticks;
-  p.offsets = r.tab.get();
-  p.lists = reinterpret_cast<const int *>(r.tab.get() + B + 1);
-  p.tick_len = r.tick_len();
-  for (int i = 0; i <= fvad::rs::kPsRates; i++) p.list_at[i] = r.list_at[i];
-  for (int i = 0; i < fvad::rs::kPsRates; i++) {
-    p.taps[i] = r.taps_r[i].get();
-    p.d[i] = r.dr[i];
-  }
-  r.pushed_len = r.tick_len();
-  EventTimer &tm = r.tm[r.slot = (r.slot + 1) % 4];
-  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
-  HIP_TRY(fvad::launch_resample_out_ps(p, st));
-  return tm.end(st);
-}
-}  // namespace
-
-// the two launches of the push being launched, on the engine stream behind
-// its last writer of d_den, timed without waiting (as resample_push)
-int fvad::eng::resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
-  ResampleOut &r = *e->ro;
-  if (r.ps) return resample_out_push_ps(e, n_ticks, d_ticks);
-  fvad::ResampleOutArgs a{};
-  a.den = e->d_den.get();
-  a.taps = r.taps.get();
-  a.tails = r.tails.get();
-  a.ticks_valid = d_ticks;
-  a.out = r.out.get();
-  a.n_streams = e->cfg.n_streams;
-  a.n_channels = e->cfg.n_channels;
-  a.n_ticks = n_ticks;
-  a.d = r.d;
-  hipStream_t st = e->stream.get();
-  EventTimer &tm = r.tm[r.slot = (r.slot + 1) % 4];
-  int rc;
-  if ((rc = tm.collect(r.ms_sum, r.n_timed)) || (rc = tm.begin(st))) return rc;
-  HIP_TRY(fvad::launch_resample_out(a, st));
-  return tm.end(st);
-}
-
-extern "C" int fvad_engine_denoised_frame(const fvad_engine *e) {
-  if (!e) return FVAD_EINVAL;
-  if (e->ro && e->ro->ps)
-    return fail(FVAD_EINVAL, "an engine of per-stream denoised rates has no single frame: fvad_engine_denoised_layout");
-  return denoised_frame(e);
-}
-
-// ---------------------------------------------------------------------------
-// Per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)
-// ---------------------------------------------------------------------------
-extern "C" int fvad_denoised_layout(const int *rates, int n_streams, int n_channels, int64_t *offsets) {
-  return fvad_input_layout(rates, n_streams, n_channels, offsets);  // (the same arithmetic, the same refusals)
-}
-
-extern "C" int fvad_engine_stream_denoised_rates(const fvad_engine *e, int *rates) {
-  if (!e || !rates) return fail(FVAD_EINVAL, "null argument");
-  if (!e->ro || !e->ro->ps) return fail(FVAD_EINVAL, "not an engine of per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)");
-  for (int s = 0; s < e->cfg.n_streams; s++) rates[s] = fvad::rs::index_rate(e->ro->ridx[s]);
-  return FVAD_OK;
-}
-
-extern "C" int fvad_engine_denoised_layout(const fvad_engine *e, int64_t *offsets) {
-  if (!e || !offsets) return fail(FVAD_EINVAL, "null argument");
-  if (!e->ro || !e->ro->ps) return fail(FVAD_EINVAL, "not an engine of per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)");
-  for (size_t i = 0; i < e->ro->offsets.size(); i++) offsets[i] = e->ro->offsets[i];
-  return FVAD_OK;
-}
-
-// Only the host's rates and layout change here: the device tables follow ahead
-// of the next push (resample_out_tables), and the history, which does not
-// depend on a row's rate, is left alone.  No device call at all.
-extern "C" int fvad_engine_set_stream_denoised_rates(fvad_engine *e, const int *streams, int n, const int *rates) {
-  if (!e) return fail(FVAD_EINVAL, "null engine");
-  if (!e->ro || !e->ro->ps) return fail(FVAD_EINVAL, "not an engine of per-stream denoised rates (FVAD_DENOISED_RATE_PER_STREAM)");
-  if (const int rc = check_stream_list(e, streams, n)) return rc;
-  if (n == 0) return FVAD_OK;
-  if (!rates) return fail(FVAD_EINVAL, "null rates");
-  ResampleOut &r = *e->ro;
-  for (int i = 0; i < n; i++)
-    if (fvad::rs::rate_index(rates[i]) < 0 || rates[i] > r.rate_max)
-      return fail(FVAD_ERATE, "a stream's denoised rate must be a listed rate or 48000, at most denoised_rate_max");
-  for (int i = 0; i < n; i++) r.ridx[streams[i]] = fvad::rs::rate_index(rates[i]);
-  resample_out_relayout(e);
-  return FVAD_OK;
-}
-
-extern "C" int fvad_engine_resample_out_times(fvad_engine *e, double *ms_avg, int *n_runs) {
-  if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
-  if (!e->ro) return fail(FVAD_EINVAL, "fvad_engine_resample_out_times reads an engine with denoised_rate set");
-  if (const int rc = fvad_engine_sync(e)) return rc;
-  ResampleOut &r = *e->ro;
-  for (EventTimer &tm : r.tm)
-    if (const int rc = tm.collect(r.ms_sum, r.n_timed)) return rc;
-  *ms_avg = r.n_timed ? r.ms_sum / r.n_timed : 0.0;
-  if (n_runs) *n_runs = r.n_timed;
-  return FVAD_OK;
-}
-
 int fvad::eng::check_ticks(const fvad_engine *e, const int32_t *ticks_valid, int n_ticks) {
   if (ticks_valid)
     for (int s = 0; s < e->cfg.n_streams; s++)
@@ -526,7 +52,7 @@ int fvad::eng::tail_ticks(const fvad_engine *e, const int32_t *ticks_valid, cons
   const int B = e->cfg.n_streams;
   if (e->rs) {  // whole ticks only: the resampler's phase restarts with every tick
     for (int s = 0; s < B; s++)
-      if (last[s] != (e->rs->ps ? e->rs->frame(s) : e->rs->d.n_in))
+      if (last[s] != (e->rs->plan.on() ? e->rs->plan.frame(s) : e->rs->d.n))
         return fail(FVAD_EINVAL, "a resampling engine consumes whole ticks only");
     return FVAD_OK;
   }

@@ -42,17 +42,18 @@ uint64_t config_hash_of(const fvad_engine *e) {
   }
   // a resampling engine's rate; an engine of 48 kHz input hashes what it always did
   // (per-stream rates: the marker, not input_rate_max -- a record carries its stream's rate)
-  if (e->rs) h = fnv_add(h, e->rs->ps ? (int)FVAD_INPUT_RATE_PER_STREAM : e->rs->d.rate);
+  if (e->rs) h = fnv_add(h, e->rs->plan.on() ? (int)FVAD_INPUT_RATE_PER_STREAM : e->rs->d.rate);
   // likewise the rate of the denoised PCM, when it is not the 48 kHz signal
   // (per-stream denoised rates: the marker, not denoised_rate_max)
-  if (e->ro) h = fnv_add(h, e->ro->ps ? (int)FVAD_DENOISED_RATE_PER_STREAM : e->ro->d.rate);
+  if (e->ro) h = fnv_add(h, e->ro->plan.on() ? (int)FVAD_DENOISED_RATE_PER_STREAM : e->ro->d.rate);
   return h;
 }
 
 fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
   return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap,
-                           e->rs ? resample_tail_words(e) : 0, e->ro ? resample_out_tail_words(e) : 0, e->rs && e->rs->ps,
-                           e->ro && e->ro->ps);
+                           e->rs ? resample_tail_words(e, fvad::rs::Dir::kIn) : 0,
+                           e->ro ? resample_tail_words(e, fvad::rs::Dir::kOut) : 0, e->rs && e->rs->plan.on(),
+                           e->ro && e->ro->plan.on());
 }
 
 fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
@@ -74,8 +75,8 @@ fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   h.config_hash = config_hash_of(e);
   h.model_hash = e->model_hash;
   h.sample_rate = (uint32_t)e->cfg.sample_rate;
-  h.reserved[0] = !e->rs ? 0u : e->rs->ps ? 0xFFFFFFFFu : (uint32_t)e->rs->d.rate;
-  h.reserved[1] = !e->ro ? 0u : e->ro->ps ? 0xFFFFFFFFu : (uint32_t)e->ro->d.rate;
+  h.reserved[0] = !e->rs ? 0u : e->rs->plan.on() ? 0xFFFFFFFFu : (uint32_t)e->rs->d.rate;
+  h.reserved[1] = !e->ro ? 0u : e->ro->plan.on() ? 0xFFFFFFFFu : (uint32_t)e->ro->d.rate;
   return h;
 }
 
@@ -136,6 +137,28 @@ int check_record(const fvad_engine *e, const fvad::BlobLayout &lay, const float 
     if (S.lt_widx >= nl || S.st_widx >= ns || S.r_widx >= nr || S.lt_count > nl || S.st_count > ns || S.r_count > nr ||
         S.lt_nw > nl || S.lt_neg < 0 || S.lt_neg > K.n_lt || S.state < 0 || S.state > 3)
       return fail(FVAD_EFORMAT, "stream record: machine state out of range");
+  }
+  return FVAD_OK;
+}
+
+// Per-stream rates: a record carries its stream's rate in word o_word (three
+// zero words behind it).  Nothing to do for a plan that is not on.
+void save_rates(const RatePlan &p, const int32_t *streams, int n, char *body, size_t stream_bytes, long long o_word) {
+  for (int i = 0; p.on() && i < n; i++) {
+    const uint32_t w[4] = {p.save_rate(streams[i]), 0u, 0u, 0u};
+    std::memcpy(body + (size_t)i * stream_bytes + 4 * (size_t)o_word, w, sizeof(w));
+  }
+}
+
+// the rates of the records about to be restored, each checked
+int restored_rates(const RatePlan &p, const int32_t *index, int n, const char *body, size_t stream_bytes,
+                   long long o_word, std::vector<int> &rates, const char *off_list, const char *above_max) {
+  for (int i = 0; p.on() && i < n; i++) {
+    uint32_t rate;
+    std::memcpy(&rate, body + (size_t)(index ? index[i] : i) * stream_bytes + 4 * (size_t)o_word, sizeof(rate));
+    int r;
+    if (const int bad = p.check_restored_rate(rate, &r)) return fail(FVAD_EFORMAT, bad == 1 ? off_list : above_max);
+    rates.push_back((int)rate);
   }
   return FVAD_OK;
 }
@@ -215,20 +238,7 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
       va.ids = ca.ids;
       HIP_TRY(fvad::launch_stream_vclear(va, e->side));
     }
-    if (e->rs) {  // the resampler's tails, on the stream k_resample runs on
-      fvad::ResampleClearArgs ra{};
-      ra.tails = e->rs->tails.get();
-      ra.row_words = e->cfg.n_channels * resample_tail_words(e);
-      ra.ids = ca.ids;
-      HIP_TRY(fvad::launch_resample_clear(ra, resample_stream(e)));
-    }
-    if (e->ro) {  // the output resampler's tails, on the engine stream, where k_resample_out runs
-      fvad::ResampleClearArgs ra{};
-      ra.tails = e->ro->tails.get();
-      ra.row_words = e->cfg.n_channels * resample_out_tail_words(e);
-      ra.ids = ca.ids;
-      HIP_TRY(fvad::launch_resample_clear(ra, e->stream.get()));
-    }
+    if ((rc = resample_reset_streams(e, ca.ids))) return rc;  // the resamplers' tails
   }
   // clip capture: the streams' positions restart behind the appends already
   // queued, their pending clips go behind the passes already queued
@@ -287,19 +297,12 @@ extern "C" int fvad_engine_save_streams(fvad_engine *e, const int32_t *streams, 
   }
   HIP_TRY(hipMemcpyAsync(static_cast<char *>(blob) + sizeof(h), e->d_blob.get(), body, hipMemcpyDeviceToHost, e->stream.get()));
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
-  if (e->rs && e->rs->ps) {  // each record's rate (the gather leaves these words alone)
-    const long long o_rate = layout_of(e, (int)h.seg_capacity).o_rate;
-    for (int i = 0; i < n; i++) {
-      const uint32_t w[4] = {(uint32_t)fvad::rs::index_rate(e->rs->ridx[streams[i]]), 0u, 0u, 0u};
-      std::memcpy(static_cast<char *>(blob) + sizeof(h) + (size_t)i * (size_t)h.stream_bytes + 4 * (size_t)o_rate, w, sizeof(w));
-    }
-  }
-  if (e->ro && e->ro->ps) {  // likewise each record's denoised rate
-    const long long o_orate = layout_of(e, (int)h.seg_capacity).o_orate;
-    for (int i = 0; i < n; i++) {
-      const uint32_t w[4] = {(uint32_t)fvad::rs::index_rate(e->ro->ridx[streams[i]]), 0u, 0u, 0u};
-      std::memcpy(static_cast<char *>(blob) + sizeof(h) + (size_t)i * (size_t)h.stream_bytes + 4 * (size_t)o_orate, w, sizeof(w));
-    }
+  // per-stream rates: each record's rate and denoised rate (the gather leaves these words alone)
+  if ((e->rs && e->rs->plan.on()) || (e->ro && e->ro->plan.on())) {
+    const fvad::BlobLayout lay = layout_of(e, (int)h.seg_capacity);
+    char *recs = static_cast<char *>(blob) + sizeof(h);
+    if (e->rs) save_rates(e->rs->plan, streams, n, recs, (size_t)h.stream_bytes, lay.o_rate);
+    if (e->ro) save_rates(e->ro->plan, streams, n, recs, (size_t)h.stream_bytes, lay.o_orate);
   }
   std::memcpy(blob, &h, sizeof(h));
   return FVAD_OK;
@@ -339,27 +342,16 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
     std::memcpy(head.data(), body + r * (size_t)h.stream_bytes, (size_t)h.stream_bytes);
     if ((rc = check_record(e, lay, head.data()))) return rc;
   }
-  std::vector<int> rec_ridx;  // per-stream rates: the records' rates, checked before a device byte is written
-  if (e->rs && e->rs->ps)
-    for (int i = 0; i < n; i++) {
-      uint32_t rate;
-      std::memcpy(&rate, body + (size_t)(index ? index[i] : i) * (size_t)h.stream_bytes + 4 * (size_t)lay.o_rate, sizeof(rate));
-      const int ri = rate <= 96000u ? fvad::rs::rate_index((int)rate) : -1;
-      if (ri < 0) return fail(FVAD_EFORMAT, "stream record: not a listed rate");
-      if ((int)rate > e->rs->rate_max) return fail(FVAD_EFORMAT, "stream record: its rate exceeds this engine's input_rate_max");
-      rec_ridx.push_back(ri);
-    }
-  std::vector<int> rec_oridx;  // per-stream denoised rates: likewise
-  if (e->ro && e->ro->ps)
-    for (int i = 0; i < n; i++) {
-      uint32_t rate;
-      std::memcpy(&rate, body + (size_t)(index ? index[i] : i) * (size_t)h.stream_bytes + 4 * (size_t)lay.o_orate, sizeof(rate));
-      const int ri = rate <= 96000u ? fvad::rs::rate_index((int)rate) : -1;
-      if (ri < 0) return fail(FVAD_EFORMAT, "stream record: not a listed denoised rate");
-      if ((int)rate > e->ro->rate_max)
-        return fail(FVAD_EFORMAT, "stream record: its denoised rate exceeds this engine's denoised_rate_max");
-      rec_oridx.push_back(ri);
-    }
+  // per-stream rates: the records' rates, checked before a device byte is written
+  std::vector<int> rec_rates, rec_orates;
+  if (e->rs && (rc = restored_rates(e->rs->plan, index, n, body, (size_t)h.stream_bytes, lay.o_rate, rec_rates,
+                                    "stream record: not a listed rate",
+                                    "stream record: its rate exceeds this engine's input_rate_max")))
+    return rc;
+  if (e->ro && (rc = restored_rates(e->ro->plan, index, n, body, (size_t)h.stream_bytes, lay.o_orate, rec_orates,
+                                    "stream record: not a listed denoised rate",
+                                    "stream record: its denoised rate exceeds this engine's denoised_rate_max")))
+    return rc;
   if ((rc = fvad_engine_sync(e))) return rc;
   HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t bytes = (size_t)h.count * (size_t)h.stream_bytes;
@@ -375,14 +367,9 @@ extern "C" int fvad_engine_restore_streams(fvad_engine *e, const int32_t *stream
     HIP_TRY(fvad::launch_stream_scatter(a, e->stream.get()));
   }
   HIP_TRY(hipStreamSynchronize(e->stream.get()));
-  if (!rec_ridx.empty()) {  // the slots take their records' rates: the layout of the next push follows
-    for (int i = 0; i < n; i++) e->rs->ridx[streams[i]] = rec_ridx[i];
-    resample_relayout(e);
-  }
-  if (!rec_oridx.empty()) {  // and their records' denoised rates: the layout of the next push's denoised PCM follows
-    for (int i = 0; i < n; i++) e->ro->ridx[streams[i]] = rec_oridx[i];
-    resample_out_relayout(e);
-  }
+  // the slots take their records' rates and denoised rates: the layouts of the next push follow
+  if (!rec_rates.empty()) e->rs->plan.apply(streams, n, rec_rates.data());
+  if (!rec_orates.empty()) e->ro->plan.apply(streams, n, rec_orates.data());
   if (e->cap) {
     // the slots continue at their records' sample counts with nothing held
     // (a blob carries no audio and no pending clip)

@@ -1,8 +1,7 @@
-// Input resampling to 48 kHz, host side: the tap design (f64, once per rate)
-// and fvad_resample_host, the mirror of k_resample the tests hold the kernel
-// to (fvad_resample_core.h is the arithmetic they share); and the same for the
-// decimating direction (denoised_rate): fvad_resample_out_host mirrors
-// k_resample_out.  No GPU.
+// Resampling to and from 48 kHz, host side: the tap design (f64, once per rate
+// and direction) and fvad_resample_host / fvad_resample_out_host, the mirrors
+// of k_resample / k_resample_out the tests hold the kernels to
+// (fvad_resample_core.h is the arithmetic they share).  No GPU.
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -11,8 +10,6 @@
 #include "../../include/fvad.h"
 #include "fvad_hip_own.h"  // fvad::set_error
 #include "fvad_resample.h"
-#include "fvad_resample_out.h"
-#include "fvad_resample_core.h"
 
 namespace {
 
@@ -63,129 +60,102 @@ int rate_slot(int rate) {
 
 }  // namespace
 
-// the [L][K] table of a listed rate, designed on first use and kept
-const std::vector<float> &fvad::resample_table(const rs::Desc &d) {
-  static std::vector<float> tables[rs::kRates];
-  static std::once_flag once[rs::kRates];
-  const int i = rate_slot(d.rate);
-  std::call_once(once[i], [&] { design(d.L, d.K, d.rate, d.rate, tables[i]); });
-  return tables[i];
+// the [L][K] table of a listed rate, designed on first use and kept; the
+// filter reads samples at the rate itself (kIn) or at 48000 (kOut)
+const std::vector<float> &fvad::resample_table(rs::Dir dir, const rs::Desc &d) {
+  static std::vector<float> tables[2][rs::kRates];
+  static std::once_flag once[2][rs::kRates];
+  const int o = dir == rs::Dir::kOut, i = rate_slot(d.rate);
+  std::call_once(once[o][i], [&] { design(d.L, d.K, o ? 48000 : d.rate, d.rate, tables[o][i]); });
+  return tables[o][i];
 }
 
-// the decimating direction's [L][K] table (48 kHz to d.rate), likewise
-const std::vector<float> &fvad::resample_out_table(const rs::DescOut &d) {
-  static std::vector<float> tables[rs::kRates];
-  static std::once_flag once[rs::kRates];
-  const int i = rate_slot(d.rate);
-  std::call_once(once[i], [&] { design(d.L, d.K, 48000, d.rate, tables[i]); });
-  return tables[i];
-}
+namespace {
+using fvad::rs::Dir;
+const char *const kInRates = "input_rate must be 8000, 16000, 24000, 32000, 44100 or 96000";
+const char *const kOutRates = "denoised_rate must be 8000, 16000, 24000, 32000, 44100 or 96000";
 
-extern "C" int fvad_resample_info(int input_rate, fvad_resample_desc *out) {
-  if (!out) return fvad::set_error(FVAD_EINVAL, "null argument");
+// fvad_resample_taps / fvad_resample_out_taps
+size_t taps_of(int rate, Dir dir, const char *rates, float *out, size_t cap) {
   fvad::rs::Desc d;
-  if (!fvad::rs::describe(input_rate, d))
-    return fvad::set_error(FVAD_ERATE, "input_rate must be 8000, 16000, 24000, 32000, 44100 or 96000");
-  out->input_rate = d.rate;
-  out->L = d.L;
-  out->M = d.M;
-  out->taps_per_phase = d.K;
-  out->frame_in = d.n_in;
-  out->delay = ((double)d.L * d.K - 1.0) / (2.0 * d.M);
-  return FVAD_OK;
-}
-
-extern "C" size_t fvad_resample_taps(int input_rate, float *out, size_t cap) {
-  fvad::rs::Desc d;
-  if (!fvad::rs::describe(input_rate, d)) {
-    fvad::set_error(FVAD_ERATE, "input_rate must be 8000, 16000, 24000, 32000, 44100 or 96000");
+  if (!fvad::rs::describe(rate, dir, d)) {
+    fvad::set_error(FVAD_ERATE, rates);
     return 0;
   }
-  const std::vector<float> &t = fvad::resample_table(d);
+  const std::vector<float> &t = fvad::resample_table(dir, d);
   if (out) std::memcpy(out, t.data(), sizeof(float) * (t.size() < cap ? t.size() : cap));
   return t.size();
 }
 
-extern "C" int fvad_resample_host(int input_rate, const float *in, size_t n_ticks, float *tail, float *out) {
+// fvad_resample_host / fvad_resample_out_host, the mirrors of k_resample and
+// k_resample_out: one row tick by tick, n_src samples in and n_dst out a tick
+// (d.n and 480, or 480 and d.n)
+int mirror(int rate, Dir dir, const char *rates, const float *in, size_t n_ticks, float *tail, float *out) {
   fvad::rs::Desc d;
-  if (!fvad::rs::describe(input_rate, d))
-    return fvad::set_error(FVAD_ERATE, "input_rate must be 8000, 16000, 24000, 32000, 44100 or 96000");
+  if (!fvad::rs::describe(rate, dir, d)) return fvad::set_error(FVAD_ERATE, rates);
   if (n_ticks == 0) return FVAD_OK;
   if (!in || !out) return fvad::set_error(FVAD_EINVAL, "null argument");
-  const float *taps = fvad::resample_table(d).data();
-  const int hist = d.K - 1;
+  const float *taps = fvad::resample_table(dir, d).data();
+  const int hist = d.K - 1, n_src = dir == Dir::kIn ? d.n : fvad::rs::kIn, n_dst = dir == Dir::kIn ? fvad::rs::kOut : d.n;
   // [the K - 1 samples before the tick | the tick]
-  std::vector<float> x((size_t)hist + d.n_in, 0.0f);
+  std::vector<float> x((size_t)hist + n_src, 0.0f);
   if (tail) std::memcpy(x.data(), tail, sizeof(float) * hist);
   for (size_t t = 0; t < n_ticks; t++) {
-    std::memcpy(x.data() + hist, in + t * d.n_in, sizeof(float) * d.n_in);
-    for (int r = 0; r < fvad::rs::kOut; r++) {
+    std::memcpy(x.data() + hist, in + t * n_src, sizeof(float) * n_src);
+    for (int r = 0; r < n_dst; r++) {
       int i, p;
       fvad::rs::position(r, d.L, d.M, i, p);
       float acc[1];
       fvad::rs::accumulate<1>(
           d.K, [&](int k) { return taps[(size_t)p * d.K + k]; }, [&](int, int k) { return x[(size_t)hist + i - k]; }, acc);
-      out[t * fvad::rs::kOut + r] = acc[0];
+      out[t * n_dst + r] = acc[0];
     }
-    std::memmove(x.data(), x.data() + d.n_in, sizeof(float) * hist);
+    std::memmove(x.data(), x.data() + n_src, sizeof(float) * hist);
   }
   if (tail) std::memcpy(tail, x.data(), sizeof(float) * hist);
   return FVAD_OK;
 }
+}  // namespace
 
-// ---------------------------------------------------------------------------
-// The decimating direction: 48 kHz to denoised_rate (include/fvad.h section 2d)
-// ---------------------------------------------------------------------------
-namespace {
-const char *const kOutRates = "denoised_rate must be 8000, 16000, 24000, 32000, 44100 or 96000";
+extern "C" int fvad_resample_info(int input_rate, fvad_resample_desc *out) {
+  if (!out) return fvad::set_error(FVAD_EINVAL, "null argument");
+  fvad::rs::Desc d;
+  if (!fvad::rs::describe(input_rate, Dir::kIn, d)) return fvad::set_error(FVAD_ERATE, kInRates);
+  out->input_rate = d.rate;
+  out->L = d.L;
+  out->M = d.M;
+  out->taps_per_phase = d.K;
+  out->frame_in = d.n;
+  out->delay = ((double)d.L * d.K - 1.0) / (2.0 * d.M);
+  return FVAD_OK;
 }
 
+extern "C" size_t fvad_resample_taps(int input_rate, float *out, size_t cap) {
+  return taps_of(input_rate, Dir::kIn, kInRates, out, cap);
+}
+
+extern "C" int fvad_resample_host(int input_rate, const float *in, size_t n_ticks, float *tail, float *out) {
+  return mirror(input_rate, Dir::kIn, kInRates, in, n_ticks, tail, out);
+}
+
+// The decimating direction: 48 kHz to denoised_rate (include/fvad.h section 2d)
 extern "C" int fvad_resample_out_info(int rate, fvad_resample_out_desc *out) {
   if (!out) return fvad::set_error(FVAD_EINVAL, "null argument");
-  fvad::rs::DescOut d;
-  if (!fvad::rs::describe_out(rate, d)) return fvad::set_error(FVAD_ERATE, kOutRates);
+  fvad::rs::Desc d;
+  if (!fvad::rs::describe(rate, Dir::kOut, d)) return fvad::set_error(FVAD_ERATE, kOutRates);
   out->rate = d.rate;
   out->L = d.L;
   out->M = d.M;
   out->taps_per_phase = d.K;
-  out->frame_out = d.n_out;
+  out->frame_out = d.n;
   out->delay = ((double)d.L * d.K - 1.0) / (2.0 * d.L);
   return FVAD_OK;
 }
 
 extern "C" size_t fvad_resample_out_taps(int rate, float *out, size_t cap) {
-  fvad::rs::DescOut d;
-  if (!fvad::rs::describe_out(rate, d)) {
-    fvad::set_error(FVAD_ERATE, kOutRates);
-    return 0;
-  }
-  const std::vector<float> &t = fvad::resample_out_table(d);
-  if (out) std::memcpy(out, t.data(), sizeof(float) * (t.size() < cap ? t.size() : cap));
-  return t.size();
+  return taps_of(rate, Dir::kOut, kOutRates, out, cap);
 }
 
 extern "C" int fvad_resample_out_host(int rate, const float *in48, size_t n_ticks, float *tail, float *out) {
-  fvad::rs::DescOut d;
-  if (!fvad::rs::describe_out(rate, d)) return fvad::set_error(FVAD_ERATE, kOutRates);
-  if (n_ticks == 0) return FVAD_OK;
-  if (!in48 || !out) return fvad::set_error(FVAD_EINVAL, "null argument");
-  const float *taps = fvad::resample_out_table(d).data();
-  const int hist = d.K - 1;
-  // [the K - 1 samples before the tick | the tick]
-  std::vector<float> y((size_t)hist + fvad::rs::kIn, 0.0f);
-  if (tail) std::memcpy(y.data(), tail, sizeof(float) * hist);
-  for (size_t t = 0; t < n_ticks; t++) {
-    std::memcpy(y.data() + hist, in48 + t * fvad::rs::kIn, sizeof(float) * fvad::rs::kIn);
-    for (int r = 0; r < d.n_out; r++) {
-      int i, p;
-      fvad::rs::position(r, d.L, d.M, i, p);
-      float acc[1];
-      fvad::rs::accumulate<1>(
-          d.K, [&](int k) { return taps[(size_t)p * d.K + k]; }, [&](int, int k) { return y[(size_t)hist + i - k]; }, acc);
-      out[t * d.n_out + r] = acc[0];
-    }
-    std::memmove(y.data(), y.data() + fvad::rs::kIn, sizeof(float) * hist);
-  }
-  if (tail) std::memcpy(tail, y.data(), sizeof(float) * hist);
-  return FVAD_OK;
+  return mirror(rate, Dir::kOut, kOutRates, in48, n_ticks, tail, out);
 }

@@ -4,7 +4,7 @@
 // host mirror fvad_resample_host, so the two agree by the bits).
 //
 // One workgroup works on one (tick, row) at a time, row = (stream, channel):
-// it stages the tick's n_in inputs behind the K - 1 before them in LDS -- the
+// it stages the tick's n inputs behind the K - 1 before them in LDS -- the
 // previous tick's end in the push, or the row's tail for tick 0 -- and every
 // thread computes the outputs r, r + S, r + 2 S, ... of the tick.  S (the
 // block size) is chosen so that S M is a multiple of L: a thread's outputs
@@ -104,7 +104,7 @@ __device__ __forceinline__ void resample_units(const ResampleArgs &a, const Map 
   __shared__ float s_tap[TAPCAP];  // [k][p]
   __shared__ float s_x[XCAP];      // [the K - 1 inputs before the tick | the tick]
   const int tid = threadIdx.x;
-  const int L = a.d.L, M = a.d.M, K = a.d.K, n_in = a.d.n_in, hist = K - 1;
+  const int L = a.d.L, M = a.d.M, K = a.d.K, n_in = a.d.n, hist = K - 1;
   for (int j = tid; j < L * K; j += S) {
     const int p = j / K, k = j - p * K;
     s_tap[k * L + p] = a.taps[j];
@@ -144,7 +144,7 @@ __device__ __forceinline__ void resample_units(const ResampleArgs &a, const Map 
 
 template <typename In, int S, int TAPCAP, int XCAP>
 __global__ void __launch_bounds__(S) k_resample(ResampleArgs a) {
-  const RowsAll m{(size_t)a.n_streams * a.n_channels, a.n_channels, a.n_ticks, a.d.n_in, a.d.K - 1};
+  const RowsAll m{(size_t)a.n_streams * a.n_channels, a.n_channels, a.n_ticks, a.d.n, a.d.K - 1};
   resample_units<In, S, TAPCAP, XCAP>(a, m);
 }
 
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(S) k_resample(ResampleArgs a) {
 // row and the K - 1 <= n_in words before it lie inside the push.
 template <typename In, int S, int TAPCAP, int XCAP>
 __global__ void __launch_bounds__(S) k_resample_ps(ResamplePsArgs a) {
-  const RowsListed m{a.list, a.offsets, (size_t)a.tick_len, a.n_list, a.r.n_streams, a.r.n_channels, a.r.d.n_in};
+  const RowsListed m{a.list, a.offsets, (size_t)a.tick_len, a.n_list, a.r.n_streams, a.r.n_channels, a.r.d.n};
   resample_units<In, S, TAPCAP, XCAP>(a.r, m);
 }
 
@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(256) k_resample_tail(ResampleArgs a) {
   const int tv = a.ticks_valid ? a.ticks_valid[s] : a.n_ticks;
   if (tv < 1) return;
   const In *raw = static_cast<const In *>(a.raw);
-  a.tails[idx] = load_in(raw + ((size_t)(tv - 1) * rows + row) * (size_t)a.d.n_in + (a.d.n_in - hist) + j);
+  a.tails[idx] = load_in(raw + ((size_t)(tv - 1) * rows + row) * (size_t)a.d.n + (a.d.n - hist) + j);
 }
 
 // k_resample_tail over a per-stream engine's rows [stream][channel][kMaxTail]:
@@ -218,13 +218,13 @@ namespace {
 
 template <typename In, int S, int TAPCAP, int XCAP>
 hipError_t run(const ResampleArgs &a, dim3 grid, hipStream_t stream) {
-  if (a.d.L * a.d.K > TAPCAP || a.d.n_in + a.d.K - 1 > XCAP || (S * a.d.M) % a.d.L) return hipErrorInvalidValue;
+  if (a.d.L * a.d.K > TAPCAP || a.d.n + a.d.K - 1 > XCAP || (S * a.d.M) % a.d.L) return hipErrorInvalidValue;
   hipLaunchKernelGGL((k_resample<In, S, TAPCAP, XCAP>), grid, dim3(S), 0, stream, a);
   return hipGetLastError();
 }
 template <typename In, int S, int TAPCAP, int XCAP>
 hipError_t run(const ResamplePsArgs &a, dim3 grid, hipStream_t stream) {
-  if (a.r.d.L * a.r.d.K > TAPCAP || a.r.d.n_in + a.r.d.K - 1 > XCAP || (S * a.r.d.M) % a.r.d.L)
+  if (a.r.d.L * a.r.d.K > TAPCAP || a.r.d.n + a.r.d.K - 1 > XCAP || (S * a.r.d.M) % a.r.d.L)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL((k_resample_ps<In, S, TAPCAP, XCAP>), grid, dim3(S), 0, stream, a);
   return hipGetLastError();
@@ -256,54 +256,35 @@ hipError_t launch_typed(const ResampleArgs &a, hipStream_t stream) {
 template <typename In>
 hipError_t launch_typed_ps(const ResamplePsPush &p, hipStream_t stream) {
   ResamplePsArgs a{};
-  a.r.raw = p.raw;
-  a.r.tails = p.tails;
-  a.r.ticks_valid = p.ticks_valid;
-  a.r.out = p.out;
-  a.r.n_streams = p.n_streams;
-  a.r.n_channels = p.n_channels;
-  a.r.n_ticks = p.n_ticks;
-  a.r.in16 = p.in16;
-  a.offsets = p.offsets;
-  a.tick_len = p.tick_len;
+  a.r = p.r;
   bool tails = false;
-  for (int i = 0; i < rs::kPsRates; i++) {
-    a.n_list = p.list_at[i + 1] - p.list_at[i];
-    if (a.n_list < 1) continue;
-    a.list = p.lists + p.list_at[i];
-    a.r.taps = p.taps[i];
-    a.r.d = p.d[i];
-    // about 2048 workgroups, as launch_resample: (ticks x channels) of them side by side over the list
-    const unsigned across = (unsigned)p.n_ticks * p.n_channels;
-    const dim3 grid(std::max(1u, std::min((unsigned)a.n_list, 2048u / across)), p.n_ticks, p.n_channels);
-    hipError_t rc;
-    if (i == rs::kPsIndex48) {
-      hipLaunchKernelGGL(k_resample_copy<In>, grid, dim3(256), 0, stream, a);
-      rc = hipGetLastError();
-    } else {
-      if (!a.r.taps) return hipErrorInvalidValue;
+  const hipError_t rc = ps_launches(p.ps, a, [&](const ResamplePsArgs &l, bool copy) {
+    // about 2048 workgroups, as launch_resample
+    const dim3 grid = ps_grid((unsigned)l.n_list, p.r.n_ticks, p.r.n_channels);
+    if (!copy) {
       tails = true;
-      rc = run_rate<In>(a.r.d, a, grid, stream);
+      return run_rate<In>(l.r.d, l, grid, stream);
     }
-    if (rc != hipSuccess) return rc;
-  }
-  if (!tails) return hipSuccess;
+    hipLaunchKernelGGL(k_resample_copy<In>, grid, dim3(256), 0, stream, l);
+    return hipGetLastError();
+  });
+  if (rc != hipSuccess || !tails) return rc;
   ResampleTailPsArgs t{};
-  t.raw = p.raw;
-  t.tails = p.tails;
-  t.ticks_valid = p.ticks_valid;
-  t.rate_idx = p.rate_idx;
-  t.offsets = p.offsets;
-  t.tick_len = p.tick_len;
-  t.n_streams = p.n_streams;
-  t.n_channels = p.n_channels;
-  t.n_ticks = p.n_ticks;
-  t.in16 = p.in16;
+  t.raw = p.r.raw;
+  t.tails = p.r.tails;
+  t.ticks_valid = p.r.ticks_valid;
+  t.rate_idx = p.ps.rate_idx;
+  t.offsets = p.ps.offsets;
+  t.tick_len = p.ps.tick_len;
+  t.n_streams = p.r.n_streams;
+  t.n_channels = p.r.n_channels;
+  t.n_ticks = p.r.n_ticks;
+  t.in16 = p.r.in16;
   for (int i = 0; i < rs::kPsRates; i++) {
-    t.hist[i] = p.d[i].K - 1;
-    t.n_in[i] = p.d[i].n_in;
+    t.hist[i] = p.ps.d[i].K - 1;
+    t.n_in[i] = p.ps.d[i].n;
   }
-  const size_t words = (size_t)p.n_streams * p.n_channels * rs::kMaxTail;
+  const size_t words = (size_t)p.r.n_streams * p.r.n_channels * rs::kMaxTail;
   hipLaunchKernelGGL(k_resample_tail_ps<In>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, t);
   return hipGetLastError();
 }
@@ -317,10 +298,10 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream) {
 }
 
 hipError_t launch_resample_ps(const ResamplePsPush &p, hipStream_t stream) {
-  if (p.n_ticks < 1 || p.n_streams < 1 || p.n_channels < 1) return hipSuccess;
-  if (p.n_ticks > 65535 || p.n_channels > 65535) return hipErrorInvalidValue;  // (grid y and z)
+  if (p.r.n_ticks < 1 || p.r.n_streams < 1 || p.r.n_channels < 1) return hipSuccess;
+  if (p.r.n_ticks > 65535 || p.r.n_channels > 65535) return hipErrorInvalidValue;  // (grid y and z)
   (void)hipGetLastError();
-  return p.in16 ? launch_typed_ps<short>(p, stream) : launch_typed_ps<float>(p, stream);
+  return p.r.in16 ? launch_typed_ps<short>(p, stream) : launch_typed_ps<float>(p, stream);
 }
 
 hipError_t launch_resample_clear(const ResampleClearArgs &a, hipStream_t stream) {

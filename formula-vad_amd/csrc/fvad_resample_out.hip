@@ -167,7 +167,7 @@ __device__ __forceinline__ void resample_out_units(const ResampleOutArgs &a, con
 
 template <int S, int NOUT, int U, int TAPCAP, int XCAP>
 __global__ void __launch_bounds__(S *U) k_resample_out(ResampleOutArgs a) {
-  const OutRowsAll m{(size_t)a.n_streams * a.n_channels, a.n_channels, a.n_ticks, a.d.n_out, a.d.K - 1};
+  const OutRowsAll m{(size_t)a.n_streams * a.n_channels, a.n_channels, a.n_ticks, a.d.n, a.d.K - 1};
   resample_out_units<S, NOUT, U, TAPCAP, XCAP>(a, m);
 }
 
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(S *U) k_resample_out(ResampleOutArgs a) {
 template <int S, int NOUT, int U, int TAPCAP, int XCAP>
 __global__ void __launch_bounds__(S *U) k_resample_out_ps(ResampleOutPsArgs a) {
   const OutRowsListed m{a.list,      a.offsets,      (size_t)a.tick_len, a.n_list,
-                        a.r.n_streams, a.r.n_channels, a.r.d.n_out,        a.r.d.K - 1};
+                        a.r.n_streams, a.r.n_channels, a.r.d.n,        a.r.d.K - 1};
   resample_out_units<S, NOUT, U, TAPCAP, XCAP>(a.r, m);
 }
 
@@ -235,7 +235,7 @@ namespace {
 
 template <int S, int NOUT, int U, int TAPCAP, int XCAP>
 hipError_t run(const ResampleOutArgs &a, hipStream_t stream) {
-  if (a.d.L * a.d.K > TAPCAP || rs::kIn + a.d.K - 1 > XCAP || S * NOUT != a.d.n_out || (S * a.d.M) % a.d.L)
+  if (a.d.L * a.d.K > TAPCAP || rs::kIn + a.d.K - 1 > XCAP || S * NOUT != a.d.n || (S * a.d.M) % a.d.L)
     return hipErrorInvalidValue;
   const size_t units = (size_t)a.n_streams * a.n_channels * (size_t)a.n_ticks, groups = (units + U - 1) / U;
   const unsigned grid = (unsigned)std::min<size_t>(groups, 2048);
@@ -247,10 +247,9 @@ hipError_t run(const ResampleOutArgs &a, hipStream_t stream) {
 // the list's groups of U, about 2048 in all, as above
 template <int S, int NOUT, int U, int TAPCAP, int XCAP>
 hipError_t run(const ResampleOutPsArgs &a, hipStream_t stream) {
-  if (a.r.d.L * a.r.d.K > TAPCAP || rs::kIn + a.r.d.K - 1 > XCAP || S * NOUT != a.r.d.n_out || (S * a.r.d.M) % a.r.d.L)
+  if (a.r.d.L * a.r.d.K > TAPCAP || rs::kIn + a.r.d.K - 1 > XCAP || S * NOUT != a.r.d.n || (S * a.r.d.M) % a.r.d.L)
     return hipErrorInvalidValue;
-  const unsigned groups = ((unsigned)a.n_list + U - 1) / U, across = (unsigned)a.r.n_ticks * a.r.n_channels;
-  const dim3 grid(std::max(1u, std::min(groups, 2048u / across)), a.r.n_ticks, a.r.n_channels);
+  const dim3 grid = ps_grid(((unsigned)a.n_list + U - 1) / U, a.r.n_ticks, a.r.n_channels);
   hipLaunchKernelGGL((k_resample_out_ps<S, NOUT, U, TAPCAP, XCAP>), grid, dim3(S * U), 0, stream, a);
   return hipGetLastError();
 }
@@ -286,41 +285,21 @@ hipError_t launch_resample_out(const ResampleOutArgs &a, hipStream_t stream) {
 }
 
 hipError_t launch_resample_out_ps(const ResampleOutPsPush &p, hipStream_t stream) {
-  if (p.n_ticks < 1 || p.n_streams < 1 || p.n_channels < 1) return hipSuccess;
-  if (p.n_ticks > 65535 || p.n_channels > 65535) return hipErrorInvalidValue;  // (grid y and z)
+  if (p.r.n_ticks < 1 || p.r.n_streams < 1 || p.r.n_channels < 1) return hipSuccess;
+  if (p.r.n_ticks > 65535 || p.r.n_channels > 65535) return hipErrorInvalidValue;  // (grid y and z)
   (void)hipGetLastError();
   ResampleOutPsArgs a{};
-  a.r.den = p.den;
-  a.r.tails = p.tails;
-  a.r.ticks_valid = p.ticks_valid;
-  a.r.out = p.out;
-  a.r.n_streams = p.n_streams;
-  a.r.n_channels = p.n_channels;
-  a.r.n_ticks = p.n_ticks;
-  a.offsets = p.offsets;
-  a.tick_len = p.tick_len;
-  for (int i = 0; i < rs::kPsRates; i++) {
-    a.n_list = p.list_at[i + 1] - p.list_at[i];
-    if (a.n_list < 1) continue;
-    a.list = p.lists + p.list_at[i];
-    a.r.taps = p.taps[i];
-    a.r.d = p.d[i];
-    hipError_t rc;
-    if (i == rs::kPsIndex48) {
-      const unsigned across = (unsigned)p.n_ticks * p.n_channels;
-      const dim3 grid(std::max(1u, std::min((unsigned)a.n_list, 2048u / across)), p.n_ticks, p.n_channels);
-      hipLaunchKernelGGL(k_resample_out_copy, grid, dim3(256), 0, stream, a);
-      rc = hipGetLastError();
-    } else {
-      if (!a.r.taps) return hipErrorInvalidValue;
-      rc = run_rate(a.r.d.rate, a, stream);
-    }
-    if (rc != hipSuccess) return rc;
-  }
+  a.r = p.r;
+  const hipError_t rc = ps_launches(p.ps, a, [&](const ResampleOutPsArgs &l, bool copy) {
+    if (!copy) return run_rate(l.r.d.rate, l, stream);
+    const dim3 grid = ps_grid((unsigned)l.n_list, p.r.n_ticks, p.r.n_channels);
+    hipLaunchKernelGGL(k_resample_out_copy, grid, dim3(256), 0, stream, l);
+    return hipGetLastError();
+  });
+  if (rc != hipSuccess) return rc;
   // every row's history, the 48000 rows' too, behind the launches that read it
-  a.r.taps = nullptr;
-  const size_t words = (size_t)p.n_streams * p.n_channels * rs::kMaxTailOut;
-  hipLaunchKernelGGL(k_resample_out_tail_ps, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, a.r);
+  const size_t words = (size_t)p.r.n_streams * p.r.n_channels * rs::kMaxTailOut;
+  hipLaunchKernelGGL(k_resample_out_tail_ps, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, p.r);
   return hipGetLastError();
 }
 

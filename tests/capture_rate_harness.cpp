@@ -3,7 +3,7 @@
 // by its definition: the first clip-rate sample r with r M / L >= x), the due
 // test in either unit for positions that are multiples of 480, the cut of a
 // converted segment in clip-rate units, and cap::to_s16 against lrint in
-// double.  The seven rates are the engine's: 48000 and describe_out's six.
+// double.  The seven rates are the engine's: 48000 and rs::describe's six.
 // Built with -fsanitize=address,undefined by tests/test_capture_den_cpu.py.
 // Usage: capture_rate_harness [cases]
 #include <algorithm>

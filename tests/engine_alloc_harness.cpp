@@ -13,7 +13,9 @@
 //   - kernel launches: every fvad::launch_* and the host helpers the .hip
 //     files define return at once, doing only what the host code reads back.
 //
-// One scenario walks every allocation site of an engine kind.  Run without a
+// One scenario walks every allocation site of an engine kind, the two
+// resamplers' among them (a fixed-rate kind and a per-stream kind, whose rate
+// plans, staging rings and tap tables it reaches).  Run without a
 // failure it must leave nothing live and gives the number N of creating
 // calls; then for every k < N the k-th creating call fails: the API call it
 // fails in must report it, destroy must still release everything, and
@@ -175,12 +177,18 @@ struct Kind {
   const char *name;
   int mode, fft_size, use_denoiser;
   bool machines;  // fused engines refuse device VADMachines (and with them the event feed)
+  // both resamplers: 0 for none, input_rate = denoised_rate = 16000, or
+  // FVAD_INPUT_RATE_PER_STREAM (= FVAD_DENOISED_RATE_PER_STREAM) with both *_rate_max = 48000
+  int rate;
 };
-const Kind kKinds[] = {{"staged", FVAD_MODE_STAGED, 2048, 1, true},
-                       {"staged, fft_size above kMaxFftB", FVAD_MODE_STAGED, 2 * fvad::kMaxFftB, 1, true},
-                       {"fused", FVAD_MODE_FUSED, 2048, 1, false},
-                       {"fp16", FVAD_MODE_FP16, 2048, 1, true},
-                       {"use_denoiser = 0", FVAD_MODE_STAGED, 2048, 0, true}};
+const Kind kKinds[] = {{"staged", FVAD_MODE_STAGED, 2048, 1, true, 0},
+                       {"staged, fft_size above kMaxFftB", FVAD_MODE_STAGED, 2 * fvad::kMaxFftB, 1, true, 0},
+                       {"fused", FVAD_MODE_FUSED, 2048, 1, false, 0},
+                       {"fp16", FVAD_MODE_FP16, 2048, 1, true, 0},
+                       {"use_denoiser = 0", FVAD_MODE_STAGED, 2048, 0, true, 0},
+                       {"staged, resampling at 16000", FVAD_MODE_STAGED, 2048, 1, true, 16000},
+                       {"staged, per-stream rates", FVAD_MODE_STAGED, 2048, 1, true, FVAD_INPUT_RATE_PER_STREAM}};
+static_assert(FVAD_INPUT_RATE_PER_STREAM == FVAD_DENOISED_RATE_PER_STREAM, "Kind::rate");
 
 constexpr int kStreams = 2, kChannels = 1, kTicks = 2;
 int g_fail = 0;
@@ -236,6 +244,12 @@ long run(const Kind &k, long fail_at) {
   cfg.fft_size = k.fft_size;
   cfg.use_denoiser = k.use_denoiser;
   cfg.max_ticks = kTicks;
+  const bool per_stream = k.rate == FVAD_INPUT_RATE_PER_STREAM;
+  if (k.rate) {
+    cfg.input_rate = cfg.denoised_rate = k.rate;
+    cfg.want_denoised = 1;
+    if (per_stream) cfg.input_rate_max = cfg.denoised_rate_max = 48000;
+  }
   fvad_vadm_config vc;
   fvad_vadm_config_default(&vc);
   // the machine's speech band as an engine band
@@ -248,7 +262,14 @@ long run(const Kind &k, long fail_at) {
     all_released("after the failed create", k.name, fail_at);
     return g_fail == fails_before ? g_creates : -1;
   }
-  const size_t n_in = (size_t)kTicks * kStreams * kChannels * 480;
+  // a push's samples (a per-stream engine's streams start at *_rate_max: the largest push)
+  int64_t offsets[kStreams + 1] = {};
+  if (per_stream) {
+    CHECK(fvad_engine_input_layout(e, offsets) == FVAD_OK, "%s: input_layout: %s", k.name, fvad_last_error());
+  } else {
+    offsets[kStreams] = (int64_t)kStreams * kChannels * fvad_engine_input_frame(e);
+  }
+  const size_t n_in = (size_t)kTicks * (size_t)offsets[kStreams];
   const int32_t stream0 = 0;
   if (k.machines) {
     step("attach_vadm", [&] { return fvad_engine_attach_vadm(e, &vc, 1, 4) < 0; }, true);
@@ -260,13 +281,20 @@ long run(const Kind &k, long fail_at) {
     std::memset(slot, 0, n_in * sizeof(float));
     return fvad_engine_submit(e, slot, kTicks, nullptr) < 0;
   });
+  if (per_stream) {  // between two pushes: the next one syncs both plans' tables a second time (a second staging row each)
+    const int rate = 16000;
+    step("set_stream_rates", [&] { return fvad_engine_set_stream_rates(e, &stream0, 1, &rate) < 0; });
+    step("set_stream_denoised_rates", [&] { return fvad_engine_set_stream_denoised_rates(e, &stream0, 1, &rate) < 0; });
+  }
   step("submit_i16", [&] {
     const std::vector<int16_t> pcm(n_in, 0);
     return fvad_engine_submit_i16(e, pcm.data(), kTicks, nullptr, nullptr) < 0;
   });
   for (int i = 0; i < 2; i++) step("collect", [&] { return fvad_engine_collect(e, nullptr, nullptr) < 0; });
-  step("load_synthetic_ex", [&] { return fvad_engine_load_synthetic_ex(e, kTicks, 2, 0) < 0; });
-  for (int i = 0; i < 2; i++) step("run_resident", [&] { return fvad_engine_run_resident(e, kTicks) < 0; });
+  if (!k.rate) {  // (a resampling engine refuses both)
+    step("load_synthetic_ex", [&] { return fvad_engine_load_synthetic_ex(e, kTicks, 2, 0) < 0; });
+    for (int i = 0; i < 2; i++) step("run_resident", [&] { return fvad_engine_run_resident(e, kTicks) < 0; });
+  }
   step("set_debug", [&] { return fvad_engine_set_debug(e, FVAD_DEBUG_RESET_TIMES, 1) < 0; });
   step("reset_streams", [&] { return fvad_engine_reset_streams(e, &stream0, 1) < 0; });
   std::vector<char> blob;

@@ -319,7 +319,7 @@ def test_engine_objects_export_only_the_api(fvad_mod):
     hdr = open(os.path.join(ROOT, "include", "fvad.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     api = set(re.findall(r"\b(fvad_[A-Za-z0-9_]*)\s*\(", hdr)) | {"fvad_engine_set_raw_s16"}
-    units = ["fvad_engine", "fvad_engine_ingest", "fvad_engine_vadm", "fvad_engine_lifecycle"]
+    units = ["fvad_engine", "fvad_engine_ingest", "fvad_engine_rates", "fvad_engine_vadm", "fvad_engine_lifecycle"]
     subprocess.check_call(["make", "-s", "-j", "4", "-C", PKG] + ["build/%s.cpp.o" % u for u in units])
     objs = sorted(glob.glob(os.path.join(PKG, "build", "fvad_engine*.cpp.o")))
     assert len(objs) == len(units), objs
@@ -339,7 +339,11 @@ def test_engine_objects_export_only_the_api(fvad_mod):
 def test_engine_releases_everything_when_an_allocation_fails():
     """tests/engine_alloc_harness.cpp: the engine's host objects over a stub HIP
     runtime that fails each creating call in turn, for staged (fft_size 2048
-    and above kMaxFftB), fused, fp16 and use_denoiser = 0 engines.  The failing
+    and above kMaxFftB), fused, fp16 and use_denoiser = 0 engines, and for two
+    staged engines with both resamplers: input_rate = denoised_rate = 16000, and
+    per-stream rates in both directions (both *_rate_max = 48000), whose rate
+    plans' tables are synced a second time after a change of stream 0's rates
+    between two submits.  The failing
     API call reports it, fvad_engine_destroy leaves no device memory, pinned
     memory, event or stream live, and a failed attach_vadm / enable_events
     succeeds when called again.  The same for a config sweep (fvad_sweep.cpp):
@@ -357,8 +361,8 @@ def test_engine_releases_everything_when_an_allocation_fails():
                          timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.strip().splitlines()
-    assert lines[-1] == "ok" and len(lines) == 7, out.stdout
-    for line in lines[:5]:
+    assert lines[-1] == "ok" and len(lines) == 9, out.stdout
+    for line in lines[:7]:
         m = re.search(r": (\d+) creating calls, (\d+) of them failed in turn and survived", line)
         assert m and int(m[1]) == int(m[2]) >= 40, line
-    assert lines[5] == "sweep: 24 creating calls, 24 of them failed in turn and survived"
+    assert lines[7] == "sweep: 24 creating calls, 24 of them failed in turn and survived"
