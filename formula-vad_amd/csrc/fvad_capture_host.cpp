@@ -25,7 +25,7 @@ static_assert(sizeof(fvad::CapSetArgs) <= 4096 && sizeof(fvad::CapPassArgs) <= 4
 namespace {
 
 constexpr size_t kDefaultPool = (size_t)64 << 20;
-constexpr int kFlushSlot = fvad_engine::kEvHeaders;  // the header slot of a flush
+constexpr int kFlushSlot = kEvHeaders;  // the header slot of a flush
 
 fvad::CapPassArgs pass_args(const fvad_engine *e, const fvad::VadmArgs &v) {
   const Capture &c = *e->cap;
@@ -89,9 +89,9 @@ int fvad::eng::capture_append(fvad_engine *e, const fvad::StagedArgs &a, int b, 
   p.snap = c.snap[b].get();
   p.frame = fvad::kFrame;
   int rc;
-  if (timed && (rc = c.at[b].begin(s))) return rc;
+  if (timed && (rc = c.tm.begin(b, s))) return rc;
   HIP_TRY(fvad::launch_hist_append(p, s));
-  if (timed && (rc = c.at[b].end(s))) return rc;
+  if (timed && (rc = c.tm.end(b, s, Capture::kAppend))) return rc;
   return FVAD_OK;
 }
 
@@ -126,9 +126,9 @@ int fvad::eng::capture_append_den(fvad_engine *e, const fvad::StagedArgs &a, int
   // ahead of it are (a host-fed push is never a sampled one)
   (void)timed;
   int rc;
-  if ((rc = c.at[b].collect(c.ms_sum[0], c.n_timed[0])) || (rc = c.at[b].begin(s))) return rc;
+  if ((rc = c.tm.collect(b)) || (rc = c.tm.begin(b, s))) return rc;
   HIP_TRY(fvad::launch_hist_append(p, s));
-  return c.at[b].end(s);
+  return c.tm.end(b, s, Capture::kAppend);
 }
 
 // The capture pass of push `push` (parity b) on the side stream, behind its
@@ -139,17 +139,17 @@ int fvad::eng::capture_pass(fvad_engine *e, const fvad::VadmArgs &v, uint64_t pu
   Capture &c = *e->cap;
   // the header slot is free: at most kEvHeaders passes in flight
   int rc = events_retire(e, false);
-  if (!rc && e->ev_flight.size() >= (size_t)fvad_engine::kEvHeaders) rc = events_retire(e, true);
+  if (!rc && e->feed.flight.size() >= (size_t)kEvHeaders) rc = events_retire(e, true);
   if (rc) return rc;
   fvad::CapPassArgs a = pass_args(e, v);
   a.flush_mode = 0;
   a.pos = c.snap[b].get();
-  a.pass = e->ev_pass_next;
+  a.pass = e->feed.pass_next;
   a.push = push;
-  a.header = c.dv_hdr + a.pass % fvad_engine::kEvHeaders;
-  if (timed && (rc = c.pt[slot].begin(e->side))) return rc;
+  a.header = c.dv_hdr + a.pass % kEvHeaders;
+  if (timed && (rc = c.tm.begin(Capture::kPassSlot + slot, e->side))) return rc;
   HIP_TRY(fvad::launch_capture_pass(a, e->side));
-  if (timed && (rc = c.pt[slot].end(e->side))) return rc;
+  if (timed && (rc = c.tm.end(Capture::kPassSlot + slot, e->side, Capture::kPass))) return rc;
   HIP_TRY(hipEventRecord(c.ev_pass[b].get(), e->side));
   return FVAD_OK;
 }
@@ -157,7 +157,7 @@ int fvad::eng::capture_pass(fvad_engine *e, const fvad::VadmArgs &v, uint64_t pu
 // events_retire saw the `done` event of pass `pass` complete
 int fvad::eng::capture_retire(fvad_engine *e, uint64_t pass) {
   Capture &c = *e->cap;
-  const volatile fvad::CapHeader *h = c.hdr.get() + pass % fvad_engine::kEvHeaders;
+  const volatile fvad::CapHeader *h = c.hdr.get() + pass % kEvHeaders;
   if (h->pass != pass) return fail(FVAD_EDEVICE, "clip capture: a finished pass left no header");
   take_header(c, h);
   return FVAD_OK;
@@ -171,9 +171,9 @@ int fvad::eng::capture_reset(fvad_engine *e) {
   for (auto &sn : c.snap) HIP_TRY(hipMemset(sn.get(), 0, B * sizeof(fvad::CapPos)));
   HIP_TRY(hipMemset(c.pend_n.get(), 0, B * sizeof(unsigned)));
   HIP_TRY(hipMemset(c.state.get(), 0, sizeof(fvad::CapState)));
-  std::memset(c.hdr.get(), 0xff, sizeof(fvad::CapHeader) * (fvad_engine::kEvHeaders + 1));
+  std::memset(c.hdr.get(), 0xff, sizeof(fvad::CapHeader) * (kEvHeaders + 1));
   c.desc_read = c.desc_end = c.pool_read = c.pool_end = c.lost = 0;
-  for (int k = 0; k < 2; k++) c.at[k].pending = c.pt[k].pending = false;
+  c.tm.drop();
   return FVAD_OK;
 }
 
@@ -200,13 +200,7 @@ int fvad::eng::capture_set_streams(fvad_engine *e, const int32_t *streams, const
 }
 
 int fvad::eng::capture_collect_timing(fvad_engine *e) {
-  if (!e->cap) return FVAD_OK;
-  Capture &c = *e->cap;
-  int rc;
-  for (int k = 0; k < 2; k++)
-    if ((rc = c.at[k].collect(c.ms_sum[0], c.n_timed[0])) || (rc = c.pt[k].collect(c.ms_sum[1], c.n_timed[1])))
-      return rc;
-  return FVAD_OK;
+  return e->cap ? e->cap->tm.collect() : FVAD_OK;
 }
 
 // All or nothing, as fvad_engine_attach_vadm: everything is made in a local
@@ -245,12 +239,12 @@ extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_
     return fail(FVAD_EINVAL, "a capture of the denoised rows needs an engine created with want_denoised");
   if (den && e->ro && e->ro->plan.on())  // (clips at a stream's own rate: not built)
     return fail(FVAD_EINVAL, "a capture of the denoised rows is not available with per-stream denoised rates");
-  if (e->vadm.n == 0 || !e->events_on)
+  if (!e->vadm.on() || !e->feed.on())
     return fail(FVAD_EINVAL, "clip capture needs fvad_engine_attach_vadm and fvad_engine_enable_events first");
   if (e->cap) return fail(FVAD_EINVAL, "capture already enabled");
   if (e->cfg.mode == FVAD_MODE_FUSED || !e->cfg.use_denoiser)
     return fail(FVAD_EINVAL, "clip capture needs a staged-family engine with the denoiser");
-  if (machine < 0 || machine >= e->vadm.n) return fail(FVAD_EINVAL, "no such attached machine");
+  if (machine < 0 || machine >= e->vadm.args.n) return fail(FVAD_EINVAL, "no such attached machine");
   if (!(history_sec >= 4.0) || !(history_sec <= 86400.0))
     return fail(FVAD_EINVAL, "history_sec must be at least 4 (two seconds of margin at each end)");
   for (const auto &sl : e->slots)
@@ -283,11 +277,10 @@ extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_
       (rc = fvad::make_dev(c->flush, B)) ||
       (rc = s16 ? fvad::make_pinned(c->pool16, c->pool_cap) : fvad::make_pinned(c->pool, c->pool_cap)) ||
       (rc = fvad::make_pinned(c->desc, c->desc_cap)) ||
-      (rc = fvad::make_pinned(c->hdr, (size_t)fvad_engine::kEvHeaders + 1)) || (rc = fvad::make_event(c->ev_pass[0])) ||
+      (rc = fvad::make_pinned(c->hdr, (size_t)kEvHeaders + 1)) || (rc = fvad::make_event(c->ev_pass[0])) ||
       (rc = fvad::make_event(c->ev_pass[1])))
     return rc;
-  for (int k = 0; k < 2; k++)
-    if ((rc = c->at[k].create()) || (rc = c->pt[k].create())) return rc;
+  if ((rc = c->tm.create())) return rc;
   void *dv_pool = nullptr, *dv_desc = nullptr, *dv_hdr = nullptr;
   if (hipHostGetDevicePointer(&dv_pool, s16 ? (void *)c->pool16.get() : (void *)c->pool.get(), 0) != hipSuccess ||
       hipHostGetDevicePointer(&dv_desc, c->desc.get(), 0) != hipSuccess ||
@@ -324,7 +317,7 @@ extern "C" int fvad_engine_enable_capture_ex(fvad_engine *e, const fvad_capture_
     (void)hipGetLastError();
     return fail(FVAD_EDEVICE, "initialising clip capture failed");
   }
-  std::memset(c->hdr.get(), 0xff, sizeof(fvad::CapHeader) * (fvad_engine::kEvHeaders + 1));
+  std::memset(c->hdr.get(), 0xff, sizeof(fvad::CapHeader) * (kEvHeaders + 1));
   // nothing below fails
   e->cap = std::move(c);
   return FVAD_OK;
@@ -414,7 +407,7 @@ extern "C" int fvad_engine_capture_flush(fvad_engine *e, const int32_t *streams,
   HIP_TRY(hipSetDevice(e->cfg.device));
   Capture &c = *e->cap;
   if (streams) HIP_TRY(hipMemcpy(c.flush.get(), flags.data(), B, hipMemcpyHostToDevice));
-  fvad::CapPassArgs a = pass_args(e, e->vadm);
+  fvad::CapPassArgs a = pass_args(e, e->vadm.args);
   a.flush_mode = streams ? 1 : 2;
   a.flush = c.flush.get();
   a.pos = c.pos.get();
@@ -435,7 +428,7 @@ extern "C" int fvad_engine_capture_times(fvad_engine *e, double *ms_avg, int *n_
   if (!e->cap) return fail(FVAD_EINVAL, "capture not enabled");
   if (const int rc = fvad_engine_sync(e)) return rc;
   const Capture &c = *e->cap;
-  for (int k = 0; k < 2; k++) ms_avg[k] = c.n_timed[k] ? c.ms_sum[k] / c.n_timed[k] : 0.0;
-  if (n_runs) *n_runs = c.n_timed[1];
+  c.tm.read(Capture::kAppend, &ms_avg[0], nullptr);
+  c.tm.read(Capture::kPass, &ms_avg[1], n_runs);
   return FVAD_OK;
 }

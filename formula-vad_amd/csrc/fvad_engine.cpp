@@ -1,4 +1,5 @@
-// Batched multi-stream engine (C ABI in include/fvad.h).
+// Batched multi-stream engine (C ABI in include/fvad.h): the push path, fetch
+// and the timing reads (construction: fvad_engine_create.cpp).
 //
 // One engine owns one GPU and a partition of streams.  Device memory layout
 // (all HBM, sized for thousands of streams; 288 GB per MI355X leaves room for
@@ -25,8 +26,6 @@
 
 #include "fvad_engine_impl.h"
 
-const fvad::HostModel *fvad_model_host(const fvad_model *m);
-
 using namespace fvad::eng;
 
 namespace {
@@ -45,136 +44,8 @@ void fvad_engine_set_raw_s16(fvad_engine *e, int raw) {
   if (!e->rs) e->raw_s16 = raw;
 }
 
-extern "C" void fvad_engine_config_default(fvad_engine_config *c, int n_streams, int n_channels) {
-  std::memset(c, 0, sizeof(*c));
-  c->n_streams = n_streams;
-  c->n_channels = n_channels;
-  c->device = 0;
-  c->sample_rate = 48000;
-  c->fft_size = 2048;
-  c->max_ticks = 100;
-  c->n_bands = 1;
-  // VADMachine defaults: freqToBin(100) .. freqToBin(1500) at 48 kHz / 2048 (FFT.zig:120-131)
-  c->band_lo[0] = 4;
-  c->band_hi[0] = 64;
-  c->want_denoised = 0;
-  c->use_denoiser = 1;
-  c->denoised_rate_max = 0;
-  c->input_rate_max = 0;
-  c->denoised_rate = 0;
-  c->input_rate = 0;
-  c->want_spectrum = 0;
-  c->spec_lo = 0;
-  c->spec_hi = 1024;
-}
-
 namespace {
-
 using fvad::make_dev;
-using fvad::make_event;
-
-// int8 GRU-stack image for k_rnn3 (layout: fvad_internal.h rnnimg).  Term j of
-// a column's C-order sum lives in segment g at seg_off(g) + (j - start of g).
-void build_rnn_image(const fvad::HostModel &hm, std::vector<int8_t> &img, int *act) {
-  namespace R = fvad::rnnimg;
-  img.assign(R::kBytes, 0);
-  const int8_t *b = hm.blob;
-  auto put = [&](int m, int c, int j, int8_t v) {
-    int g = 0, base = 0;
-    while (j >= base + R::kSegs[m][g]) base += R::kSegs[m][g++];
-    img[R::off_w(m) + c * R::stride(m) + R::seg_off(m, g) + (j - base)] = v;
-  };
-  auto dense = [&](int m, int l) {
-    const fvad::HostLayer &L = hm.layers[l];
-    for (int c = 0; c < L.nout; c++) {
-      img[R::off_b(m) + c] = b[L.off_b + c];
-      for (int j = 0; j < L.nin; j++) put(m, c, j, b[L.off_w + (size_t)j * L.nout + c]);
-    }
-    act[m] = L.act;
-  };
-  auto gru = [&](int mg, int mh, int l) {
-    const fvad::HostLayer &L = hm.layers[l];
-    const int N = L.nout, M = L.nin, S3 = 3 * N;
-    for (int col = 0; col < S3; col++) {
-      const int m = col < 2 * N ? mg : mh, c = col < 2 * N ? col : col - 2 * N;
-      img[R::off_b(m) + c] = b[L.off_b + col];
-      for (int j = 0; j < M; j++) put(m, c, j, b[L.off_w + (size_t)j * S3 + col]);
-      for (int j = 0; j < N; j++) put(m, c, M + j, b[L.off_r + (size_t)j * S3 + col]);
-    }
-    act[mg] = fvad::kActSigmoid;
-    act[mh] = L.act;
-  };
-  dense(0, 0);
-  gru(1, 2, 1);
-  gru(3, 4, 2);
-  gru(5, 6, 3);
-  dense(7, 4);
-  dense(8, 5);
-}
-
-// every int8 array of the model (what fvad_model_blob returns)
-uint64_t model_hash_of(const fvad::HostModel &hm) { return fnv1a(kFnvBasis, hm.blob, hm.blob_size); }
-
-int upload_model(fvad_engine *e, const fvad::HostModel &hm) {
-  std::vector<float> w(hm.blob_size);
-  for (size_t i = 0; i < hm.blob_size; i++) w[i] = (float)hm.blob[i];
-  int rc = make_dev(e->d_weights, w.size());
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(e->d_weights.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-  auto dense = [&](int l) {
-    const fvad::HostLayer &L = hm.layers[l];
-    fvad::DevDense d;
-    d.nin = L.nin;
-    d.nout = L.nout;
-    d.act = L.act;
-    d.w = e->d_weights.get() + L.off_w;
-    d.b = e->d_weights.get() + L.off_b;
-    return d;
-  };
-  auto gru = [&](int l) {
-    const fvad::HostLayer &L = hm.layers[l];
-    fvad::DevGru g;
-    g.nin = L.nin;
-    g.nout = L.nout;
-    g.act = L.act;
-    g.win = e->d_weights.get() + L.off_w;
-    g.wrec = e->d_weights.get() + L.off_r;
-    g.b = e->d_weights.get() + L.off_b;
-    return g;
-  };
-  for (int l = 0; l < 6; l++) {
-    const fvad::HostLayer &L = hm.layers[l];
-    const int m = l == 0 ? 0 : l == 1 ? 1 : l == 2 ? 3 : l == 3 ? 5 : l == 4 ? 7 : 8;
-    if (L.nin != fvad::rnnimg::kKin[m] || (l >= 1 && l <= 3 ? 2 * L.nout : L.nout) != fvad::rnnimg::kCols[m])
-      return fail(FVAD_EFORMAT, "model layer shapes differ from the rnnoise classic model");
-  }
-  {
-    std::vector<int8_t> img;
-    build_rnn_image(hm, img, e->rnn_act);
-    rc = make_dev(e->d_rnn_img, img.size());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(e->d_rnn_img.get(), img.data(), img.size(), hipMemcpyHostToDevice));
-    if (fp16_mode(e->cfg.mode)) {  // MFMA fragments of the same image (fvad_gru16.hip)
-      std::vector<uint16_t> frags((size_t)fvad::gru16_frag_count() * 64 * 8);
-      std::vector<float> bias(fvad::gru16_bias_rows());
-      fvad::gru16_build(img.data(), frags.data(), bias.data());
-      if ((rc = make_dev(e->d_gru16, frags.size())) || (rc = make_dev(e->d_gru16_bias, bias.size()))) return rc;
-      HIP_TRY(hipMemcpy(e->d_gru16.get(), frags.data(), frags.size() * 2, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(e->d_gru16_bias.get(), bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    }
-  }
-  e->dmodel.in_dense = dense(0);
-  e->dmodel.vad = gru(1);
-  e->dmodel.noise = gru(2);
-  e->dmodel.den = gru(3);
-  e->dmodel.den_out = dense(4);
-  e->dmodel.vad_out = dense(5);
-  rc = make_dev(e->d_model, 1);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(e->d_model.get(), &e->dmodel, sizeof(fvad::DevModel), hipMemcpyHostToDevice));
-  return FVAD_OK;
-}
-
 }  // namespace
 
 extern "C" int fvad_engine_reset(fvad_engine *e) {
@@ -182,19 +53,19 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
   HIP_TRY(hipSetDevice(e->cfg.device));
   if (e->cstream) HIP_TRY(hipStreamSynchronize(e->cstream.get()));
   if (e->pstream) HIP_TRY(hipStreamSynchronize(e->pstream));
-  if (e->vadm.n > 0) {
-    e->vpend = false;  // the pending push's machine state is wiped below: not run
-    e->vowed = false;
+  if (e->vadm.on()) {
+    e->vadm.pend = false;  // the pending push's machine state is wiped below: not run
+    e->vadm.owed = false;
     HIP_TRY(hipStreamSynchronize(e->stream.get()));
     HIP_TRY(hipStreamSynchronize(e->side));
     int rc = vadm_reset(e);
-    if (!rc && e->events_on) rc = events_reset(e);
+    if (!rc && e->feed.on()) rc = events_reset(e);
     if (rc) return rc;
   }
   e->push_count = 0;
   HIP_TRY(hipMemsetAsync(e->d_state.get(), 0, sizeof(float) * fvad::st::kWords * (size_t)e->cfg.n_streams, e->stream.get()));
   e->res_next = 0;  // fresh streams start at the resident cycle's first push (t = 0)
-  if (e->d_work) HIP_TRY(hipMemsetAsync(e->d_work.get(), 0, sizeof(unsigned) * fvad::kWorkCounters, e->stream.get()));
+  if (e->sg) HIP_TRY(hipMemsetAsync(e->sg->d_work.get(), 0, sizeof(unsigned) * fvad::kWorkCounters, e->stream.get()));
   HIP_TRY(hipMemsetAsync(e->d_ring.get(), 0,
                          sizeof(float) * (size_t)e->ring_len * e->cfg.n_channels * e->cfg.n_streams, e->stream.get()));
   if (const int rc = resample_reset(e)) return rc;
@@ -202,8 +73,8 @@ extern "C" int fvad_engine_reset(fvad_engine *e) {
   return FVAD_OK;
 }
 
-namespace {
-void fill_bands(const fvad_engine_config &c, int *band_lo, int *band_hi, int *lo_all, int *hi_all) {
+// a config's bands as the argument blocks carry them, and the bins they span
+void fvad::eng::fill_bands(const fvad_engine_config &c, int *band_lo, int *band_hi, int *lo_all, int *hi_all) {
   int lo = 1 << 30, hi = -1;
   for (int b = 0; b < fvad::kMaxBandCfg; b++) {
     band_lo[b] = b < c.n_bands ? c.band_lo[b] : 0;
@@ -217,281 +88,13 @@ void fill_bands(const fvad_engine_config &c, int *band_lo, int *band_hi, int *lo
   *hi_all = hi;
 }
 
-// fvad_engine_create's check of input_rate / denoised_rate and its *_rate_max:
-// per-stream, rate_max is a listed rate or 48000; otherwise rate_max is 0 and
-// the rate, when it is not 0 or 48000, a listed one, described in d
-struct RateTexts {
-  const char *max_off_list, *max_unread, *rate_off_list;
-};
-int check_rate(int rate, int rate_max, bool per_stream, fvad::rs::Dir dir, fvad::rs::Desc &d, const RateTexts &t) {
-  if (per_stream) return fvad::rs::rate_index(rate_max) < 0 ? fail(FVAD_ERATE, t.max_off_list) : FVAD_OK;
-  if (rate_max != 0) return fail(FVAD_ERATE, t.max_unread);
-  if (rate != 0 && rate != 48000 && !fvad::rs::describe(rate, dir, d)) return fail(FVAD_ERATE, t.rate_off_list);
-  return FVAD_OK;
-}
-
-}  // namespace
-
-// one set of window outputs (the pass's ticks copy is attach_vadm's)
-int fvad::eng::make_win_out(const fvad_engine *e, fvad_engine::WinOut &w) {
-  const fvad_engine_config &c = e->cfg;
-  const size_t TB = (size_t)c.max_ticks * c.n_streams, TBW = TB * e->wpt;  // window slots
-  int rc;
-  if ((rc = make_dev(w.ratio, TBW)) || (rc = make_dev(w.vad, TBW)) || (rc = make_dev(w.flag, TB)) ||
-      (rc = make_dev(w.band, TBW * c.n_channels * c.n_bands)))
-    return rc;
-  return FVAD_OK;
-}
-
 // the push about to launch writes window-output set b
 void fvad::eng::use_win_out(fvad_engine *e, int b) {
-  const fvad_engine::WinOut &w = e->wout[e->wout[1].flag ? b : 0];
+  const WinOut &w = b && e->vadm.on() ? e->vadm.set1 : e->wout0;
   e->d_wflag = w.flag.get();
   e->d_wratio = w.ratio.get();
   e->d_wvad = w.vad.get();
   e->d_band = w.band.get();
-}
-
-extern "C" int fvad_engine_create(const fvad_engine_config *cfg, const fvad_model *model, fvad_engine **out) {
-  if (!cfg || !model || !out) return fail(FVAD_EINVAL, "null argument");
-  const fvad_engine_config &c = *cfg;
-  if (c.sample_rate != 48000) return fail(FVAD_ERATE, "only 48 kHz is supported (VAD.zig:101-104)");
-  // input_rate: 0 or 48000 for none, or a rate k_resample brings to 48 kHz;
-  // FVAD_INPUT_RATE_PER_STREAM: every stream its own rate, up to input_rate_max
-  const bool resample = c.input_rate != 0 && c.input_rate != 48000;
-  const bool per_stream = c.input_rate == FVAD_INPUT_RATE_PER_STREAM;
-  fvad::rs::Desc rd{};
-  if (const int rc = check_rate(c.input_rate, c.input_rate_max, per_stream, fvad::rs::Dir::kIn, rd,
-                                {"input_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000",
-                                 "input_rate_max is read only with input_rate = FVAD_INPUT_RATE_PER_STREAM",
-                                 "input_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000"}))
-    return rc;
-  // denoised_rate: 0 or 48000 for the 48 kHz signal, or a rate k_resample_out brings it to;
-  // FVAD_DENOISED_RATE_PER_STREAM: every stream its own rate, up to denoised_rate_max
-  const bool resample_out = c.denoised_rate != 0 && c.denoised_rate != 48000;
-  const bool per_stream_out = c.denoised_rate == FVAD_DENOISED_RATE_PER_STREAM;
-  fvad::rs::Desc od{};
-  if (const int rc = check_rate(c.denoised_rate, c.denoised_rate_max, per_stream_out, fvad::rs::Dir::kOut, od,
-                                {"denoised_rate_max must be 8000, 16000, 24000, 32000, 44100, 48000 or 96000",
-                                 "denoised_rate_max is read only with denoised_rate = FVAD_DENOISED_RATE_PER_STREAM",
-                                 "denoised_rate must be 0, 48000, 8000, 16000, 24000, 32000, 44100 or 96000"}))
-    return rc;
-  if (per_stream_out) {
-    if (c.want_denoised != 1 || !c.use_denoiser)
-      return fail(FVAD_EINVAL, "per-stream denoised rates need want_denoised = 1 and use_denoiser = 1");
-    if (c.max_ticks > 65535) return fail(FVAD_EINVAL, "per-stream denoised rates: max_ticks <= 65535 (a grid dimension)");
-  }
-  if (resample_out && !per_stream_out && (!c.want_denoised || !c.use_denoiser))
-    return fail(FVAD_EINVAL, "denoised_rate needs want_denoised = 1 and use_denoiser = 1");
-  if (c.n_streams < 1 || c.n_channels < 1 || c.n_channels > FVAD_MAX_CHANNELS)
-    return fail(FVAD_EINVAL, "n_streams >= 1 and 1 <= n_channels <= 8 required");
-  // FFT.zig:29-31: any even, non-zero size.  fft_size < 480 completes several
-  // windows per tick (VAD.zig:307-347; fvad_engine_windows_per_tick slots per
-  // tick in the window outputs); kMaxFftSize keeps window indices in 32 bits
-  if (c.fft_size < 2 || (c.fft_size & 1) || c.fft_size > fvad::kMaxFftSize)
-    return fail(FVAD_EINVAL, "fft_size must be even, 2 <= fft_size <= 4194304 (FFT.zig:29-31)");
-  if (c.mode == FVAD_MODE_FUSED) {
-    int n = c.fft_size / 2;
-    for (int p : {4, 2, 3, 5})
-      while (n % p == 0) n /= p;
-    if (n != 1 || c.fft_size > 2048 || c.fft_size < fvad::kFrame)
-      return fail(FVAD_EINVAL, "fused mode: 480 <= fft_size <= 2048 with radices 2, 3, 4, 5 (use the staged mode)");
-  }
-  if (!c.use_denoiser && c.mode == FVAD_MODE_FUSED)
-    return fail(FVAD_EINVAL, "use_denoiser = 0 runs on the staged engine");
-  if (c.max_ticks < 1) return fail(FVAD_EINVAL, "max_ticks must be >= 1");
-  if (c.n_bands < 1 || c.n_bands > FVAD_MAX_BANDS) return fail(FVAD_EINVAL, "1 <= n_bands <= 4");
-  int lo = 1 << 30, hi = -1;
-  for (int b = 0; b < c.n_bands; b++) {
-    if (c.band_lo[b] < 0 || c.band_hi[b] < c.band_lo[b] || c.band_hi[b] > c.fft_size / 2)
-      return fail(FVAD_EINVAL, "invalid band range");
-    lo = std::min(lo, c.band_lo[b]);
-    hi = std::max(hi, c.band_hi[b]);
-  }
-  if (hi - lo + 1 > 256 && (c.mode == FVAD_MODE_FUSED || c.fft_size == 2048))
-    return fail(FVAD_EINVAL, "reported bins must span <= 256");
-  if (c.mode != FVAD_MODE_STAGED && c.mode != FVAD_MODE_FUSED && !fp16_mode(c.mode) && c.mode != FVAD_MODE_F32_FAST)
-    return fail(FVAD_EINVAL, "unknown engine mode");
-  if (c.want_spectrum) {
-    if (c.mode == FVAD_MODE_FUSED) return fail(FVAD_EINVAL, "want_spectrum runs on the staged engines (k_frame has no tap)");
-    if (c.spec_lo < 0 || c.spec_hi < c.spec_lo || c.spec_hi > c.fft_size / 2)
-      return fail(FVAD_EINVAL, "invalid spectrum range: 0 <= spec_lo <= spec_hi <= fft_size / 2 required");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FVAD_EDEVICE, "no HIP device available");
-  if (c.device < 0 || c.device >= ndev) return fail(FVAD_EDEVICE, "device ordinal out of range");
-
-  fvad_engine *e = new fvad_engine();
-  e->cfg = c;
-  if (!resample) e->cfg.input_rate = 0;
-  if (!resample_out) e->cfg.denoised_rate = 0;
-  // the staged path writes every tick of a push before FFT B reads its
-  // windows, so the ring holds one window plus a whole push
-  // the re-block ring holds a window plus a push; a multiple of 4 so a
-  // frame's float4 writes never straddle its end (k_ola, k_ndring)
-  e->ring_len = (c.fft_size + c.max_ticks * fvad::kFrame + 3) & ~3;
-  e->n_kernels = 2;  // fused: k_prep, k_frame
-  if (c.mode != FVAD_MODE_FUSED) {
-    // the kernels of this engine's pushes (launch_staged's variant: run_staged
-    // sets a.fma, a.gru16_frags and a.fuse16 from the mode)
-    fvad::StagedArgs probe{};
-    probe.nfft_b = c.fft_size;
-    probe.n_channels = c.n_channels;
-    const bool olafb = c.use_denoiser && fvad::olafb_fused(probe);
-    e->kernels = fvad::staged_kernels({c.mode == FVAD_MODE_F32_FAST && c.use_denoiser, fp16_mode(c.mode),
-                                       c.mode == FVAD_MODE_FP16_FUSED, olafb});
-    e->n_kernels = e->kernels.n;
-    if (c.want_spectrum && c.fft_size == 2048)  // the tap twins' names in the FFT-B slot (fvad_wave.hip)
-      for (int i = 0; i < e->kernels.n; i++) {
-        fvad::StagedKernel &k = e->kernels.k[i];
-        if (k.stage == fvad::kStageOla && olafb) k.name = "k_olafb_spec";
-        if (k.stage == fvad::kStageFftB) k.name = "k_fftbw_spec";
-      }
-  }
-  e->n_events = c.mode != FVAD_MODE_FUSED ? fvad::kStagedEvents : 3;
-  e->last_event = c.mode != FVAD_MODE_FUSED ? fvad::kStagedLast : 2;
-  static_assert(fvad::kStagedEvents <= FVAD_MAX_TIMES, "timing events");
-  auto bail = [&](int rc) {
-    delete e;
-    return rc;
-  };
-  if (hipSetDevice(c.device) != hipSuccess) return bail(fail(FVAD_EDEVICE, "hipSetDevice failed"));
-  int rc = fvad::make_stream(e->stream);
-  if (rc) return bail(rc);
-  if (c.mode != FVAD_MODE_FUSED) {
-    fvad::stream_ptr prep;
-    if ((rc = fvad::make_stream(prep)) || (rc = make_event(e->ev_prep_done[0])) ||
-        (rc = make_event(e->ev_prep_done[1])) || (rc = make_event(e->ev_buf_free[0])) ||
-        (rc = make_event(e->ev_buf_free[1])) || (rc = make_event(e->ev_fft_a)) || (rc = make_event(e->ev_synth)))
-      return bail(rc);
-    e->pstream_ref = std::move(prep);
-    e->pstream = e->pstream_ref.get();
-  }
-  for (int i = 0; i < e->n_events; i++)
-    for (int k = 0; k < 2; k++) {
-      if ((rc = make_event(e->evs_own[k][i], true))) return bail(rc);
-      e->evs[k][i] = e->evs_own[k][i].get();
-    }
-  fvad::Plan *plan = new fvad::Plan();
-  fvad::build_plan(plan, c.fft_size);
-  e->wpt = fvad::windows_per_tick(c.fft_size);
-  if (c.fft_size > fvad::kMaxFftB) {  // FFT B's tables outside the plan: [tw | sup | hann | perm]
-    const size_t n = c.fft_size;
-    std::vector<float> tab(n + n / 2 + n + n / 2);
-    int *perm = reinterpret_cast<int *>(tab.data() + n + n / 2 + n);
-    plan->norm_b = fvad::build_fftb_tables(c.fft_size, plan->fac_b, tab.data(), tab.data() + n, perm,
-                                           tab.data() + n + n / 2);
-    rc = make_dev(e->d_fbtab, tab.size());
-    if (!rc && hipMemcpy(e->d_fbtab.get(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail(FVAD_EDEVICE, "FFT-B table upload failed");
-  }
-  if (!rc) rc = make_dev(e->d_plan, 1);
-  if (!rc && hipMemcpy(e->d_plan.get(), plan, sizeof(fvad::Plan), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(FVAD_EDEVICE, "plan upload failed");
-  delete plan;
-  if (rc) return bail(rc);
-  if ((rc = upload_model(e, *fvad_model_host(model)))) return bail(rc);
-  e->model_hash = model_hash_of(*fvad_model_host(model));
-  const size_t B = c.n_streams, C = c.n_channels, T = c.max_ticks;
-  const size_t frames = T * B * C * fvad::kFrame;
-  if ((rc = make_dev(e->d_state, B * fvad::st::kWords)) || (rc = make_dev(e->d_ring, B * C * e->ring_len)) ||
-      (rc = make_dev(e->d_pcm_b[0], frames)) || (rc = make_dev(e->d_pcm_b[1], frames)) ||
-      (rc = make_dev(e->d_ratio_b[0], T * B)) ||
-      (rc = make_dev(e->d_vad, T * B)) || (rc = make_win_out(e, e->wout[0])) ||
-      (rc = make_dev(e->d_ticks_b[0], 2 * B)) || (c.want_denoised && (rc = make_dev(e->d_den, frames))))
-    return bail(rc);
-  e->d_pcm = e->d_pcm_b[0].get();
-  if ((rc = make_event(e->ev_in_free[0])) || (rc = make_event(e->ev_in_free[1]))) return bail(rc);
-  e->d_ratio = e->d_ratio_b[0].get();
-  e->d_ticks = e->d_ticks_b[0].get();
-  use_win_out(e, 0);
-  if (c.mode == FVAD_MODE_FUSED) {
-    if ((rc = make_dev(e->d_xbuf, frames))) return bail(rc);
-  } else {
-    e->V = (int)(T * C);
-    e->L = (fvad::kPitchBuf - fvad::kFrame) + e->V * fvad::kFrame;
-    e->LX = e->L / 2;
-    e->wmax = (int)(T * fvad::kFrame / c.fft_size) + 2;
-    const size_t F = B * e->V;
-    if ((rc = make_dev(e->d_xs_b[0], B * e->L)) || (rc = make_dev(e->d_xs_b[1], B * e->L)) ||
-        (rc = make_dev(e->d_xlp_b[0], B * e->LX)) || (rc = make_dev(e->d_xlp_b[1], B * e->LX)) ||
-        (rc = make_dev(e->d_ratio_b[1], T * B)) || (rc = make_dev(e->d_ticks_b[1], 2 * B)) || (rc = make_dev(e->d_X, F * fvad::kFreq * 2)) ||
-        (rc = make_dev(e->d_P, F * fvad::kFreq * 2)) || (rc = make_dev(e->d_Ex, F * fvad::kBands)) ||
-        (rc = make_dev(e->d_Ep, F * fvad::kBands)) || (rc = make_dev(e->d_Exp, F * fvad::kBands)) ||
-        (rc = make_dev(e->d_Lyf, F * fvad::kBands)) || (rc = make_dev(e->d_f34, F * 8)) ||
-        (rc = make_dev(e->d_rec, F * fvad::kPitchRecord)) || (rc = make_dev(e->d_work, (size_t)fvad::kWorkCounters)) ||
-        (rc = make_dev(e->d_ptile, (B + fvad::ptile::kTile - 1) / fvad::ptile::kTile * e->V * fvad::ptile::kTile *
-                                      fvad::ptile::kRows)) || (rc = make_dev(e->d_vadf, F)) ||
-        (rc = make_dev(e->d_ys, F * fvad::kWin)) || (rc = make_dev(e->d_sil, F)) || (rc = make_dev(e->d_pitch, F)) ||
-        (rc = make_dev(e->d_wtick, B * e->wmax)) || (rc = make_dev(e->d_wstart, B * e->wmax)) ||
-        (rc = make_dev(e->d_gr, F * fvad::kBands)) || (rc = make_dev(e->d_gs, F * fvad::kBands)))
-      return bail(rc);
-    e->d_xs = e->d_xs_b[0].get();
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c.device) != hipSuccess) return bail(fail(FVAD_EDEVICE, "device query failed"));
-    // CUs; persistent grids are sized per kernel
-    e->grid_frames = prop.multiProcessorCount;
-    // k_fftb's device scratch when a transform does not fit in LDS: a slice per
-    // workgroup, at most two per CU and 1 GiB
-    int lo = 0, hi = 0, band_lo[fvad::kMaxBandCfg], band_hi[fvad::kMaxBandCfg];
-    fill_bands(c, band_lo, band_hi, &lo, &hi);
-    e->fb_work_stride = fvad::fftb_work_stride(c.fft_size, lo, hi, fvad::fftb_generic(c.fft_size / 2));
-    if (e->fb_work_stride > 0) {
-      const long long per = e->fb_work_stride * (long long)sizeof(float2);
-      const long long units = (long long)B * e->wmax;
-      e->fb_work_blocks = (int)std::max<long long>(
-          1, std::min<long long>({units, 2LL * e->grid_frames, (1LL << 30) / per}));
-      if ((rc = make_dev(e->d_fbwork, (size_t)e->fb_work_blocks * e->fb_work_stride))) return bail(rc);
-    }
-  }
-  if (c.want_spectrum) {
-    e->n_spec = c.spec_hi - c.spec_lo + 1;
-    if ((rc = make_dev(e->d_spec, T * B * e->wpt * C * (size_t)e->n_spec))) return bail(rc);
-  }
-  if (resample && (rc = resample_make(e, rd, c.input_rate_max))) return bail(rc);
-  if (resample_out && (rc = resample_out_make(e, od, c.denoised_rate_max))) return bail(rc);
-  if ((rc = fvad_engine_reset(e))) return bail(rc);
-  *out = e;
-  return FVAD_OK;
-}
-
-extern "C" void fvad_engine_destroy(fvad_engine *e) {
-  if (!e) return;
-  (void)hipSetDevice(e->cfg.device);
-  if (e->cstream) (void)hipStreamSynchronize(e->cstream.get());
-  if (e->pstream) (void)hipStreamSynchronize(e->pstream);
-  e->vpend = false;  // the last push's machine would only update state that is freed
-  if (e->stream) (void)hipStreamSynchronize(e->stream.get());
-  if (e->side) (void)hipStreamSynchronize(e->side);
-  delete e;
-}
-
-// e runs its k_prep3 (which & FVAD_SHARE_PREP) and / or its VADMachine
-// kernels (which & FVAD_SHARE_SIDE) on other's streams from now on.  Both
-// engines idle (synchronised here); every dependency stays an event, so
-// sharing only adds order between the engines' side work.  An engine whose
-// prep stream is shared runs k_fftAw on its own stream (launch_staged), so
-// the main pipelines stay independent.
-extern "C" int fvad_engine_share_streams(fvad_engine *e, fvad_engine *other, int which) {
-  if (!e || !other || e == other || (which & ~(FVAD_SHARE_PREP | FVAD_SHARE_SIDE)) || !which)
-    return fail(FVAD_EINVAL, "invalid argument");
-  if (e->cfg.device != other->cfg.device) return fail(FVAD_EINVAL, "engines on different devices");
-  if ((which & FVAD_SHARE_PREP) && (!e->pstream || !other->pstream))
-    return fail(FVAD_EINVAL, "FVAD_SHARE_PREP needs two staged engines");
-  if ((which & FVAD_SHARE_SIDE) && (!e->side || !other->side))
-    return fail(FVAD_EINVAL, "FVAD_SHARE_SIDE needs device VADMachines attached to both engines");
-  int rc;
-  if ((rc = fvad_engine_sync(e)) || (rc = fvad_engine_sync(other))) return rc;
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  if (which & FVAD_SHARE_PREP) {
-    e->pstream_ref = other->pstream_ref;
-    e->pstream = other->pstream;
-  }
-  if (which & FVAD_SHARE_SIDE) {
-    e->side_ref = other->side_ref;
-    e->side = other->side;
-  }
-  return FVAD_OK;
 }
 
 namespace {
@@ -550,40 +153,41 @@ namespace {
 // (with their test hooks' current values)
 fvad::StagedArgs staged_fixed(const fvad_engine *e) {
   const fvad_engine_config &c = e->cfg;
+  const Staged &g = *e->sg;
   fvad::StagedArgs a{};
   a.n_streams = c.n_streams;
   a.n_channels = c.n_channels;
-  a.V = e->V;
-  a.L = e->L;
-  a.LX = e->LX;
+  a.V = g.V;
+  a.L = g.L;
+  a.LX = g.LX;
   a.state = e->d_state.get();
-  a.X = reinterpret_cast<float2 *>(e->d_X.get());
-  a.P = reinterpret_cast<float2 *>(e->d_P.get());
-  a.Ex = e->d_Ex.get();
-  a.Ep = e->d_Ep.get();
-  a.Exp = e->d_Exp.get();
-  a.Lyf = e->d_Lyf.get();
-  a.f34 = e->d_f34.get();
-  a.silence = e->d_sil.get();
-  a.rec = e->d_rec.get();
-  a.ptile = e->d_ptile.get();
-  a.work = e->d_work.get();
-  a.pitch = e->d_pitch.get();
-  a.vadf = e->d_vadf.get();
-  a.gr = e->d_gr.get();
-  a.gs = e->d_gs.get();
+  a.X = reinterpret_cast<float2 *>(g.d_X.get());
+  a.P = reinterpret_cast<float2 *>(g.d_P.get());
+  a.Ex = g.d_Ex.get();
+  a.Ep = g.d_Ep.get();
+  a.Exp = g.d_Exp.get();
+  a.Lyf = g.d_Lyf.get();
+  a.f34 = g.d_f34.get();
+  a.silence = g.d_sil.get();
+  a.rec = g.d_rec.get();
+  a.ptile = g.d_ptile.get();
+  a.work = g.d_work.get();
+  a.pitch = g.d_pitch.get();
+  a.vadf = g.d_vadf.get();
+  a.gr = g.d_gr.get();
+  a.gs = g.d_gs.get();
   a.rnn_img = e->d_rnn_img.get();
   a.gru16_frags = e->d_gru16.get();
   a.gru16_bias = e->d_gru16_bias.get();
   a.fuse16 = e->cfg.mode == FVAD_MODE_FP16_FUSED;
   a.fma = e->cfg.mode == FVAD_MODE_F32_FAST;
   for (int m = 0; m < fvad::rnnimg::kMats; m++) a.rnn_act[m] = e->rnn_act[m];
-  a.ys = e->d_ys.get();
+  a.ys = g.d_ys.get();
   a.ring = e->d_ring.get();
   a.ring_len = e->ring_len;
-  a.win_tick = e->d_wtick.get();
-  a.win_start = e->d_wstart.get();
-  a.wmax = e->wmax;
+  a.win_tick = g.d_wtick.get();
+  a.win_start = g.d_wstart.get();
+  a.wmax = g.wmax;
   a.wpt = e->wpt;
   if (e->d_fbtab) {  // fft_size > kMaxFftB: [tw | sup | hann | perm] (fvad_engine_create)
     const size_t n = c.fft_size;
@@ -598,9 +202,9 @@ fvad::StagedArgs staged_fixed(const fvad_engine *e) {
     a.fb_hann = reinterpret_cast<const float *>(pb + offsetof(fvad::Plan, hannb));
     a.fb_perm = reinterpret_cast<const int *>(pb + offsetof(fvad::Plan, permb));
   }
-  a.fb_work = e->d_fbwork.get();
-  a.fb_work_blocks = e->fb_work_blocks;
-  a.fb_work_stride = e->fb_work_stride;
+  a.fb_work = g.d_fbwork.get();
+  a.fb_work_blocks = g.fb_work_blocks;
+  a.fb_work_stride = g.fb_work_stride;
   a.plan = e->d_plan.get();
   a.model = e->d_model.get();
   a.n_bands = c.n_bands;
@@ -610,7 +214,7 @@ fvad::StagedArgs staged_fixed(const fvad_engine *e) {
   a.out_vad = e->d_vad.get();
   a.out_den = e->d_den.get();
   a.raw_s16 = e->raw_s16;
-  a.vadm = e->vadm;
+  a.vadm = e->vadm.args;
   a.stamps = e->d_stamps.get();
   a.spec = e->d_spec.get();
   a.spec_lo = c.spec_lo;
@@ -620,15 +224,16 @@ fvad::StagedArgs staged_fixed(const fvad_engine *e) {
 
 int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool timed) {
   const fvad_engine_config &c = e->cfg;
+  Staged &g = *e->sg;
   // the previous push's VADMachine (after that push's ev_buf_free)
-  if (e->vpend)
+  if (e->vadm.pend)
     if (const int rf = vadm_flush(e, false)) return rf;
   // push k uses buffer b = k & 1 of xs / ratio / ticks; its k_prep3 waits
   // (on pstream) until push k-2 released b, then runs beside push k-1
-  const int b = e->next_buf;
-  if (e->buf_busy[b]) HIP_TRY(wait_event(e->pstream, e->ev_buf_free[b].get()));
-  if (e->fft_a_rec) HIP_TRY(wait_event(e->pstream, e->ev_fft_a.get()));
-  e->d_xs = e->d_xs_b[b].get();
+  const int b = g.next_buf;
+  if (g.buf_busy[b]) HIP_TRY(wait_event(e->pstream, g.ev_buf_free[b].get()));
+  if (g.fft_a_rec) HIP_TRY(wait_event(e->pstream, g.ev_fft_a.get()));
+  g.d_xs = g.d_xs_b[b].get();
   e->d_ratio = e->d_ratio_b[b].get();
   e->d_ticks = e->d_ticks_b[b].get();
   use_win_out(e, b);
@@ -639,8 +244,8 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
   a.tail = use_tail ? e->d_ticks + c.n_streams : nullptr;  // [B..2B) of the ticks buffer
   a.pcm = e->d_pcm;
   a.pcm16 = e->pcm16_push ? reinterpret_cast<const int16_t *>(e->d_pcm) : nullptr;
-  a.xs = e->d_xs;
-  a.xlp = e->d_xlp_b[b].get();
+  a.xs = g.d_xs;
+  a.xlp = g.d_xlp_b[b].get();
   a.ratio = e->d_ratio;
   a.out_win_ratio = e->d_wratio;
   a.out_win_vad = e->d_wvad;
@@ -658,42 +263,42 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
     // reads it, before ev_prep_done (and the caller's ev_in_free) are recorded
     if (e->cap && e->cap->source == FVAD_CLIP_SOURCE_INPUT)
       if (const int rc = capture_append(e, a, b, timed)) return rc;
-    HIP_TRY(hipEventRecord(e->ev_prep_done[b].get(), e->pstream));
-    HIP_TRY(wait_event(e->stream.get(), e->ev_prep_done[b].get()));
+    HIP_TRY(hipEventRecord(g.ev_prep_done[b].get(), e->pstream));
+    HIP_TRY(wait_event(e->stream.get(), g.ev_prep_done[b].get()));
     // window output set b is free once push k-2's k_vadm_hbm has read it
-    if (e->vadm.n > 0) HIP_TRY(wait_event(e->stream.get(), e->ev_vadm_b[b].get()));
+    if (e->vadm.on()) HIP_TRY(wait_event(e->stream.get(), e->vadm.ev_set_free[b].get()));
     // k_fftAw runs on the prep stream only while this engine owns it: on a
     // shared one (FVAD_SHARE_PREP) it would queue behind the other engine's
     // waits and couple the two pipelines, so it stays on the engine stream
     const bool own_prep = e->pstream_ref.use_count() <= 1;
-    HIP_TRY(fvad::launch_staged(a, e->grid_frames, e->stream.get(), timed ? e->ev : nullptr, e->ev_fft_a.get(),
-                                own_prep ? e->pstream : nullptr, e->synth_rec ? e->synth_wait : nullptr,
-                                e->ev_synth.get()));
+    HIP_TRY(fvad::launch_staged(a, g.grid_frames, e->stream.get(), timed ? e->ev : nullptr, g.ev_fft_a.get(),
+                                own_prep ? e->pstream : nullptr, g.synth_rec ? g.synth_wait : nullptr,
+                                g.ev_synth.get()));
     // (launch_staged records the timing event in ev_synth's place when timed)
-    e->synth_wait = timed ? e->ev[fvad::kEvSynthEnd] : e->ev_synth.get();
-    e->synth_rec = true;
-    e->fft_a_rec = true;
+    g.synth_wait = timed ? e->ev[fvad::kEvSynthEnd] : g.ev_synth.get();
+    g.synth_rec = true;
+    g.fft_a_rec = true;
   } else {
     // no denoiser: raw input frames to the ring, windows, FFT B, all on the
     // engine stream after the input copy (queued on the prep stream)
-    HIP_TRY(hipEventRecord(e->ev_prep_done[b].get(), e->pstream));
-    HIP_TRY(wait_event(e->stream.get(), e->ev_prep_done[b].get()));
-    if (e->vadm.n > 0) HIP_TRY(wait_event(e->stream.get(), e->ev_vadm_b[b].get()));
-    HIP_TRY(fvad::launch_nodenoise(a, e->grid_frames, e->stream.get()));
+    HIP_TRY(hipEventRecord(g.ev_prep_done[b].get(), e->pstream));
+    HIP_TRY(wait_event(e->stream.get(), g.ev_prep_done[b].get()));
+    if (e->vadm.on()) HIP_TRY(wait_event(e->stream.get(), e->vadm.ev_set_free[b].get()));
+    HIP_TRY(fvad::launch_nodenoise(a, g.grid_frames, e->stream.get()));
   }
-  if (e->vadm.n > 0) {
+  if (e->vadm.on()) {
     // the ticks copy of parity b may be overwritten once push k - 2's
-    // VADMachine has read it (ev_vadm_b[b], waited for above)
+    // VADMachine has read it (ev_set_free[b], waited for above)
     if (use_ticks)
-      HIP_TRY(hipMemcpyAsync(e->wout[b].vticks.get(), e->d_ticks, (size_t)c.n_streams * 4, hipMemcpyDeviceToDevice,
+      HIP_TRY(hipMemcpyAsync(e->vadm.vticks[b].get(), e->d_ticks, (size_t)c.n_streams * 4, hipMemcpyDeviceToDevice,
                              e->stream.get()));
     fvad::StagedArgs v = a;
-    v.ticks_valid = use_ticks ? e->wout[b].vticks.get() : nullptr;
-    e->vpend = true;
-    e->vpend_args = v;
-    e->vpend_b = b;
-    e->vpend_timed = timed;
-    e->vpend_push = e->push_count;
+    v.ticks_valid = use_ticks ? e->vadm.vticks[b].get() : nullptr;
+    e->vadm.pend = true;
+    e->vadm.pend_args = v;
+    e->vadm.pend_b = b;
+    e->vadm.pend_timed = timed;
+    e->vadm.pend_push = e->push_count;
   }
   e->push_count++;
   if (e->log_n < e->log_cap) {  // test hook: this push's outputs into the log (read after a sync)
@@ -717,9 +322,9 @@ int run_staged(fvad_engine *e, int n_ticks, bool use_ticks, bool use_tail, bool 
   if (e->cap && e->cap->source == FVAD_CLIP_SOURCE_DENOISED)
     if (const int rc = capture_append_den(e, a, b, timed)) return rc;
   // every reader of buffer b (incl. the copy of ticks for k_vadm_hbm) is queued
-  HIP_TRY(hipEventRecord(e->ev_buf_free[b].get(), e->stream.get()));
-  e->buf_busy[b] = true;
-  e->next_buf = b ^ 1;
+  HIP_TRY(hipEventRecord(g.ev_buf_free[b].get(), e->stream.get()));
+  g.buf_busy[b] = true;
+  g.next_buf = b ^ 1;
   return FVAD_OK;
 }
 
@@ -731,7 +336,7 @@ int fvad::eng::launch(fvad_engine *e, int n_ticks, bool use_ticks, bool timed, b
     // the push's first kernel: the raw input to 48 kHz, on the stream that
     // owns the tails, behind the copies of the input and of ticks_valid
     const int *tv = !use_ticks ? nullptr
-                    : e->cfg.mode != FVAD_MODE_FUSED ? e->d_ticks_b[e->next_buf].get() : e->d_ticks;
+                    : e->cfg.mode != FVAD_MODE_FUSED ? e->d_ticks_b[e->sg->next_buf].get() : e->d_ticks;
     if (const int rr = resample_push(e, n_ticks, tv)) return rr;
   }
   const int rc = e->cfg.mode == FVAD_MODE_FUSED ? run_fused(e, n_ticks, use_ticks, timed)
@@ -817,8 +422,8 @@ extern "C" int fvad_engine_push_ex(fvad_engine *e, const float *pcm, int n_ticks
   hipStream_t cs = e->stream.get();
   int *dticks = e->d_ticks;
   if (e->cfg.mode != FVAD_MODE_FUSED) {
-    const int b = e->next_buf;
-    if (e->buf_busy[b]) HIP_TRY(hipStreamWaitEvent(e->pstream, e->ev_buf_free[b].get(), 0));
+    const int b = e->sg->next_buf;
+    if (e->sg->buf_busy[b]) HIP_TRY(hipStreamWaitEvent(e->pstream, e->sg->ev_buf_free[b].get(), 0));
     cs = e->pstream;
     dticks = e->d_ticks_b[b].get();
   }
@@ -960,8 +565,7 @@ extern "C" int fvad_engine_kernel_times(fvad_engine *e, double *ms_avg, int *n_r
   // the pipeline kernels, not part of [0]; k_vadm_hbm (steady state) and
   // k_vadm_par (the push flushed at a sync point) separately
   for (int k = 0; k < 2; k++)
-    if (e->vadm.n > 0 && e->n_kernels + 1 + k < FVAD_MAX_TIMES)
-      ms_avg[e->n_kernels + 1 + k] = e->vadm_timed[k] ? e->vadm_ms_sum[k] / e->vadm_timed[k] : 0.0;
+    if (e->vadm.on() && e->n_kernels + 1 + k < FVAD_MAX_TIMES) e->vadm.tm.read(k, &ms_avg[e->n_kernels + 1 + k], nullptr);
   if (n_runs) *n_runs = e->n_timed;
   return FVAD_OK;
 }
@@ -971,19 +575,11 @@ extern "C" int fvad_engine_clear_times(fvad_engine *e) {
   int rc = fvad_engine_sync(e);
   if (rc) return rc;
   for (double &v : e->ms_sum) v = 0;
-  for (int k = 0; k < 2; k++) {
-    e->vadm_ms_sum[k] = 0;
-    e->vadm_timed[k] = 0;
-  }
-  e->et_ms_sum = 0;
-  e->et_timed = 0;
+  e->vadm.tm.clear();
+  e->feed.tm.clear();
   if (e->rs) e->rs->tm.clear();
   if (e->ro) e->ro->tm.clear();
-  if (e->cap)
-    for (int k = 0; k < 2; k++) {
-      e->cap->ms_sum[k] = 0;
-      e->cap->n_timed[k] = 0;
-    }
+  if (e->cap) e->cap->tm.clear();
   e->n_timed = 0;
   e->res_count = 0;
   return FVAD_OK;
@@ -1021,8 +617,8 @@ extern "C" int fvad_engine_windows_per_tick(const fvad_engine *e) { return e ? e
 
 extern "C" const char *fvad_engine_kernel_name(const fvad_engine *e, int i) {
   // (per-stream configs run the _ps kernels, reported in the same two slots)
-  if (e && i == e->n_kernels && e->vadm.n > 0) return e->vadm_ps ? "k_vadm_hbm_ps" : "k_vadm_hbm";
-  if (e && i == e->n_kernels + 1 && e->vadm.n > 0) return e->vadm_ps ? "k_vadm_par_ps" : "k_vadm_par";
+  if (e && i == e->n_kernels && e->vadm.on()) return e->vadm.ps ? "k_vadm_hbm_ps" : "k_vadm_hbm";
+  if (e && i == e->n_kernels + 1 && e->vadm.on()) return e->vadm.ps ? "k_vadm_par_ps" : "k_vadm_par";
   if (!e || i < 0 || i >= e->n_kernels) return nullptr;
   if (e->cfg.mode == FVAD_MODE_FUSED) return i == 0 ? "k_prep" : "k_frame";
   return e->kernels.k[i].name;

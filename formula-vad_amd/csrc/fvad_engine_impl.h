@@ -1,7 +1,10 @@
 // The batched engine's private parts: struct fvad_engine and the functions its
-// translation units share (fvad_engine.cpp, fvad_engine_ingest.cpp,
-// fvad_engine_rates.cpp, fvad_engine_vadm.cpp, fvad_engine_lifecycle.cpp,
-// fvad_capture_host.cpp).
+// translation units share (fvad_engine.cpp, fvad_engine_create.cpp,
+// fvad_engine_ingest.cpp, fvad_engine_rates.cpp, fvad_engine_vadm.cpp,
+// fvad_engine_events.cpp, fvad_engine_lifecycle.cpp, fvad_capture_host.cpp).
+// The engine's subsystems each have one owner, a struct of namespace eng:
+// Capture, Resample / ResampleOut with their RatePlan, Vadm, EventFeed and
+// Staged; their timing samples are Timers.
 // Host code only: not installed, and no .hip file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,6 +79,54 @@ struct EventTimer {
   }
 };
 
+// N EventTimers and the samples read from them, by kind: each of the K kinds
+// has its own sum and count, and end() names the kind of the sample its slot
+// brackets.  What becomes of a sample that is unread when its slot comes up
+// again is the caller's: begin alone drops it, collect(slot) ahead of begin
+// keeps it if it is complete.
+template <int N, int K = 1>
+struct Timers {
+  EventTimer tm[N];
+  int kind[N] = {};
+  double ms_sum[K] = {};
+  int n_timed[K] = {};
+  // the events of n slots from slot `first` on (a slot that has them keeps them)
+  int create(int first = 0, int n = N) {
+    for (int i = first; i < first + n; i++)
+      if (const int rc = tm[i].create()) return rc;
+    return FVAD_OK;
+  }
+  int begin(int slot, hipStream_t s) { return tm[slot].begin(s); }
+  int end(int slot, hipStream_t s, int k = 0) {
+    kind[slot] = k;
+    return tm[slot].end(s);
+  }
+  // never waits: a sample whose end event has not completed stays pending
+  int collect(int slot) { return tm[slot].collect(ms_sum[kind[slot]], n_timed[kind[slot]]); }
+  int collect() {
+    for (int i = 0; i < N; i++)
+      if (const int rc = collect(i)) return rc;
+    return FVAD_OK;
+  }
+  // the round-robin use: the slot after `slot` keeps what it held if that is
+  // complete, then begins
+  int begin_next(int &slot, hipStream_t s) {
+    slot = (slot + 1) % N;
+    if (const int rc = collect(slot)) return rc;
+    return begin(slot, s);
+  }
+  void drop() {
+    for (EventTimer &t : tm) t.pending = false;
+  }
+  void read(int k, double *ms_avg, int *n_runs) const {
+    *ms_avg = n_timed[k] ? ms_sum[k] / n_timed[k] : 0.0;
+    if (n_runs) *n_runs = n_timed[k];
+  }
+  void clear() {
+    for (int k = 0; k < K; k++) ms_sum[k] = 0, n_timed[k] = 0;
+  }
+};
+
 // FNV-1a (64 bit), the hash of a stream blob's compatibility fields
 constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull;
 inline uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
@@ -125,46 +176,10 @@ struct Capture {
   // that pass read)
   event_ptr ev_pass[2];
   uint64_t desc_read = 0, desc_end = 0, pool_read = 0, pool_end = 0, lost = 0;
-  EventTimer at[2], pt[2];  // k_hist_append (by push parity) and the pass (by vadm_slot)
-  double ms_sum[2] = {};
-  int n_timed[2] = {};
-};
-
-// EventTimers round the launches of one kind, taken in turn and read without
-// waiting (a sample still running when its timer comes round again is
-// dropped): the two resamplers' launches of a push.
-struct TimerRing {
-  static constexpr int kMax = 4;
-  EventTimer tm[kMax];
-  int n = 0, slot = 0;
-  double ms_sum = 0;
-  int n_timed = 0;
-  int create(int slots) {
-    for (n = 0; n < slots; n++)
-      if (const int rc = tm[n].create()) return rc;
-    return FVAD_OK;
-  }
-  // the next timer: what it held is collected, then it begins (n > 0: the
-  // resamplers' make functions create the ring, and an engine whose create
-  // failed is destroyed before a push)
-  int begin(hipStream_t s) {
-    EventTimer &t = tm[slot = (slot + 1) % n];
-    if (const int rc = t.collect(ms_sum, n_timed)) return rc;
-    return t.begin(s);
-  }
-  int end(hipStream_t s) { return tm[slot].end(s); }
-  // (after a sync: every pending sample is complete)
-  int read(double *ms_avg, int *n_runs) {
-    for (int i = 0; i < n; i++)
-      if (const int rc = tm[i].collect(ms_sum, n_timed)) return rc;
-    *ms_avg = n_timed ? ms_sum / n_timed : 0.0;
-    if (n_runs) *n_runs = n_timed;
-    return FVAD_OK;
-  }
-  void clear() {
-    ms_sum = 0;
-    n_timed = 0;
-  }
+  // slots [0, 2): k_hist_append by push parity, kind kAppend; kPassSlot +
+  // the machines' timer slot: the pass, kind kPass
+  enum { kAppend = 0, kPass = 1, kPassSlot = 2 };
+  Timers<4, 2> tm;
 };
 
 // Per-stream rates of either resampler (input_rate = FVAD_INPUT_RATE_PER_STREAM,
@@ -239,7 +254,8 @@ struct Resample {
   // which is behind k_resample)
   dev_ptr<float> raw[2];  // max_ticks * B * C * (rate or rate_max) / 100 words each
   bool in16 = false;      // the push being launched holds int16 samples
-  TimerRing tm;           // the resample launches of a push: two timers
+  Timers<2> tm;           // the resample launches of a push, taken in turn (tm_slot)
+  int tm_slot = 0;
   RatePlan plan;          // per-stream rates; tables by raw buffer parity
 };
 
@@ -256,11 +272,147 @@ struct ResampleOut {
   // d_den_out: [tick][s][c][n], max_ticks ticks; per-stream rates: packed
   // [tick][s][c][rate(s) / 100], max_ticks * B * C * rate_max / 100 words
   dev_ptr<float> out;
-  TimerRing tm;          // the launches of a push: four timers (three pushes in flight and their copies)
+  Timers<4> tm;          // the launches of a push, taken in turn (tm_slot): three pushes in flight and their copies
+  int tm_slot = 0;
   RatePlan plan;         // per-stream rates; one copy of the tables
   // a tick's length of the push launched last: what fetch and the D2H copies
   // of that push move (the layout may have changed since)
   long long pushed_len = 0;
+};
+// One set of a push's window outputs
+struct WinOut {
+  dev_ptr<int> flag;
+  dev_ptr<float> ratio, vad, band;
+};
+
+// The device VADMachines (fvad_engine_attach_vadm / attach_vadm_ex; DESIGN.md
+// section 7): everything they own, made by the attaching call in a local Vadm
+// that is move-assigned into the engine once nothing can fail any more.  Held
+// by value: args goes by value into every argument block, and the test hooks
+// (par_serial_every, defer_max, always_par) may be set before the attach, which
+// carries them over.  fvad_engine_vadm.cpp.
+struct Vadm {
+  VadmArgs args{};  // its pointers are views of the owners below (ev_stage / ev_count: the feed's)
+  dev_ptr<VadmState> st;
+  dev_ptr<float> buf;
+  dev_ptr<VadmSeg> seg;
+  dev_ptr<unsigned long long> count;  // FVAD_DEBUG_VADM_COUNT
+  // Window outputs of push k in set k & 1: set 0 is the engine's own, set 1
+  // exists with the machines (without them every push writes set 0).
+  // k_vadm_hbm of push k reads set k & 1 in place, push k + 2 rewrites it
+  // after that pass (ev_set_free).  vticks: the pass's copy of the push's ticks.
+  WinOut set1;
+  dev_ptr<int32_t> vticks[2];
+  event_ptr ev_done, ev_set_free[2];  // behind the pass queued last; behind the last pass of each parity
+  // The VADMachine of push k is enqueued when the next push is launched, as
+  // k_vadm_hbm (32 waves, overlapping that push quietly: the 512-wave burst of
+  // k_vadm_par beside the next push's k_fftAw cost more than it saved,
+  // measured), or at a sync point with nothing else queued as k_vadm_par
+  // (0.25 ms instead of 1.45: the drain of a job's last push).
+  bool pend = false, pend_timed = false;
+  int pend_b = 0;
+  StagedArgs pend_args{};
+  uint64_t pend_push = 0;  // the pending pass's push (fvad_engine::push_count)
+  // a non-final k_vadm_hbm was queued last (its machines may owe their
+  // long-term fold): a sync point with no push pending resolves it with a
+  // resolve-only pass (owed_args: that launch's argument block)
+  bool owed = false;
+  StagedArgs owed_args{};
+  // VADMachine timing never blocks the host (it would serialise the overlap):
+  // two timers alternate (slot) and are read once complete.  By kernel: kind 0
+  // k_vadm_hbm (steady state), kind 1 k_vadm_par (a push flushed at a sync point)
+  Timers<2, 2> tm;
+  int slot = 0;
+  bool always_par = false;  // test hook FVAD_DEBUG_VADM_ALWAYS_PAR
+  bool lt_full = false;     // test hook FVAD_DEBUG_VADM_LT_FULL
+  std::vector<fvad_vadm_config> cfgs;  // the attached machines' configs (hashed into a stream blob's header)
+  std::vector<VadmState> init;         // [m][stream] initial states
+  size_t buf_len = 0;
+  // Per-stream configs (fvad_engine_attach_vadm_ex; DESIGN.md section 7): the
+  // device table args.tab [m][stream] and its host mirror -- the rows, the
+  // configs they came from, and init above, which then holds each stream's own
+  // fresh machine.  args.c[m] carries the room's lengths (the buffers'
+  // layout).  nopar: rows without an initial average; while there is one, sync
+  // points run k_vadm_hbm_ps (launch_vadm).
+  bool ps = false;
+  dev_ptr<VadmRow> tab;
+  std::vector<VadmRow> rows;
+  std::vector<fvad_vadm_config> stream_cfgs;
+  size_t nopar = 0;
+
+  bool on() const { return args.n > 0; }
+};
+
+// Speech event feed (fvad_engine_enable_events):
+// everything it owns, made by the enabling call in a local EventFeed and
+// move-assigned like Vadm (chunk may be set before).  The machine kernels stage
+// events per lane in HBM (stage), k_vadm_events packs them behind each pass
+// into a ring in pinned host memory and writes the pass's header slot there;
+// flight holds, oldest first, the passes whose `done` event (recorded behind
+// k_vadm_events) has not been seen complete yet.  poll_events reads the ring
+// only up to the end cursor of the last retired pass: the host never looks at
+// ring or header bytes of a pass before its event has completed (an event's
+// completion releases the kernel's stores to the system, whichever coherence
+// the allocation has).  fvad_engine_events.cpp.
+constexpr int kEvHeaders = 64;  // header slots: passes in flight at most (an older one is waited for)
+struct EventFeed {
+  struct Pass {
+    uint64_t pass, push;
+    event_ptr done;
+  };
+  dev_ptr<VadmEvRec> stage;            // Vadm::args.ev_stage
+  dev_ptr<unsigned> count;             // Vadm::args.ev_count
+  dev_ptr<unsigned long long> cursor;  // device: [0] write cursor, [1] lost
+  pinned_ptr<fvad_event> ring;         // written by the device through dv_ring
+  VadmEvent *dv_ring = nullptr;
+  pinned_ptr<VadmEventHeader> hdr;  // [kEvHeaders], slot pass % kEvHeaders
+  VadmEventHeader *dv_hdr = nullptr;
+  size_t ring_cap = 0;
+  uint64_t read = 0, end = 0, lost = 0;  // host read cursor; ring valid up to end; lost so far
+  uint64_t pass_next = 0;
+  uint64_t pushes_done = 0;  // pushes up to here have every event in the ring's valid part
+  std::deque<Pass> flight;
+  std::vector<event_ptr> pool;  // retired passes' events, re-used
+  Timers<2> tm;                 // k_vadm_events' samples, by the machines' timer slot
+  int chunk = 0;                // test hook FVAD_DEBUG_EVENTS_CHUNK
+
+  bool on() const { return ring_cap > 0; }
+};
+
+// The staged pipeline (every mode but FVAD_MODE_FUSED): its intermediates,
+// the double-buffered arrays and the events that order a push's parts, made by
+// staged_make (fvad_engine_create.cpp); a fused engine has none of it.
+struct Staged {
+  int V = 0, L = 0, LX = 0, wmax = 0, grid_frames = 0;
+  dev_ptr<float> d_X, d_P, d_Ex, d_Ep, d_Exp, d_Lyf, d_f34, d_rec, d_ptile, d_vadf, d_ys, d_gr, d_gs;
+  dev_ptr<int> d_sil, d_pitch, d_wtick;
+  dev_ptr<long long> d_wstart;
+  dev_ptr<unsigned> d_work;  // persistent-kernel group counters
+  // k_fftb's scratch (FFT B above kMaxFftB)
+  dev_ptr<float2> d_fbwork;
+  int fb_work_blocks = 0;
+  long long fb_work_stride = 0;
+  // xs / xlp / ratio / ticks are double-buffered: push k uses buffer k & 1,
+  // reused once the push that used it last has finished (ev_buf_free[b]).
+  // (ratio and ticks: fvad_engine::d_ratio_b / d_ticks_b, whose buffer 0 a
+  // fused engine has too.)  d_xs: the buffer of the latest push (a view)
+  dev_ptr<float> d_xs_b[2], d_xlp_b[2];
+  float *d_xs = nullptr;
+  event_ptr ev_prep_done[2], ev_buf_free[2];
+  bool buf_busy[2] = {false, false};
+  int next_buf = 0;
+  // the last push's k_fftAw done: push k's k_prep3 starts once push k-1's
+  // k_fftAw has finished, so it runs beside k_plpc / k_pcorr instead (measured:
+  // k_fftAw 0.64 -> 0.57, k_plpc 0.48 -> 0.40, k_pcorr 1.18 -> 1.24 ms, push
+  // 5.00 -> 4.90 ms; started after k_plpc it overruns into k_rnn3: 5.93 ms)
+  event_ptr ev_fft_a;
+  bool fft_a_rec = false;
+  // push k's k_fftAw runs on pstream (after its k_prep3) once push k-1's
+  // k_synthw, the last reader of what it writes, is done (ev_synth): beside
+  // push k-1's k_olafb instead of after it (push 4.87 -> 4.78 ms)
+  event_ptr ev_synth;
+  bool synth_rec = false;
+  hipEvent_t synth_wait = nullptr;  // the last push's k_synthw-end event: ev_synth, or ev[kEvSynthEnd] in a timed push (a view)
 };
 }  // namespace eng
 }  // namespace fvad
@@ -289,139 +441,38 @@ struct fvad_engine {
   fvad::DevModel dmodel{};
   fvad::dev_ptr<fvad::DevModel> d_model;
   fvad::dev_ptr<float> d_state, d_ring, d_xbuf, d_vad, d_den;
-  // staged-mode intermediates
-  fvad::dev_ptr<float> d_X, d_P, d_Ex, d_Ep, d_Exp, d_Lyf, d_f34, d_rec, d_ptile, d_vadf, d_ys, d_gr, d_gs;
-  fvad::dev_ptr<int> d_sil, d_pitch, d_wtick;
-  fvad::dev_ptr<long long> d_wstart;
   fvad::dev_ptr<int8_t> d_rnn_img;
   fvad::dev_ptr<uint16_t> d_gru16;  // FVAD_MODE_FP16: MFMA weight fragments (f16 bits)
   fvad::dev_ptr<float> d_gru16_bias;
-  // xs / xlp / ratio / ticks are double-buffered: push k uses buffer k & 1,
-  // reused once the push that used it last has finished (ev_buf_free[b]).
-  // d_xs, d_ratio, d_ticks: the buffer of the latest push (views)
-  fvad::dev_ptr<float> d_xs_b[2], d_ratio_b[2], d_xlp_b[2];
+  // ratio / ticks of a push: buffer 0, and on a staged engine buffer 1 for
+  // the pushes of odd parity (eng::Staged).  d_ratio, d_ticks: the buffer of
+  // the latest push (views)
+  fvad::dev_ptr<float> d_ratio_b[2];
   fvad::dev_ptr<int> d_ticks_b[2];
-  float *d_xs = nullptr, *d_ratio = nullptr;
+  float *d_ratio = nullptr;
   int *d_ticks = nullptr;
-  fvad::event_ptr ev_prep_done[2], ev_buf_free[2];
-  bool buf_busy[2] = {false, false};
-  int next_buf = 0;
-  // the last push's k_fftAw done: push k's k_prep3 starts once push k-1's
-  // k_fftAw has finished, so it runs beside k_plpc / k_pcorr instead (measured:
-  // k_fftAw 0.64 -> 0.57, k_plpc 0.48 -> 0.40, k_pcorr 1.18 -> 1.24 ms, push
-  // 5.00 -> 4.90 ms; started after k_plpc it overruns into k_rnn3: 5.93 ms)
-  fvad::event_ptr ev_fft_a;
-  bool fft_a_rec = false;
-  // push k's k_fftAw runs on pstream (after its k_prep3) once push k-1's
-  // k_synthw, the last reader of what it writes, is done (ev_synth): beside
-  // push k-1's k_olafb instead of after it (push 4.87 -> 4.78 ms)
-  fvad::event_ptr ev_synth;
-  bool synth_rec = false;
-  hipEvent_t synth_wait = nullptr;  // the last push's k_synthw-end event: ev_synth, or ev[kEvSynthEnd] in a timed push (a view)
-  // Window outputs of push k in set k & 1; set 1 exists once VADMachines are
-  // attached (without them every push writes set 0): k_vadm_hbm of push k
-  // reads set k & 1 in place, push k + 2 rewrites it after that pass
-  // (ev_vadm_b).  vticks (with machines): the pass's copy of the push's ticks.
-  // d_wflag / d_wratio / d_wvad / d_band: the latest push's set (views).
-  struct WinOut {
-    fvad::dev_ptr<int> flag;
-    fvad::dev_ptr<float> ratio, vad, band;
-    fvad::dev_ptr<int32_t> vticks;
-  } wout[2];
+  // the staged pipeline: null on a fused engine
+  std::unique_ptr<fvad::eng::Staged> sg;
+  // Window-output set 0 (set 1: eng::Vadm).  d_wflag / d_wratio / d_wvad /
+  // d_band: the latest push's set (views).
+  fvad::eng::WinOut wout0;
   int *d_wflag = nullptr;
   float *d_wratio = nullptr, *d_wvad = nullptr, *d_band = nullptr;
-  // device VADMachines (fvad_engine_attach_vadm); vadm's pointers are views of
-  // the owners below
-  fvad::VadmArgs vadm{};
-  fvad::dev_ptr<fvad::VadmState> vadm_st;
-  fvad::dev_ptr<float> vadm_buf;
-  fvad::dev_ptr<fvad::VadmSeg> vadm_seg;
-  fvad::dev_ptr<unsigned long long> vadm_count;  // FVAD_DEBUG_VADM_COUNT
-  fvad::event_ptr ev_vadm, ev_vadm_b[2];
-  // The VADMachine of push k is enqueued when the next push is launched, as
-  // k_vadm_hbm (32 waves, overlapping that push quietly: the 512-wave burst of
-  // k_vadm_par beside the next push's k_fftAw cost more than it saved,
-  // measured), or at a sync point with nothing else queued as k_vadm_par
-  // (0.25 ms instead of 1.45: the drain of a job's last push).
-  bool vpend = false, vpend_timed = false;
-  int vpend_b = 0;
-  fvad::StagedArgs vpend_args{};
-  // a non-final k_vadm_hbm was queued last (its machines may owe their
-  // long-term fold): a sync point with no push pending resolves it with a
-  // resolve-only pass (vowed_args: that launch's argument block)
-  bool vowed = false;
-  fvad::StagedArgs vowed_args{};
-  // VADMachine timing never blocks the host (it would serialise the overlap):
-  // two timers alternate (vadm_slot) and are read once complete.  By kernel:
-  // [0] k_vadm_hbm (steady state), [1] k_vadm_par (a push flushed at a sync
-  // point); vadm_kind[slot]: the kernel a pending sample brackets
-  fvad::eng::EventTimer vt[2];
-  double vadm_ms_sum[2] = {};
-  int vadm_timed[2] = {};
-  int vadm_kind[2] = {};
-  int vadm_slot = 0;
-  bool dbg_always_par = false;  // test hook FVAD_DEBUG_VADM_ALWAYS_PAR
-  bool dbg_lt_full = false;     // test hook FVAD_DEBUG_VADM_LT_FULL
-  // Speech event feed (fvad_engine_enable_events).  The
-  // machine kernels stage events per lane in HBM (ev_stage), k_vadm_events
-  // packs them behind each pass into a ring in pinned host memory and writes
-  // the pass's header slot there; ev_flight holds, oldest first, the passes
-  // whose `done` event (recorded behind k_vadm_events) has not been seen
-  // complete yet.  poll_events reads the ring only up to the end cursor of the
-  // last retired pass: the host never looks at ring or header bytes of a pass
-  // before its event has completed (an event's completion releases the
-  // kernel's stores to the system, whichever coherence the allocation has).
-  struct EvPass {
-    uint64_t pass, push;
-    fvad::event_ptr done;
-  };
-  static constexpr int kEvHeaders = 64;  // header slots: passes in flight at most (an older one is waited for)
-  bool events_on = false;
-  fvad::dev_ptr<fvad::VadmEvRec> ev_stage;       // vadm.ev_stage
-  fvad::dev_ptr<unsigned> ev_count;              // vadm.ev_count
-  fvad::dev_ptr<unsigned long long> d_ev_cursor;  // device: [0] write cursor, [1] lost
-  fvad::pinned_ptr<fvad_event> h_ev_ring;         // written by the device through dv_ev_ring
-  fvad::VadmEvent *dv_ev_ring = nullptr;
-  fvad::pinned_ptr<fvad::VadmEventHeader> h_ev_hdr;  // [kEvHeaders], slot pass % kEvHeaders
-  fvad::VadmEventHeader *dv_ev_hdr = nullptr;
-  size_t ev_ring_cap = 0;
-  uint64_t ev_read = 0, ev_end = 0, ev_lost = 0;  // host read cursor; ring valid up to ev_end; lost so far
-  uint64_t ev_pass_next = 0;
-  uint64_t ev_pushes_done = 0;  // pushes up to here have every event in the ring's valid part
-  std::deque<EvPass> ev_flight;
-  std::vector<fvad::event_ptr> ev_pool;  // retired passes' events, re-used
-  uint64_t push_count = 0, vpend_push = 0;  // pushes launched since create / reset; the pending pass's
-  int dbg_events_chunk = 0;  // test hook FVAD_DEBUG_EVENTS_CHUNK
-  fvad::eng::EventTimer et[2];  // k_vadm_events' samples, by vadm_slot
-  double et_ms_sum = 0;
-  int et_timed = 0;
+  // device VADMachines (fvad_engine_attach_vadm): vadm.on() once attached
+  fvad::eng::Vadm vadm;
+  // speech event feed (fvad_engine_enable_events): feed.on() once enabled
+  fvad::eng::EventFeed feed;
+  uint64_t push_count = 0;  // pushes launched since create / reset
   // test hook (fvad_engine_output_log): the per-tick outputs of the next
   // log_cap pushes, copied on the engine stream as each push ends
   fvad::dev_ptr<float> d_log;
   int log_cap = 0, log_n = 0;
   size_t log_stride = 0;
   std::vector<int> log_ticks;
-  std::vector<fvad::VadmState> vadm_init;  // [m][stream] initial states
-  size_t vadm_buf_len = 0;
-  // Per-stream configs (fvad_engine_attach_vadm_ex; DESIGN.md section 7): the
-  // device table vadm.tab [m][stream] and its host mirror -- the rows, the
-  // configs they came from, and vadm_init above, which then holds each
-  // stream's own fresh machine.  vadm.c[m] carries the room's lengths (the
-  // buffers' layout).  vadm_nopar: rows without an initial average; while
-  // there is one, sync points run k_vadm_hbm_ps (launch_vadm).
-  bool vadm_ps = false;
-  fvad::dev_ptr<fvad::VadmRow> vadm_tab;
-  std::vector<fvad::VadmRow> vadm_rows;
-  std::vector<fvad_vadm_config> vadm_stream_cfgs;
-  size_t vadm_nopar = 0;
   int rnn_act[fvad::rnnimg::kMats] = {};
-  int V = 0, L = 0, LX = 0, wmax = 0, grid_frames = 0;
   int wpt = 1;  // window slots per (tick, stream): windows_per_tick(fft_size)
-  // FFT B above kMaxFftB: tables [tw | sup | hann | perm] and k_fftb's scratch
+  // FFT B above kMaxFftB: tables [tw | sup | hann | perm]
   fvad::dev_ptr<float> d_fbtab;
-  fvad::dev_ptr<float2> d_fbwork;
-  int fb_work_blocks = 0;
-  long long fb_work_stride = 0;
   // Window spectra (fvad_engine_config.want_spectrum; DESIGN.md section 7,
   // "Window spectra and band sweeps"): the last launched push's,
   // [max_ticks][streams][wpt][channels][n_spec]; null without the tap.
@@ -446,7 +497,6 @@ struct fvad_engine {
   int res_count = 0;  // run_resident calls since the last clear_times (event sampling)
   int raw_s16 = 0;    // rnnoise compat mode (s16-scaled I/O)
   fvad::dev_ptr<unsigned long long> d_stamps;  // diagnostic stamp buffer (FVAD_STAMPS builds)
-  fvad::dev_ptr<unsigned> d_work;              // staged: persistent-kernel group counters
   // Device inputs alternate by push (d_pcm: the current one, a view): the
   // input of push k+1 may be copied in while push k's k_prep3 still reads
   // its own.  ev_in_free[i]: buffer i's last reader (k_prep3 / k_prep) done.
@@ -484,19 +534,17 @@ struct fvad_engine {
   // itself (staged engines with the denoiser: no d_pcm16, no k_pcm16)
   bool pcm16_push = false;
   // per-stream lifecycle (fvad_engine_reset_streams / save_streams / restore_streams)
-  uint64_t model_hash = 0;                  // of the model's int8 arrays (a blob's compatibility check)
-  std::vector<fvad_vadm_config> vadm_cfgs;  // the attached machines' configs (hashed into a blob's header)
-  fvad::dev_ptr<float> d_blob;              // device staging of a save / restore, grown on demand
-  size_t blob_cap = 0;                      //   (bytes)
+  uint64_t model_hash = 0;      // of the model's int8 arrays (a blob's compatibility check)
+  fvad::dev_ptr<float> d_blob;  // device staging of a save / restore, grown on demand
+  size_t blob_cap = 0;          //   (bytes)
   // test hook FVAD_DEBUG_RESET_TIMES: timers round the launches of
-  // fvad_engine_reset_streams ([0] engine stream, [1] prep stream, [2] side
-  // stream), kRtSlots calls deep, read at fvad_engine_reset_times
+  // fvad_engine_reset_streams (kind and slot within a call: 0 engine stream,
+  // 1 prep stream, 2 side stream), kRtSlots calls deep (slot 3 * call + kind,
+  // their events made on first use), read at fvad_engine_reset_times
   static constexpr int kRtSlots = 64;
   bool dbg_reset_times = false;
-  fvad::eng::EventTimer rt[kRtSlots][3];
+  fvad::eng::Timers<3 * kRtSlots, 3> rt;
   int rt_next = 0;
-  double rt_ms[3] = {};
-  int rt_n[3] = {};
   // input resampling (input_rate set): null on an engine of 48 kHz input
   std::unique_ptr<fvad::eng::Resample> rs;
   // the denoised PCM at another rate (denoised_rate set): null otherwise
@@ -511,8 +559,10 @@ namespace eng {
 // fvad_engine.cpp
 int launch(fvad_engine *e, int n_ticks, bool use_ticks, bool timed, bool use_tail = false);
 int fetch(fvad_engine *e, int n_ticks, fvad_outputs *o);
-int make_win_out(const fvad_engine *e, fvad_engine::WinOut &w);
+void fill_bands(const fvad_engine_config &c, int *band_lo, int *band_hi, int *lo_all, int *hi_all);
 void use_win_out(fvad_engine *e, int b);
+// fvad_engine_create.cpp
+int make_win_out(const fvad_engine *e, WinOut &w);
 // fvad_engine_ingest.cpp: the device input buffers
 hipStream_t input_reader(const fvad_engine *e);
 int input_buffer(fvad_engine *e, hipStream_t cs);
@@ -553,9 +603,12 @@ int resample_reset_streams(fvad_engine *e, const IdList &ids);
 // fvad_engine_vadm.cpp
 int vadm_reset(fvad_engine *e);
 int vadm_flush(fvad_engine *e, bool fast = true);
+int collect_vadm_timing(fvad_engine *e);
+// fvad_engine_events.cpp: k_vadm_events behind the machine pass just queued on
+// the side stream, the feed as after enable, and the passes that have finished
+int enqueue_events(fvad_engine *e, const VadmArgs &v, uint64_t push, int slot, bool timed);
 int events_reset(fvad_engine *e);
 int events_retire(fvad_engine *e, bool wait_oldest);
-int collect_vadm_timing(fvad_engine *e);
 // fvad_capture_host.cpp
 int capture_append(fvad_engine *e, const fvad::StagedArgs &a, int b, bool timed);
 int capture_append_den(fvad_engine *e, const fvad::StagedArgs &a, int b, bool timed);

@@ -243,8 +243,8 @@ int submit_any(fvad_engine *e, const Sample *pcm, int n_ticks, const int32_t *ti
   if (use_ticks) {
     int *dticks = e->d_ticks;
     if (staged) {
-      const int b = e->next_buf;
-      if (e->buf_busy[b]) HIP_TRY(hipStreamWaitEvent(cs, e->ev_buf_free[b].get(), 0));
+      const int b = e->sg->next_buf;
+      if (e->sg->buf_busy[b]) HIP_TRY(hipStreamWaitEvent(cs, e->sg->ev_buf_free[b].get(), 0));
       dticks = e->d_ticks_b[b].get();
     }
     HIP_TRY(hipMemcpyAsync(dticks, sl.ticks.get(), (tt.empty() ? B : 2 * B) * sizeof(int32_t), hipMemcpyHostToDevice, cs));

@@ -30,8 +30,8 @@ uint64_t config_hash_of(const fvad_engine *e) {
     h = fnv_add(h, c.band_lo[b]);
     h = fnv_add(h, c.band_hi[b]);
   }
-  h = fnv_add(h, (int)e->vadm_cfgs.size());
-  for (const fvad_vadm_config &m : e->vadm_cfgs) {  // field by field: the struct has padding
+  h = fnv_add(h, (int)e->vadm.cfgs.size());
+  for (const fvad_vadm_config &m : e->vadm.cfgs) {  // field by field: the struct has padding
     for (float v : {m.speech_min_freq, m.speech_max_freq, m.long_term_speech_avg_sec}) h = fnv_add(h, v);
     h = fnv_add(h, (int)(m.has_initial_long_term_avg != 0));
     h = fnv_add(h, m.has_initial_long_term_avg ? m.initial_long_term_avg : 0.0);
@@ -50,7 +50,7 @@ uint64_t config_hash_of(const fvad_engine *e) {
 }
 
 fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
-  return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm, seg_cap,
+  return fvad::blob_layout(e->cfg.n_channels, e->cfg.fft_size, e->cfg.use_denoiser, e->vadm.args, seg_cap,
                            e->rs ? resample_tail_words(e, fvad::rs::Dir::kIn) : 0,
                            e->ro ? resample_tail_words(e, fvad::rs::Dir::kOut) : 0, e->rs && e->rs->plan.on(),
                            e->ro && e->ro->plan.on());
@@ -58,7 +58,7 @@ fvad::BlobLayout layout_of(const fvad_engine *e, int seg_cap) {
 
 fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   fvad_stream_blob_header h{};
-  const int cap = e->vadm.n > 0 ? e->vadm.seg_cap : 0;
+  const int cap = e->vadm.on() ? e->vadm.args.seg_cap : 0;
   h.magic = FVAD_STREAM_BLOB_MAGIC;
   h.version = FVAD_STREAM_BLOB_VERSION;
   h.header_bytes = FVAD_STREAM_BLOB_HEADER_BYTES;
@@ -69,7 +69,7 @@ fvad_stream_blob_header header_of(const fvad_engine *e, int count) {
   h.fft_size = (uint32_t)e->cfg.fft_size;
   h.use_denoiser = (uint32_t)(e->cfg.use_denoiser != 0);
   h.n_bands = (uint32_t)e->cfg.n_bands;
-  h.n_machines = (uint32_t)e->vadm.n;
+  h.n_machines = (uint32_t)e->vadm.args.n;
   h.seg_capacity = (uint32_t)cap;
   h.state_words = fvad::st::kWords;
   h.config_hash = config_hash_of(e);
@@ -111,7 +111,7 @@ fvad::XferArgs xfer_args(const fvad_engine *e, const fvad::BlobLayout &lay) {
   a.ring = e->d_ring.get();
   a.ring_len = e->ring_len;
   a.n_streams = e->cfg.n_streams;
-  a.vadm = e->vadm;
+  a.vadm = e->vadm.args;
   a.lay = lay;
   a.blob = e->d_blob.get();
   a.rs_tails = e->rs ? e->rs->tails.get() : nullptr;
@@ -129,8 +129,8 @@ int check_record(const fvad_engine *e, const fvad::BlobLayout &lay, const float 
     if (ist[st::kMemId] < 0 || ist[st::kMemId] >= fvad::kCeps)
       return fail(FVAD_EFORMAT, "stream record: cepstral memory index out of range");
   }
-  for (int m = 0; m < e->vadm.n; m++) {
-    const fvad::VadmConst &K = e->vadm.c[m];
+  for (int m = 0; m < e->vadm.args.n; m++) {
+    const fvad::VadmConst &K = e->vadm.args.c[m];
     fvad::VadmState S;
     std::memcpy(&S, rec + lay.o_mach[m], sizeof(S));
     const unsigned nl = (unsigned)K.n_lt, ns = (unsigned)K.n_st, nr = (unsigned)K.n_r;
@@ -166,7 +166,7 @@ int restored_rates(const RatePlan &p, const int32_t *index, int n, const char *b
 // blobs of engines with per-stream configs are a later change: a v1 record's
 // layout and config_hash assume one config per machine (include/fvad.h)
 int refuse_per_stream(const fvad_engine *e, const char *what) {
-  if (!e->vadm_ps) return FVAD_OK;
+  if (!e->vadm.ps) return FVAD_OK;
   return fail(FVAD_EINVAL, std::string(what) + " is not available on an engine attached with fvad_engine_attach_vadm_ex");
 }
 
@@ -194,22 +194,21 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
   if (!e) return fail(FVAD_EINVAL, "null engine");
   if (const int rc = check_stream_list(e, streams, n)) return rc;
   if (n == 0) return FVAD_OK;
-  if (e->vadm.n > 0 && e->dbg_lt_full)
+  if (e->vadm.on() && e->vadm.lt_full)
     return fail(FVAD_EINVAL, "fvad_engine_reset_streams is not available under FVAD_DEBUG_VADM_LT_FULL");
   HIP_TRY(hipSetDevice(e->cfg.device));
   const bool split = e->cfg.mode != FVAD_MODE_FUSED && e->cfg.use_denoiser;
   // the previous push's machine pass sees the old state: queued first
-  if (e->vadm.n > 0 && e->vpend)
+  if (e->vadm.on() && e->vadm.pend)
     if (const int rc = vadm_flush(e, false)) return rc;
   int rc;
   // test hook FVAD_DEBUG_RESET_TIMES: this call's three timers (made on first use)
-  fvad::eng::EventTimer *rt = e->dbg_reset_times ? e->rt[e->rt_next] : nullptr;
+  // (a begin drops the sample its slot held kRtSlots calls ago, if still unread)
+  const bool rt = e->dbg_reset_times;
+  const int r0 = 3 * e->rt_next;
   if (rt) {
     e->rt_next = (e->rt_next + 1) % fvad_engine::kRtSlots;
-    for (int k = 0; k < 3; k++) {
-      rt[k].pending = false;
-      if ((rc = rt[k].create())) return rc;
-    }
+    if ((rc = e->rt.create(r0, 3))) return rc;
   }
   fvad::ClearArgs ca{};
   ca.state = e->d_state.get();
@@ -217,13 +216,13 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
   ca.ring_len = e->ring_len;
   ca.n_channels = e->cfg.n_channels;
   fvad::VClearArgs va{};
-  if (e->vadm.n > 0) {
-    va.vadm = e->vadm;
+  if (e->vadm.on()) {
+    va.vadm = e->vadm.args;
     va.n_streams = e->cfg.n_streams;
-    for (int m = 0; m < e->vadm.n; m++) va.init[m] = e->vadm_init[(size_t)m * e->cfg.n_streams];
+    for (int m = 0; m < e->vadm.args.n; m++) va.init[m] = e->vadm.init[(size_t)m * e->cfg.n_streams];
   }
-  if (rt && ((rc = rt[0].begin(e->stream.get())) || (split && (rc = rt[1].begin(e->pstream))) ||
-             (e->vadm.n > 0 && (rc = rt[2].begin(e->side)))))
+  if (rt && ((rc = e->rt.begin(r0, e->stream.get())) || (split && (rc = e->rt.begin(r0 + 1, e->pstream))) ||
+             (e->vadm.on() && (rc = e->rt.begin(r0 + 2, e->side)))))
     return rc;
   for (int i0 = 0; i0 < n; i0 += fvad::kListMax) {
     ca.ids.n = std::min(fvad::kListMax, n - i0);
@@ -234,7 +233,7 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
       ca.mode = fvad::kClearPrep;
       HIP_TRY(fvad::launch_stream_clear(ca, e->pstream));
     }
-    if (e->vadm.n > 0) {
+    if (e->vadm.on()) {
       va.ids = ca.ids;
       HIP_TRY(fvad::launch_stream_vclear(va, e->side));
     }
@@ -243,8 +242,8 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
   // clip capture: the streams' positions restart behind the appends already
   // queued, their pending clips go behind the passes already queued
   if (e->cap && (rc = capture_set_streams(e, streams, nullptr, n))) return rc;
-  if (rt && ((rc = rt[0].end(e->stream.get())) || (split && (rc = rt[1].end(e->pstream))) ||
-             (e->vadm.n > 0 && (rc = rt[2].end(e->side)))))
+  if (rt && ((rc = e->rt.end(r0, e->stream.get(), 0)) || (split && (rc = e->rt.end(r0 + 1, e->pstream, 1))) ||
+             (e->vadm.on() && (rc = e->rt.end(r0 + 2, e->side, 2)))))
     return rc;
   return FVAD_OK;
 }
@@ -252,15 +251,9 @@ extern "C" int fvad_engine_reset_streams(fvad_engine *e, const int32_t *streams,
 extern "C" int fvad_engine_reset_times(fvad_engine *e, double *ms_avg, int *n_runs) {
   if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
   if (const int rc = fvad_engine_sync(e)) return rc;
-  for (auto &slot : e->rt)
-    for (int k = 0; k < 3; k++)
-      if (const int rc = slot[k].collect(e->rt_ms[k], e->rt_n[k])) return rc;
-  for (int k = 0; k < 3; k++) {
-    ms_avg[k] = e->rt_n[k] ? e->rt_ms[k] / e->rt_n[k] : 0.0;
-    if (n_runs) n_runs[k] = e->rt_n[k];
-    e->rt_ms[k] = 0;
-    e->rt_n[k] = 0;
-  }
+  if (const int rc = e->rt.collect()) return rc;
+  for (int k = 0; k < 3; k++) e->rt.read(k, &ms_avg[k], n_runs ? &n_runs[k] : nullptr);
+  e->rt.clear();  // (a read starts the next measurement)
   return FVAD_OK;
 }
 

@@ -158,7 +158,7 @@ int fvad::eng::resample_make(fvad_engine *e, const rs::Desc &d, int rate_max) {
   if ((rc = fvad::make_dev(r.tails, rows * resample_tail_words(e, rs::Dir::kIn))) || (rc = fvad::make_dev(r.raw[0], raw)) ||
       (rc = fvad::make_dev(r.raw[1], raw)))
     return rc;
-  return r.tm.create(2);
+  return r.tm.create();
 }
 
 // the resample launches of the push about to launch, timed without waiting
@@ -182,9 +182,9 @@ int fvad::eng::resample_push(fvad_engine *e, int n_ticks, const int *d_ticks) {
     if ((rc = r.plan.sync(ib, st))) return rc;
     r.plan.fill(p.ps, ib);
   }
-  if ((rc = r.tm.begin(st))) return rc;
+  if ((rc = r.tm.begin_next(r.tm_slot, st))) return rc;
   HIP_TRY(r.plan.on() ? fvad::launch_resample_ps(p, st) : fvad::launch_resample(p.r, st));
-  return r.tm.end(st);
+  return r.tm.end(r.tm_slot, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -216,7 +216,7 @@ int fvad::eng::resample_out_make(fvad_engine *e, const rs::Desc &d, int rate_max
   if ((rc = fvad::make_dev(r.tails, rows * resample_tail_words(e, rs::Dir::kOut))) ||
       (rc = fvad::make_dev(r.out, (size_t)c.max_ticks * rows * denoised_frame_max(e))))
     return rc;
-  return r.tm.create(4);
+  return r.tm.create();
 }
 
 // the launches of the push being launched, on the engine stream behind its
@@ -240,9 +240,9 @@ int fvad::eng::resample_out_push(fvad_engine *e, int n_ticks, const int *d_ticks
     r.plan.fill(p.ps, 0);
     r.pushed_len = r.plan.tick_len();
   }
-  if ((rc = r.tm.begin(st))) return rc;
+  if ((rc = r.tm.begin_next(r.tm_slot, st))) return rc;
   HIP_TRY(r.plan.on() ? fvad::launch_resample_out_ps(p, st) : fvad::launch_resample_out(p.r, st));
-  return r.tm.end(st);
+  return r.tm.end(r.tm_slot, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -328,11 +328,15 @@ int set_rates(fvad_engine *e, RatePlan *p, const int *streams, int n, const int 
   return FVAD_OK;
 }
 
-int times(fvad_engine *e, TimerRing *tm, double *ms_avg, int *n_runs, const char *none) {
+// (after a sync: every pending sample is complete)
+template <int N>
+int times(fvad_engine *e, Timers<N> *tm, double *ms_avg, int *n_runs, const char *none) {
   if (!e || !ms_avg) return fail(FVAD_EINVAL, "null argument");
   if (!tm) return fail(FVAD_EINVAL, none);
-  if (const int rc = fvad_engine_sync(e)) return rc;
-  return tm->read(ms_avg, n_runs);
+  int rc = fvad_engine_sync(e);
+  if (!rc) rc = tm->collect();
+  if (!rc) tm->read(0, ms_avg, n_runs);
+  return rc;
 }
 }  // namespace
 

@@ -21,6 +21,13 @@
 // fails in must report it, destroy must still release everything, and
 // attach_vadm / enable_events must succeed when simply called again.  The
 // sweep's scenario (run_sweep) does the same for a sweep.
+//
+// The scenario also pins two things the owners of the engine's subsystems must
+// keep.  Test hooks set before attach_vadm / enable_events reach the launches
+// after them: the launch stubs keep the last argument blocks they saw.  And
+// every *_times entry point reports the runs it has (printed for the run
+// without a failure; with every event query succeeding they are
+// deterministic) and reads 0 after fvad_engine_clear_times.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -128,6 +135,11 @@ hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { return hipMem
 // ---------------------------------------------------------------------------
 // stub kernel launches and the host helpers of the .hip files
 // ---------------------------------------------------------------------------
+namespace {
+fvad::VadmArgs g_last_vadm{};             // what launch_vadm saw last
+fvad::VadmEventArgs g_last_vadm_events{};  // what launch_vadm_events saw last
+}  // namespace
+
 namespace fvad {
 hipError_t launch_prep(const PrepArgs &, hipStream_t) { return hipSuccess; }
 hipError_t launch_frame(const FrameArgs &, hipStream_t) { return hipSuccess; }
@@ -138,13 +150,15 @@ hipError_t launch_staged(const StagedArgs &, int, hipStream_t, hipEvent_t *, hip
 }
 hipError_t launch_nodenoise(const StagedArgs &, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_pcm16(const int16_t *, float *, size_t, hipStream_t) { return hipSuccess; }
-hipError_t launch_vadm(const StagedArgs &, hipStream_t, bool fast, bool *ran_par) {
+hipError_t launch_vadm(const StagedArgs &a, hipStream_t, bool fast, bool *ran_par) {
+  g_last_vadm = a.vadm;
   if (ran_par) *ran_par = fast;
   return hipSuccess;
 }
 // the host reads the pass's header once the pass's event has completed
 hipError_t launch_vadm_events(const VadmEventArgs &a, hipStream_t) {
   *a.header = VadmEventHeader{a.pass, 0, 0, 0};
+  g_last_vadm_events = a;
   return hipSuccess;
 }
 // the sweep reads back every lane's state (left as uploaded: a fresh machine
@@ -192,6 +206,7 @@ static_assert(FVAD_INPUT_RATE_PER_STREAM == FVAD_DENOISED_RATE_PER_STREAM, "Kind
 
 constexpr int kStreams = 2, kChannels = 1, kTicks = 2;
 int g_fail = 0;
+std::string g_note;  // what the run without a failure adds to its scenario's line
 fvad_model *g_model = nullptr;
 
 #define CHECK(cond, ...)            \
@@ -271,16 +286,37 @@ long run(const Kind &k, long fail_at) {
   }
   const size_t n_in = (size_t)kTicks * (size_t)offsets[kStreams];
   const int32_t stream0 = 0;
+  constexpr int kDeferMax = 3, kSerialEvery = 5, kChunk = 7;
   if (k.machines) {
+    // the machines' and the feed's hooks, set before either exists
+    step("set_debug", [&] {
+      return fvad_engine_set_debug(e, FVAD_DEBUG_VADM_DEFER_MAX, kDeferMax) < 0 ||
+             fvad_engine_set_debug(e, FVAD_DEBUG_VADM_PAR_SERIAL_EVERY, kSerialEvery) < 0 ||
+             fvad_engine_set_debug(e, FVAD_DEBUG_EVENTS_CHUNK, kChunk) < 0;
+    });
     step("attach_vadm", [&] { return fvad_engine_attach_vadm(e, &vc, 1, 4) < 0; }, true);
     step("enable_events", [&] { return fvad_engine_enable_events(e, 16) < 0; }, true);
   }
+  g_last_vadm = fvad::VadmArgs{};
+  g_last_vadm_events = fvad::VadmEventArgs{};
   float *slot = nullptr;
   step("input_slot", [&] { return (slot = fvad_engine_input_slot(e)) == nullptr; });
   step("submit", [&] {
     std::memset(slot, 0, n_in * sizeof(float));
     return fvad_engine_submit(e, slot, kTicks, nullptr) < 0;
   });
+  if (k.machines) {  // the first push's machine pass and event pass run at the sync
+    step("sync", [&] { return fvad_engine_sync(e) < 0; });
+    if (!over && g_fail == fails_before) {
+      CHECK(g_last_vadm.n == 1 && g_last_vadm.defer_max == (unsigned)kDeferMax &&
+                g_last_vadm.par_serial_every == kSerialEvery,
+            "%s: hooks set before attach_vadm: launch_vadm saw n %d, defer_max %u, par_serial_every %d", k.name,
+            g_last_vadm.n, g_last_vadm.defer_max, g_last_vadm.par_serial_every);
+      CHECK(g_last_vadm_events.n_machines == 1 && g_last_vadm_events.chunk == kChunk,
+            "%s: hook set before enable_events: launch_vadm_events saw n_machines %d, chunk %d", k.name,
+            g_last_vadm_events.n_machines, g_last_vadm_events.chunk);
+    }
+  }
   if (per_stream) {  // between two pushes: the next one syncs both plans' tables a second time (a second staging row each)
     const int rate = 16000;
     step("set_stream_rates", [&] { return fvad_engine_set_stream_rates(e, &stream0, 1, &rate) < 0; });
@@ -308,6 +344,27 @@ long run(const Kind &k, long fail_at) {
     int n = 0;
     return fvad_engine_kernel_times(e, ms, &n) < 0;
   });
+  // every timer's runs (0: a null pointer's place where the kind has no such timer), then cleared
+  auto timing_runs = [&](int *n) {
+    double ms[FVAD_MAX_TIMES];
+    bool bad = fvad_engine_kernel_times(e, ms, &n[0]) < 0;
+    if (k.machines) bad = bad || fvad_engine_event_times(e, ms, &n[1]) < 0;
+    if (k.rate) bad = bad || fvad_engine_resample_times(e, ms, &n[2]) < 0 || fvad_engine_resample_out_times(e, ms, &n[3]) < 0;
+    return bad || fvad_engine_reset_times(e, ms, &n[4]) < 0;
+  };
+  int runs[7] = {}, after[7] = {};
+  step("timing runs", [&] { return timing_runs(runs); });
+  step("clear_times", [&] { return fvad_engine_clear_times(e) < 0; });
+  step("timing runs after clear_times", [&] { return timing_runs(after); });
+  if (!over && g_fail == fails_before) {
+    if (fail_at < 0) {
+      char note[160];
+      std::snprintf(note, sizeof(note), "; timed runs: kernels %d, event feed %d, resample %d, resample_out %d, reset %d/%d/%d",
+                    runs[0], runs[1], runs[2], runs[3], runs[4], runs[5], runs[6]);
+      g_note = note;
+    }
+    for (int i = 0; i < 7; i++) CHECK(after[i] == 0, "%s: timer %d reads %d runs after clear_times", k.name, i, after[i]);
+  }
   fvad_engine_destroy(e);
   all_released("after destroy", k.name, fail_at);
   CHECK(fail_at < 0 || fail_at < g_creates, "%s: creating call %ld was never reached (%ld made)", k.name, fail_at,
@@ -457,7 +514,8 @@ int main() {
     long done = 0;
     for (long f = 0; f < n; f++)
       if (scenario(f) >= 0) done++;
-    std::printf("%s: %ld creating calls, %ld of them failed in turn and survived\n", name, n, done);
+    std::printf("%s: %ld creating calls, %ld of them failed in turn and survived%s\n", name, n, done, g_note.c_str());
+    g_note.clear();
     CHECK(done == n, "%s: %ld of %ld failure runs passed", name, done, n);
   };
   for (const Kind &k : kKinds) every_failure(k.name, [&](long f) { return run(k, f); });

@@ -319,7 +319,8 @@ def test_engine_objects_export_only_the_api(fvad_mod):
     hdr = open(os.path.join(ROOT, "include", "fvad.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     api = set(re.findall(r"\b(fvad_[A-Za-z0-9_]*)\s*\(", hdr)) | {"fvad_engine_set_raw_s16"}
-    units = ["fvad_engine", "fvad_engine_ingest", "fvad_engine_rates", "fvad_engine_vadm", "fvad_engine_lifecycle"]
+    units = ["fvad_engine", "fvad_engine_create", "fvad_engine_ingest", "fvad_engine_rates", "fvad_engine_vadm",
+             "fvad_engine_events", "fvad_engine_lifecycle"]
     subprocess.check_call(["make", "-s", "-j", "4", "-C", PKG] + ["build/%s.cpp.o" % u for u in units])
     objs = sorted(glob.glob(os.path.join(PKG, "build", "fvad_engine*.cpp.o")))
     assert len(objs) == len(units), objs
